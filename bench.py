@@ -2,6 +2,7 @@
 """bench.py - rollout steps/s of the ACE2-shape 1-degree SFNO on N MI355X (one ensemble member per GPU).
 
     python bench.py --gpus 1 --steps 40 --warmup 5
+    python bench.py --gpus 1 --steps 40 --warmup 5 --dump-outputs DIR     # + the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -258,15 +259,34 @@ def multi_gpu_block(world, ranks_info, allreduce_bytes):
             "timing": "max over ranks of [barrier; K steps; one ensemble-mean all-reduce; sync; barrier]"}
 
 
-def time_mode(stepper, precision, forcing_names, prog, dist, dev, K, Wm, graph, world, rank, zero=False, engine_factory=None):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(eng, K, out_dir):
+    """--dump-outputs: every output plane the timed path wrote in its last timed step (window position K - 1), as the caller of
+    the engine receives it in `eng.out`, one float32 `<name>.npy` per field.  The ACE2-shape state is 50 x 180 x 360 x 4 B = 13 MB."""
+    import numpy as np
+    planes = {n: eng.out[n][:, K - 1].detach().cpu().numpy().astype(np.float32) for n in sorted(eng.out)}
+    total = sum(p.nbytes for p in planes.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for n, p in planes.items():
+        np.save(os.path.join(out_dir, f"{n}.npy"), p)
+
+
+def time_mode(stepper, precision, forcing_names, prog, dist, dev, K, Wm, graph, world, rank, zero=False, engine_factory=None,
+              dump_dir=None):
     """One precision mode: K timed steps (barrier + sync on both sides, max over ranks) + per-stage HIP-event times.
-    engine_factory(K, rank) -> engine: a stand-in engine (CPU test of the N > 1 orchestration); no stage timing then."""
+    engine_factory(K, rank) -> engine: a stand-in engine (CPU test of the N > 1 orchestration); no stage timing then.
+    dump_dir: rank 0 writes the outputs of the last timed step there (dump_outputs), after the timed region."""
     from ace_amd.distributed import AsyncEnsembleMean
     if engine_factory is not None:
         eng = engine_factory(K, rank)
         shape = (len(eng.out_names), *eng.out[eng.out_names[0]].shape[-2:])
         ens = AsyncEnsembleMean(shape, dev, dist)
         dt, allreduce_ms = timed_window(eng, ens, dist, dev, K, Wm, world)
+        if dump_dir is not None and rank == 0:
+            dump_outputs(eng, K, dump_dir)
         return dict(dt=dt, stages=None, x_cpu=None, y_gpu=None, allreduce_ms=allreduce_ms, allreduce_bytes=ens.buf.numel() * 4,
                     ensemble_mean=ens.result().clone())
     from ace_amd import _lib
@@ -288,6 +308,8 @@ def time_mode(stepper, precision, forcing_names, prog, dist, dev, K, Wm, graph, 
     eng.load(ic, fc)
     ens = AsyncEnsembleMean((len(eng.out_names), *IMG), dev, dist)   # side stream + events: the step stream never waits for RCCL
     dt, allreduce_ms = timed_window(eng, ens, dist, dev, K, Wm, world)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(eng, K, dump_dir)
 
     stages = None
     if rank == 0:  # per-stage HIP-event timing of the forward, on the stream the kernels are launched on
@@ -489,7 +511,12 @@ def main(argv=None, engine_factory=None, device=None):
                          "instruction streams, no operand switching; the line is marked invalid as a result")
     ap.add_argument("--hooks", action="store_true",
                     help="ACE2-style post-step physics (atmosphere corrector + prescribed-SST ocean) inside the timed loop")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the output fields of the last timed step of the headline mode as DIR/<name>.npy "
+                         "(float32); weights and inputs are seeded, so two builds can be compared field by field")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from ace_amd.distributed import Distributed
     from ace_amd.sfno import DEFAULT_PRECISION
@@ -526,7 +553,7 @@ def main(argv=None, engine_factory=None, device=None):
     if engine_factory is not None:
         modes = modes[:1]
     runs = {m: time_mode(stepper, m, forcing, prog, dist, dev, K, Wm, args.graph, world, rank, zero=args.zero_data,
-                         engine_factory=engine_factory) for m in modes}
+                         engine_factory=engine_factory, dump_dir=args.dump_outputs if m == modes[0] else None) for m in modes}
     ranks_info = gather_rank_records(dist, dev, rank, local_rank, world, runs[modes[0]]["allreduce_ms"])
 
     result = None

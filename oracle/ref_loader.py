@@ -25,6 +25,10 @@ import typing
 
 REF = os.environ.get("ACE_REFERENCE_ROOT", "/root/reference")
 
+# Fixtures are emitted under MKL's processor-independent code path, the one the test session runs under (tests/conftest.py):
+# seeded initialisation goes through torch's CPU erfinv, whose last bits otherwise depend on the processor.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
 
 def available() -> bool:
     return os.path.isdir(os.path.join(REF, "fme"))

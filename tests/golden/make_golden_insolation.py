@@ -1,9 +1,10 @@
-"""Emit tests/golden/gen_insolation.pt from the reference's own insolation (fme/ace/stepper/insolation/cm4.py, imported through
+"""Emit tests/golden/gen_insolation_<case>.npz from the reference's own insolation (fme/ace/stepper/insolation/cm4.py, imported through
 oracle/ref_loader.load_insolation - build container only; the stand-in for cftime's datetimes is the standard library's
 datetime.datetime, see there).  First the reference is run on the inputs of ITS OWN regression test
 (test_insolation.py:125-158) and must reproduce the golden tensor it holds (tests/golden/ref_insolation_*.pt, copied data) -
 that pins the stand-in; then cases the reference's tests do not hold are emitted: a coarse global grid over a year of 6-hourly
 times, 3-hourly and 1-hourly timesteps, other orbital parameters, a named (time-varying, fp64) solar constant, the pole rows.
+One compressed file per case: the night side is exactly zero, which halves what the repository holds.
 
 Run:  python tests/golden/make_golden_insolation.py"""
 import datetime
@@ -66,9 +67,12 @@ def main():
     g = torch.Generator().manual_seed(0)
     s0 = (1360.0 + torch.rand(1, 5, 36, 72, generator=g, dtype=torch.float64))
     case("named_fp64_solar_constant", R.proleptic_gregorian, (2030, 2, 27, 18), 6, 5, glat, glon, s0)
-    out = os.path.join(HERE, "gen_insolation.pt")
-    torch.save({"cases": cases}, out)
-    print("wrote", out, os.path.getsize(out), "bytes")
+    for c in cases:
+        out = os.path.join(HERE, f"gen_insolation_{c['name']}.npz")
+        np.savez_compressed(out, calendar=c["calendar"], components=np.array(c["components"], dtype=np.int64),
+                            timestep_seconds=c["timestep_seconds"], orbit=np.array(c["orbit"], dtype=np.float64),
+                            **{k: c[k].numpy() for k in ("lat", "lon", "solar_constant", "out")})
+        print("wrote", out, os.path.getsize(out), "bytes")
 
 
 if __name__ == "__main__":

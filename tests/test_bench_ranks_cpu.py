@@ -45,7 +45,9 @@ WORKER = textwrap.dedent(
         return engines[-1]
 
     K, W = 5, 2
-    res = bench.main(["--gpus", "2", "--steps", str(K), "--warmup", str(W), "--graph", StubEngine.graph_mode], engine_factory=factory, device="cpu")
+    dump = ["--dump-outputs", os.environ["STUB_DUMP"]] if os.environ.get("STUB_DUMP") else []
+    res = bench.main(["--gpus", "2", "--steps", str(K), "--warmup", str(W), "--graph", StubEngine.graph_mode] + dump, engine_factory=factory,
+                     device="cpu")
     rank = int(os.environ["RANK"])
     eng = engines[0]
     # warm-up W steps (or one window) untimed, then exactly K timed steps
@@ -62,10 +64,10 @@ WORKER = textwrap.dedent(
 )
 
 
-def _run(tmp_path, graph):
+def _run(tmp_path, graph, dump=""):
     script = tmp_path / "worker.py"
     script.write_text(WORKER)
-    env = dict(os.environ, ACE_ROOT=ROOT, FME_FORCE_CPU="1", OMP_NUM_THREADS="1", STUB_GRAPH=graph)
+    env = dict(os.environ, ACE_ROOT=ROOT, FME_FORCE_CPU="1", OMP_NUM_THREADS="1", STUB_GRAPH=graph, STUB_DUMP=dump)
     port = 31500 + (os.getpid() % 2000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), str(script)]
@@ -91,3 +93,16 @@ def test_bench_rank_orchestration_world_size_2(tmp_path):
 def test_bench_rank_orchestration_window_graph(tmp_path):
     d = _run(tmp_path, "window")
     assert d["n_gpus"] == 2 and d["config"]["graph"] == "window"
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes each output field of the last timed step (K - 1 = 4) as float32 DIR/<name>.npy"""
+    import numpy as np
+    out = tmp_path / "dump"
+    d = _run(tmp_path, "step", dump=str(out))
+    assert d["steps"] == 5
+    assert sorted(os.listdir(out)) == ["a.npy", "b.npy", "c.npy"]
+    for i, n in enumerate("abc"):
+        a = np.load(out / f"{n}.npy")
+        assert a.dtype == np.float32 and a.shape == (1, 4, 8)
+        assert (a == 100.0 + 10.0 * i + 4).all(), a        # rank 0's own member, field i, last timed step

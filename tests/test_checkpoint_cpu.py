@@ -168,7 +168,7 @@ def test_step_hook_order_corrector_then_ocean_then_prescribed():
         ocean={"surface_temperature_name": "sst", "ocean_fraction_name": "frac", "interpolate": False, "slab": None},
         corrector={"force_positive_names": ["q"]})
     assert set(cfg.next_step_input_names) == {"f", "frac", "sst"}          # ocean forcing names join the forcing set
-    step = SingleModuleStep(cfg, ace_amd.DatasetInfo((4, 8)), cfg.normalization.build(names), device="cpu")
+    step = SingleModuleStep(cfg, ace_amd.DatasetInfo((4, 8)), cfg.normalization.build(names, device="cpu"), device="cpu")
     step.module = Module(Net(), None)
     g = torch.Generator().manual_seed(1)
     inp = {n: torch.randn(2, 4, 8, generator=g) for n in IN}

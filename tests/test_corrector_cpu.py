@@ -117,7 +117,7 @@ def test_step_threads_corrector_state(gold):
     cfg = ace_amd.SingleModuleStepConfig(
         builder=ace_amd.ModuleSelector(type="SphericalFourierNeuralOperatorNet", config={"embed_dim": 8, "num_layers": 1}),
         in_names=in_names, out_names=out_names, normalization=norm, corrector=CONFIGS["ace2_like"])
-    step = SingleModuleStep(cfg, _info(gold), cfg.normalization.build(names), device="cpu")
+    step = SingleModuleStep(cfg, _info(gold), cfg.normalization.build(names, device="cpu"), device="cpu")
     step.module = Module(Replay([gold["gen0"], gold["gen1"]]), None)
     stepper = ace_amd.Stepper(step)
     ic = {n: gold["input0"][n][:, None] for n in prog}

@@ -254,7 +254,7 @@ def test_stepper_loop_bookkeeping_with_a_stub_module():
     cfg = ace_amd.SingleModuleStepConfig(
         builder=ace_amd.ModuleSelector(type="SphericalFourierNeuralOperatorNet", config={"embed_dim": 4, "num_layers": 1}),
         in_names=["f", "p", "g"], out_names=["p", "d"], normalization=norm, next_step_forcing_names=["g"])
-    step = SingleModuleStep(cfg, ace_amd.DatasetInfo((4, 8)), cfg.normalization.build(names), device="cpu")
+    step = SingleModuleStep(cfg, ace_amd.DatasetInfo((4, 8)), cfg.normalization.build(names, device="cpu"), device="cpu")
     step.module = Module(AddOne(), None)
     stepper = ace_amd.Stepper(step)
     g = torch.Generator().manual_seed(0)
@@ -290,7 +290,7 @@ def test_stepper_derives_the_insolation_from_the_window_times():
         builder=ace_amd.ModuleSelector(type="SphericalFourierNeuralOperatorNet", config={"embed_dim": 4, "num_layers": 1}),
         in_names=["sun", "p"], out_names=["p"], normalization=norm, next_step_forcing_names=["sun"])
     info = ace_amd.DatasetInfo((4, 8), lat=torch.linspace(-67.5, 67.5, 4), lon=torch.arange(8.0) * 45.0)
-    step = SingleModuleStep(cfg, info, cfg.normalization.build(names), device="cpu")
+    step = SingleModuleStep(cfg, info, cfg.normalization.build(names, device="cpu"), device="cpu")
     step.module = Module(Mix(), None)
     derived = {"insolation": {"insolation_name": "sun", "solar_constant": {"value": 1360.0}}}
     stepper = ace_amd.Stepper(step, derived_forcings=derived, dataset_info=info)

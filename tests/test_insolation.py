@@ -7,6 +7,7 @@
   * the properties the reference's tests assert (test_insolation.py:161-252), restated on this implementation;
 and the calendar arithmetic against the standard library and known day numbers."""
 import datetime
+import glob
 import os
 import warnings
 
@@ -108,14 +109,25 @@ def test_reference_held_golden(test_id):
     torch.testing.assert_close(_area_mean(out), torch.full((3, 2), S0 / 4), rtol=0.1, atol=0.0)
 
 
+def _reference_cases():
+    """the cases tests/golden/make_golden_insolation.py emitted from the reference, one gen_insolation_<case>.npz each"""
+    cases = []
+    for path in sorted(glob.glob(os.path.join(GOLD, "gen_insolation_*.npz"))):
+        with np.load(path) as z:
+            cases.append({"name": os.path.basename(path)[len("gen_insolation_"):-len(".npz")], "calendar": str(z["calendar"]),
+                          "components": z["components"], "timestep_seconds": int(z["timestep_seconds"]), "orbit": tuple(z["orbit"].tolist()),
+                          **{k: torch.from_numpy(z[k]) for k in ("lat", "lon", "solar_constant", "out")}})
+    return cases
+
+
 def test_against_reference_emitted_cases():
     """Whole-year, 3-hourly, hourly, pole / dateline, other orbits, fp64 named solar constant - the reference's cm4.py run in the
     build container.  Tolerance: 1e-3 W/m^2 (7e-7 of the solar constant; two fp32 ulps at 1300 W/m^2 is 2.4e-4) + 1e-6 relative -
     near the terminator the mean cos zenith is a difference of nearly equal sines over a vanishing daylight length, so a relative
     bound alone is meaningless there (the reference's CPU and GPU results differ the same way)."""
-    g = torch.load(os.path.join(GOLD, "gen_insolation.pt"))
-    assert len(g["cases"]) >= 7
-    for c in g["cases"]:
+    cases = _reference_cases()
+    assert len(cases) >= 7
+    for c in cases:
         f = CM4Insolation(*c["orbit"])
         time = TimeAxis.from_components(c["calendar"], c["components"])
         lat, lon = torch.meshgrid(c["lat"], c["lon"], indexing="ij")
@@ -241,8 +253,9 @@ def test_insolation_on_the_device_matches_the_reference_cases():
     """Same cases, computed on the MI355X (ATen elementwise kernels; sin / cos differ from the host's by an ulp): the same
     absolute bound as on the host."""
     dev = torch.device("cuda")
-    g = torch.load(os.path.join(GOLD, "gen_insolation.pt"))
-    for c in g["cases"]:
+    cases = _reference_cases()
+    assert len(cases) >= 7
+    for c in cases:
         f = CM4Insolation(*c["orbit"])
         time = TimeAxis.from_components(c["calendar"], c["components"])
         lat, lon = torch.meshgrid(c["lat"].to(dev), c["lon"].to(dev), indexing="ij")

@@ -69,7 +69,7 @@ def test_stepper_masks_inputs_and_outputs():
     mask[:2] = 0.0                                          # rows 0-1: no valid data
     provider = SpatialMaskProvider({"mask_2d": mask})
     info = ace_amd.DatasetInfo((4, 8), mask_provider=provider)
-    step = SingleModuleStep(cfg, info, cfg.normalization.build(names), device="cpu")
+    step = SingleModuleStep(cfg, info, cfg.normalization.build(names, device="cpu"), device="cpu")
     step.module = Module(Net(), None)
     stepper = ace_amd.Stepper(step, dataset_info=info, input_masking={"mask_value": 0, "fill_value": "mean"})
     ic = {"p": torch.full((1, 1, 4, 8), 5.0)}

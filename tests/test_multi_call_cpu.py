@@ -81,15 +81,18 @@ def _stub_stepper(multi_call=None):
         builder=ace_amd.ModuleSelector(type="SphericalFourierNeuralOperatorNet", config={"embed_dim": 4, "num_layers": 1}),
         in_names=["co2", "T_0"], out_names=["T_0", "ULWRFtoa"], normalization=norm)
     info = ace_amd.DatasetInfo((4, 8))
-    step = SingleModuleStep(cfg, info, cfg.normalization.build(names), device="cpu")
+    step = SingleModuleStep(cfg, info, cfg.normalization.build(names, device="cpu"), device="cpu")
     step.module = Module(Net(), None)
     return ace_amd.Stepper(step, dataset_info=info, multi_call=multi_call)
 
 
 @pytest.mark.parametrize("batched", [False, True])
-def test_stepper_reports_the_multi_call_diagnostics(batched):
+def test_stepper_reports_the_multi_call_diagnostics(batched, monkeypatch):
     """Stepper.predict with multi-call: the diagnostics are the step re-evaluated with the scaled forcing; the state that is fed
     back and the plain outputs are untouched (multi_call.py:296-312)."""
+    # a host-only stepper: the normaliser the multi-call wrapper extends is placed, like the reference's, on the default device,
+    # which is the GPU on a machine that has one
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     mc = {"forcing_name": "co2", "forcing_multipliers": {"_doubled_co2": 2.0, "_halved_co2": 0.5}, "output_names": ["ULWRFtoa"]}
     plain, multi = _stub_stepper(), _stub_stepper()
     multi.replace_multi_call(mc, batched=batched)
