@@ -120,6 +120,19 @@ SIGNATURES = {
     # x, w, bias, tmp, y, imgs, cin, cout, H, W, pitch_in, pitch_out, plane_stride_out, act, cap, xmax, ymax, stream
     "ace_hpx_tconv2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_long,
                                c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "ace_ll_last_error": (c_char_p, []),
+    # x, x_img_stride, x_chan_stride, x_pitch, c, H, W, p, circular, hi, lo, pitch_p, imgs, ss, ss_img_stride, act, cap, xmax, bscale, boff,
+    # pmax, stream
+    "ace_ll_pad_planes": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                  c_void_p, c_long, c_int, c_float, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    # x, img_stride, chan_stride, pitch, imgs, c, H, W, eps, gamma, beta, ss, mean_var, amax, stream
+    "ace_ll_norm_stats": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
+    "ace_ll_pool2": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_long, c_int, c_long, c_void_p, c_void_p]),
+    # x, planes, h, w, pitch_x, plane_stride_x, skip, pitch_skip, plane_stride_skip, y, H, W, pitch_y, plane_stride_y, circular, periodic,
+    # amax, stream
+    "ace_ll_upsample2_add": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_long, c_void_p, c_int, c_long, c_void_p, c_int, c_int, c_int,
+                                     c_long, c_int, c_int, c_void_p, c_void_p]),
     "ace_physics_last_error": (c_char_p, []),
     "ace_physics_create": (c_int, [POINTER(PhysConfig), c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "ace_physics_destroy": (None, [c_void_p]),

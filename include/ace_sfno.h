@@ -370,6 +370,37 @@ int ace_hpx_tconv2(const float* x, const ace_hpx_weight* w, const float* bias, f
                    int W, int pitch_in, int pitch_out, long plane_stride_out, int act, float cap, const unsigned* xmax, unsigned* ymax,
                    void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Lat-lon UNet glue (the Samudra ocean emulator, fme/ace/models/ocean/m2lines/): activations are [img][channel][H][pitch] fp32
+ * (pitch >= W; gap columns [W, pitch) defined) with a bound slot as above; the convolutions are ace_hpx_conv_packed /
+ * ace_hpx_conv1_packed on the P-format planes ace_ll_pad_planes writes.  Stream-ordered; no allocation or host synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+const char* ace_ll_last_error(void);
+/* hi / lo [imgs][cpad / 8][(H + 2p) x pitch_p cells][8] (cpad = c rounded up to 8, the extra channels zero; + ACE_HPX_SLACK_FLOATS zero
+ * entries behind each, kept allocated by the caller) <- the halo-padded act(scale x + shift): longitude circular (circular = 1, p <= W)
+ * or zero, latitude zero, gap columns [W + 2p, pitch_p) zero.  ss (optional): (scale, shift) float pairs at ss[2 (img ss_img_stride + ch)]
+ * (ss_img_stride 0: one pair per channel).  act 0 none / 1 GELU(erf) clamped from above at cap.  The planes are scaled by the bound
+ * act_bound(bscale bound(xmax) + boff) published to pmax (xmax: bound of the affine's input, or of its output with bscale 1, boff 0);
+ * after a capped GELU the bound is max(min(cap, b), 0.17).  p = 0: the operand of a 1 x 1 convolution. */
+int ace_ll_pad_planes(const float* x, long x_img_stride, long x_chan_stride, int x_pitch, int c, int H, int W, int p, int circular,
+                      void* hi, void* lo, int pitch_p, int imgs, const float* ss, long ss_img_stride, int act, float cap,
+                      const unsigned* xmax, float bscale, float boff, unsigned* pmax, void* stream);
+/* Instance-norm statistics of the H x W interior of every (img, channel) plane: mean and biased variance (two passes, fp64
+ * accumulation of (x - mean)^2), emitted as ss[2 plane] = gamma / sqrt(var + eps), ss[2 plane + 1] = beta - mean scale
+ * (gamma / beta optional, per channel); mean_var (optional): (mean, var) pairs; amax: bound slot of the normalised planes. */
+int ace_ll_norm_stats(const float* x, long img_stride, long chan_stride, int pitch, int imgs, int c, int H, int W, float eps,
+                      const float* gamma, const float* beta, float* ss, float* mean_var, unsigned* amax, void* stream);
+/* nn.AvgPool2d(2) with floor at odd H / W: y [planes][H / 2][pitch_out] (gap columns zeroed); amax: bound slot of y. */
+int ace_ll_pool2(const float* x, float* y, long planes, int H, int W, int pitch_in, long plane_stride_in, int pitch_out,
+                 long plane_stride_out, unsigned* amax, void* stream);
+/* y [planes][H][pitch_y] = pad(Upsample(x2, bilinear, align_corners false)) + skip: x [planes][h][pitch_x] interpolated to 2h x 2w
+ * (periodic = 1: periodic in longitude - the reference's ZonallyPeriodicBilinearUpsample), then padded to the skip's H x W by
+ * ((H - 2h) / 2, rest) rows of zeros and ((W - 2w) / 2, rest) columns, circular (circular = 1) or zero; amax: bound slot of y. */
+int ace_ll_upsample2_add(const float* x, long planes, int h, int w, int pitch_x, long plane_stride_x, const float* skip, int pitch_skip,
+                         long plane_stride_skip, float* y, int H, int W, int pitch_y, long plane_stride_y, int circular, int periodic,
+                         unsigned* amax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
