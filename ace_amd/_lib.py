@@ -56,6 +56,27 @@ class PhysFields(ctypes.Structure):
                 ("prescribed_dst", Plane * MAX_PRESCRIBED), ("prescribed_src", Plane * MAX_PRESCRIBED), ("nprescribed", c_int)]
 
 
+# ---- ocean corrector (ace_ocean_phys_*): struct ace_ocean_config / ace_ocean_fields
+OCEAN_MAX_LEVELS, OCEAN_MAX_POSITIVE, OCEAN_MAX_ZERO = 64, 40, 8
+
+
+class OceanConfig(ctypes.Structure):
+    """struct ace_ocean_config"""
+    _fields_ = [("nlat", c_int), ("nlon", c_int), ("nlev", c_int), ("max_batch", c_int), ("sea_ice", c_int),
+                ("remove_negative_ocean_fraction", c_int), ("hfds", c_int), ("ohc", c_int), ("timestep_seconds", c_double),
+                ("unaccounted_heating", c_double)]
+
+
+class OceanFields(ctypes.Structure):
+    """struct ace_ocean_fields"""
+    _fields_ = [("positive", Plane * OCEAN_MAX_POSITIVE), ("npositive", c_int), ("sif", Plane), ("zero", Plane * OCEAN_MAX_ZERO),
+                ("nzero", c_int), ("hfds", Plane), ("hfds_total_area", c_int), ("thetao", Plane * OCEAN_MAX_LEVELS), ("sst", Plane),
+                ("reb_land", Plane), ("in_land", Plane), ("in_sif", Plane), ("in_sst", Plane), ("in_sif_is_ocean_sif", c_int),
+                ("thetao_in", Plane * OCEAN_MAX_LEVELS), ("in_flux", Plane), ("in_ssf", Plane), ("in_ssf_is_land", c_int),
+                ("flux_source", c_int), ("dlw", Plane), ("ulw", Plane), ("dsw", Plane), ("usw", Plane), ("lhf", Plane), ("shf", Plane),
+                ("precip", Plane), ("frozen", Plane), ("frozen_parts", Plane * 3), ("f_ssf", Plane), ("f_ssf_is_land", c_int),
+                ("hfgeou", Plane)]
+
 
 # every symbol include/ace_sfno.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -140,10 +161,15 @@ SIGNATURES = {
     "ace_physics_set_reference": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "ace_physics_get_reference": (c_int, [c_void_p, c_void_p, POINTER(c_int), c_int, c_void_p]),
     "ace_physics_apply": (c_int, [c_void_p, POINTER(PhysFields), c_int, c_void_p]),
+    "ace_ocean_phys_last_error": (c_char_p, []),
+    "ace_ocean_phys_create": (c_int, [POINTER(OceanConfig), c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "ace_ocean_phys_destroy": (None, [c_void_p]),
+    "ace_ocean_phys_apply": (c_int, [c_void_p, POINTER(OceanFields), c_int, c_void_p]),
+    "ace_ocean_phys_launches": (c_int, [c_void_p, POINTER(c_long), POINTER(c_long)]),
 }
 
 _lib = None
-TEST_INSTRUMENTATION = ("ace_sht_plan_route", "ace_sfno_sht_route")   # queries of the parity tests, not used by the product path
+TEST_INSTRUMENTATION = ("ace_sht_plan_route", "ace_sfno_sht_route", "ace_ocean_phys_launches")   # queries of the parity tests, not used by the product path
 
 
 class AceLibraryMissing(RuntimeError):

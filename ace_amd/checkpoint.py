@@ -165,12 +165,20 @@ def stepper_config_from_state(state: Mapping[str, Any], ignore_unsupported: bool
     labels = ds_state.get("all_labels") or None
     # geometry for the conservation correctors: latitudes (or legacy area weights) and hybrid-sigma coefficients
     hc = ds_state.get("horizontal_coordinates") or {}
-    vc = ds_state.get("vertical_coordinate") or {}
+    vc_state = ds_state.get("vertical_coordinate")
+    vc = vc_state or {}
     go = ds_state.get("gridded_operations") or {}
     area = go.get("state", {}).get("area_weights") if isinstance(go, Mapping) else None
     dataset_info = DatasetInfo(_img_shape_from_dataset_state(ds_state), all_labels=set(labels) if labels else None,
                                timestep=_timestep_from_dataset_state(ds_state), lat=hc.get("lat"), lon=hc.get("lon"),
-                               ak=vc.get("ak"), bk=vc.get("bk"), area_weights=area, mask_provider=provider)
+                               ak=vc.get("ak"), bk=vc.get("bk"), area_weights=area, mask_provider=provider,
+                               depth_coordinate=vc if "idepth" in vc else None)
+    from .ocean_corrector import OceanCorrectorConfig
+    if isinstance(config.corrector, OceanCorrectorConfig) and (vc_state is None or "ak" in vc):
+        # DatasetInfo.ocean_vertical_coordinate (fme/core/dataset_info.py:208-217) raises for anything but a depth or a null
+        # ({}) coordinate: the reference cannot build an ocean_corrector for this dataset_info either
+        raise NotImplementedError("ocean_corrector needs the checkpoint's dataset_info to carry a depth (or null) vertical "
+                                  f"coordinate, got {'none' if vc_state is None else 'a hybrid sigma-pressure one'}")
     missing = config.corrector.unsupported(dataset_info)
     if missing:
         if not ignore_unsupported:

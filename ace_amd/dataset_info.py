@@ -9,10 +9,12 @@ from typing import Optional, Set, Tuple
 class DatasetInfo:
     def __init__(self, img_shape: Tuple[int, int], all_labels: Optional[Set[str]] = None,
                  timestep: datetime.timedelta = datetime.timedelta(hours=6), lat=None, lon=None, ak=None, bk=None,
-                 area_weights=None, mask_provider=None):
+                 area_weights=None, mask_provider=None, depth_coordinate=None):
         """``lat``/``lon`` (degrees; LatLonCoordinates, fme/core/coordinates.py:608-709) give the area weights of the
         conservation correctors, ``ak``/``bk`` the hybrid sigma-pressure interfaces
-        (HybridSigmaPressureCoordinate, coordinates.py:150-280); all optional."""
+        (HybridSigmaPressureCoordinate, coordinates.py:150-280), ``depth_coordinate`` the ocean's depth coordinate (an
+        ``ace_amd.ocean_corrector.DepthCoordinate`` or its state {"idepth", "mask", "deptho"?}, coordinates.py:302-440); all
+        optional."""
         self._img_shape = (int(img_shape[-2]), int(img_shape[-1]))
         self._all_labels = set(all_labels) if all_labels else set()
         self._timestep = timestep
@@ -20,6 +22,11 @@ class DatasetInfo:
         self._vertical_coordinate = None
         self._horizontal_coordinates = None
         self._mask_provider = mask_provider          # ace_amd.masking.SpatialMaskProvider or None
+        self._depth_coordinate = None
+        if depth_coordinate is not None:
+            from .ocean_corrector import DepthCoordinate
+            self._depth_coordinate = (depth_coordinate if isinstance(depth_coordinate, DepthCoordinate)
+                                      else DepthCoordinate.from_state(depth_coordinate))
         if lat is not None and lon is not None:
             from .insolation import LatLonGrid
             import torch
@@ -59,6 +66,11 @@ class DatasetInfo:
     @property
     def vertical_coordinate(self):
         return self._vertical_coordinate
+
+    @property
+    def ocean_vertical_coordinate(self):
+        """the ocean's DepthCoordinate (what the ocean corrector's heat-content budget integrates over), or None"""
+        return self._depth_coordinate
 
     @property
     def img_shape(self) -> Tuple[int, int]:

@@ -37,6 +37,10 @@ class RolloutEngine:
         self._secondary = getattr(step, "secondary_decoder", None)
         if self._secondary is not None and graph == "window":
             raise NotImplementedError("graph='window' with a secondary decoder: its module call is not captured; use graph='step'")
+        from .ocean_corrector import OceanCorrector
+        if isinstance(step._corrector, OceanCorrector):
+            raise NotImplementedError("RolloutEngine: a stepper with an ocean corrector (ocean_corrector) runs through "
+                                      "Stepper.predict; the fused post-step physics of the engine is the atmosphere corrector's")
         if getattr(stepper, "_masks", False):
             raise NotImplementedError("RolloutEngine: static spatial masking of the step inputs / outputs (input_masking, the dataset's "
                                       "mask provider) is applied by Stepper.predict")

@@ -174,6 +174,7 @@ class SingleModuleStepConfig:
     def __post_init__(self):
         from .corrector import AtmosphereCorrectorConfig
         from .ocean import OceanConfig
+        from .ocean_corrector import OceanCorrectorConfig, corrector_config_from_state
         for field in ("global_mean_removal", "input_dropout"):
             if getattr(self, field) is not None:
                 raise NotImplementedError(f"SingleModuleStepConfig.{field} is outside the accelerated hot path")
@@ -183,10 +184,11 @@ class SingleModuleStepConfig:
             self.ocean = OceanConfig.from_state(self.ocean)
         if self.ocean is not None and not isinstance(self.ocean, OceanConfig):
             raise NotImplementedError("SingleModuleStepConfig.ocean must be an OceanConfig (prescribed SST or slab ocean) or its state")
-        if not isinstance(self.corrector, (AtmosphereCorrectorConfig, dict, type(None))):
-            raise NotImplementedError("SingleModuleStepConfig.corrector must be an AtmosphereCorrectorConfig or its state")
+        if not isinstance(self.corrector, (AtmosphereCorrectorConfig, OceanCorrectorConfig, dict, type(None))):
+            raise NotImplementedError("SingleModuleStepConfig.corrector must be an AtmosphereCorrectorConfig, an "
+                                      "OceanCorrectorConfig or its state")
         if self.corrector is None or isinstance(self.corrector, dict):
-            self.corrector = AtmosphereCorrectorConfig.from_state(self.corrector)
+            self.corrector = corrector_config_from_state(self.corrector)
         if self.include_channel_mask_inputs:
             raise NotImplementedError("include_channel_mask_inputs is outside the accelerated hot path")
         for name in self.prescribed_prognostic_names:

@@ -401,6 +401,72 @@ int ace_ll_upsample2_add(const float* x, long planes, int h, int w, int pitch_x,
                          long plane_stride_skip, float* y, int H, int W, int pitch_y, long plane_stride_y, int circular, int periodic,
                          unsigned* amax, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ocean corrector (fme/core/corrector/ocean.py, "ocean_corrector"): force positive -> sea-ice fraction clamp / rebalance /
+ * zeroing -> surface energy flux (hfds) correction -> ocean heat content budget, in place on the output planes of one step.
+ * Two launches: O1 (one column per thread: every column-local correction, the columns' heat contents and net flux into the
+ * ocean, fp64 partial sums per workgroup of the masked area-weighted means), O2 (per sample: the partials re-summed in a
+ * fixed order, the ratio in fp64, every thetao level and the SST scaled).  No atomics, no allocation, no host
+ * synchronisation; input and forcing planes are only read.  Planes: ace_phys_plane, p = NULL means "absent".
+ * ------------------------------------------------------------------------------------------ */
+#define ACE_OCEAN_MAX_LEVELS 64
+#define ACE_OCEAN_MAX_POSITIVE 40
+#define ACE_OCEAN_MAX_ZERO 8
+
+typedef struct ace_ocean_config {
+    int nlat, nlon;
+    int nlev;                          /* depth layers (the dz table has nlev planes); 0 without the heat-content correction */
+    int max_batch;
+    int sea_ice;                       /* SeaIceFractionConfig present */
+    int remove_negative_ocean_fraction;
+    int hfds;                          /* 0 none, 1 "residual_prediction", 2 "prescribed" */
+    int ohc;                           /* 0 none, 1 "scaled_temperature" */
+    double timestep_seconds;
+    double unaccounted_heating;        /* OceanHeatContentBudgetConfig.constant_unaccounted_heating */
+} ace_ocean_config;
+
+typedef struct ace_ocean_fields {
+    /* output of the step, corrected in place */
+    ace_phys_plane positive[ACE_OCEAN_MAX_POSITIVE];   /* force_positive_names */
+    int npositive;
+    ace_phys_plane sif;                            /* sea_ice_fraction_name */
+    ace_phys_plane zero[ACE_OCEAN_MAX_ZERO];       /* zero_where_ice_free_names */
+    int nzero;
+    ace_phys_plane hfds;                           /* hfds, or hfds_total_area (hfds_total_area = 1) */
+    int hfds_total_area;
+    ace_phys_plane thetao[ACE_OCEAN_MAX_LEVELS];   /* thetao_0 .. thetao_{nlev-1} */
+    ace_phys_plane sst;                            /* optional */
+    /* input of the step (read only) */
+    ace_phys_plane reb_land;                       /* input[land_fraction_name] of the sea-ice rebalance */
+    ace_phys_plane in_land, in_sif, in_sst;        /* ocean fraction 1 - land - sif; sst of the net flux */
+    int in_sif_is_ocean_sif;                       /* in_sif is ocean_sea_ice_fraction: sif = it * (1 - land) */
+    ace_phys_plane thetao_in[ACE_OCEAN_MAX_LEVELS];
+    ace_phys_plane in_flux, in_ssf;                /* heat-budget flux from the input (flux_source 2 / 3) */
+    int in_ssf_is_land;                            /* in_ssf holds land_fraction: ssf = 1 - it */
+    int flux_source;                               /* 0 output hfds_total_area, 1 output hfds, 2 input hfds,
+                                                      3 input hfds_total_area / input sea-surface fraction */
+    /* next step's forcing (read only) */
+    ace_phys_plane dlw, ulw, dsw, usw, lhf, shf, precip;
+    ace_phys_plane frozen, frozen_parts[3];        /* total_frozen_precipitation_rate, or ICE + GRAUPEL + SNOW; absent: 0 */
+    ace_phys_plane f_ssf;                          /* sea_surface_fraction, or land_fraction (f_ssf_is_land = 1) */
+    int f_ssf_is_land;
+    ace_phys_plane hfgeou;                         /* optional: absent is 0 */
+} ace_ocean_fields;
+
+typedef struct ace_ocean_phys ace_ocean_phys;
+const char* ace_ocean_phys_last_error(void);
+/* area_weights_lat_host: nlat fp32 weights per row; dz_host: (nlev, nlat, nlon) fp32 layer thicknesses (DepthCoordinate.dz,
+ * zero where masked); mask_ohc_host: (nlat, nlon) fp32 mask the provider gives for "ocean_heat_content" (NULL: none);
+ * mask0_host: (nlat, nlon) fp32 top-level ocean mask (heat content is NaN where it is 0).  All but the first may be NULL
+ * without the heat-content correction. */
+int ace_ocean_phys_create(const ace_ocean_config* cfg, const float* area_weights_lat_host, const float* dz_host,
+                          const float* mask_ohc_host, const float* mask0_host, ace_ocean_phys** out);
+void ace_ocean_phys_destroy(ace_ocean_phys* h);
+/* One step; `fields` is a HOST struct of device planes (copied into the kernel arguments). */
+int ace_ocean_phys_apply(ace_ocean_phys* h, const ace_ocean_fields* fields, int batch, void* stream);
+/* Route query: O1 / O2 launches this handle has made. */
+int ace_ocean_phys_launches(const ace_ocean_phys* h, long* o1, long* o2);
+
 #ifdef __cplusplus
 }
 #endif
