@@ -28,6 +28,7 @@ from .insolation import InsolationConfig  # noqa: F401
 from .derived_forcings import DerivedForcingsConfig, ForcingDeriver, ForcingWindow  # noqa: F401
 from .multi_call import MultiCallConfig  # noqa: F401
 from .stepper import PrognosticState, Stepper  # noqa: F401
+from .ocean_rollout import OceanRolloutEngine  # noqa: F401
 from .inference import EnginePredict, ForcingWindows, InferenceData, Looper, TensorFileWriter, run_inference  # noqa: F401
 
 __version__ = "0.1.0"

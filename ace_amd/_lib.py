@@ -166,6 +166,13 @@ SIGNATURES = {
     "ace_ocean_phys_destroy": (None, [c_void_p]),
     "ace_ocean_phys_apply": (c_int, [c_void_p, POINTER(OceanFields), c_int, c_void_p]),
     "ace_ocean_phys_launches": (c_int, [c_void_p, POINTER(c_long), POINTER(c_long)]),
+    "ace_mask_last_error": (c_char_p, []),
+    # srcs, src_strides, dsts, dst_strides, mask_idx, hits, nmask, fill, nplanes, batch, hw, stream
+    "ace_mask_planes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_long,
+                                c_void_p]),
+    # srcs, src_strides, mask_idx, hits, nmask, fill, stage, stage_strides, mean, std, dst, npack, nplanes, batch, hw, stream
+    "ace_mask_pack_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
 }
 
 _lib = None

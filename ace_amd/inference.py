@@ -204,7 +204,7 @@ def run_inference(predict: Callable, data: InferenceData, aggregator=None, write
 
 
 class EnginePredict:
-    """``PredictFunction`` on the static-buffer ``RolloutEngine``: one engine per window length (the last window of a
+    """``PredictFunction`` on the static-buffer ``RolloutEngine`` (``OceanRolloutEngine`` for a Samudra stepper): one engine per window length (the last window of a
     rollout may be shorter), built on first use.  Outputs are copied out of the engine's buffers (the next window reuses them)."""
 
     def __init__(self, stepper, batch: int, graph: Optional[str] = "step", labels=None):
@@ -224,13 +224,16 @@ class EnginePredict:
 
     def __call__(self, initial_condition: TensorDict, forcing: TensorDict,
                  compute_derived_variables: bool = False) -> Tuple[TensorDict, TensorDict]:
+        from .ocean_rollout import OceanRolloutEngine
         from .rollout import RolloutEngine
+        from .samudra import Samudra
         forcing = self._stepper.forcing_deriver(forcing)      # forcings computed from the window's time axis (the insolation)
         n_steps = next(iter(forcing.values())).shape[1] - 1
         eng = self._engines.get(n_steps)
         if eng is None:
-            eng = self._engines[n_steps] = RolloutEngine(self._stepper, batch=self._batch, n_forward_steps=n_steps,
-                                                         graph=self._graph)
+            # a Samudra ocean stepper (input / output masking, the ocean corrector) runs on its own engine
+            engine = OceanRolloutEngine if isinstance(self._stepper._step_obj.module.torch_module, Samudra) else RolloutEngine
+            eng = self._engines[n_steps] = engine(self._stepper, batch=self._batch, n_forward_steps=n_steps, graph=self._graph)
             if self._labels is not None:
                 eng.set_labels(self._labels)
         out, state = eng.predict(initial_condition, forcing)

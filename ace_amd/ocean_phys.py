@@ -171,6 +171,10 @@ class FusedOceanCorrector:
                                                    torch.cuda.current_stream(self.device).cuda_stream))
         return gen
 
+    def apply(self, fields: OceanFields, stream: int) -> None:
+        """One step on planes resolved once by ``fields`` (static buffers: ``OceanRolloutEngine`` keeps a struct per step)."""
+        _check(_lib.lib().ace_ocean_phys_apply(self.handle, ctypes.byref(fields), self.batch, stream))
+
     def launches(self) -> Tuple[int, int]:
         o1, o2 = c_long(0), c_long(0)
         _check(_lib.lib().ace_ocean_phys_launches(self.handle, ctypes.byref(o1), ctypes.byref(o2)))

@@ -225,6 +225,28 @@ int ace_unpack_denormalize(const float* src, const float* mean, const float* std
                            const long* strides, int batch, int nch, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Static spatial masking (fme/core/spatial_masking.py:98-150): data[name] = fill where round(mask) == mask_value, per plane.
+ * hits: DEVICE uint8 [nmask][hw], one plane per distinct 2-D mask (broadcast over the batch), nonzero where the reference's
+ * `torch.round(mask).to(torch.int64) == mask_value` holds - computed by the caller with exactly those torch ops, so the kernels
+ * only select and their output is bitwise the torch path's.  mask_idx: DEVICE int [nplanes], the hit plane of plane j (-1: none);
+ * fill: DEVICE fp32 [nplanes].  Pointer / stride tables as in the stepper glue above (device arrays, strides in floats).
+ *   mask_planes:          dsts[j][b dst_strides[j] + p] = hit ? fill[j] : srcs[j][b src_strides[j] + p]
+ *                         (srcs[j] == dsts[j]: in place; an unmasked in-place plane is skipped, an unmasked other one copied)
+ *   mask_pack_normalize:  v = hit ? fill[j] : srcs[j][...]; stage[j] (stage NULL or a NULL entry: none) <- v;
+ *                         j < npack: dst[b][j][p] = (v - mean[j]) / std[j] with ace_pack_normalize's roundings.  Planes
+ *                         npack .. nplanes - 1 are masked and staged only.
+ * float4 accesses on a (plane, sample) whose hw % 4 == 0 and whose addresses are 16-byte aligned, scalar otherwise.
+ * Stream-ordered; no allocation or host synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+const char* ace_mask_last_error(void);
+int ace_mask_planes(const float* const* srcs, const long* src_strides, float* const* dsts, const long* dst_strides,
+                    const int* mask_idx, const unsigned char* hits, int nmask, const float* fill, int nplanes, int batch,
+                    long hw, void* stream);
+int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, const int* mask_idx, const unsigned char* hits,
+                            int nmask, const float* fill, float* const* stage, const long* stage_strides, const float* mean,
+                            const float* std_, float* dst, int npack, int nplanes, int batch, long hw, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
  * (fme/core/corrector/atmosphere.py:349-398 order, 404-700 corrections), the prescribed-SST Ocean
  * (fme/core/ocean.py:167-222, fme/core/prescriber.py:54-117) and the prescribed prognostics, applied in place on the
