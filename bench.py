@@ -3,12 +3,18 @@
 
     python bench.py --gpus 1 --steps 40 --warmup 5
     python bench.py --gpus 1 --steps 40 --warmup 5 --dump-outputs DIR     # + the last timed step's outputs as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 40 --warmup 5 --full                  # + everything beyond the headline figure
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the whole hot path over one synthetic state: gather+normalise the 44 input fields,
 the SFNO forward (8 blocks, embed 384, 180x360, fp32), scatter+denormalise the 50 output fields, feed the 36
 prognostic fields back.  Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps of the headline precision, dump the
+outputs if asked, print the line (`roofline`, `roofline_sht`, `stages` and `cpu_baseline` are null in it).  `--full` adds the
+rest: the second precision mode, per-stage HIP-event times and the rooflines, the CPU baseline and the extra legs (one-year rollout,
+S80 state).
 """
 
 import argparse
@@ -275,10 +281,11 @@ def dump_outputs(eng, K, out_dir):
 
 
 def time_mode(stepper, precision, forcing_names, prog, dist, dev, K, Wm, graph, world, rank, zero=False, engine_factory=None,
-              dump_dir=None):
+              dump_dir=None, stage_times=True):
     """One precision mode: K timed steps (barrier + sync on both sides, max over ranks) + per-stage HIP-event times.
     engine_factory(K, rank) -> engine: a stand-in engine (CPU test of the N > 1 orchestration); no stage timing then.
-    dump_dir: rank 0 writes the outputs of the last timed step there (dump_outputs), after the timed region."""
+    dump_dir: rank 0 writes the outputs of the last timed step there (dump_outputs), after the timed region.
+    stage_times: False (a plain run) skips the per-stage forwards and the host copies the CPU baseline compares against."""
     from ace_amd.distributed import AsyncEnsembleMean
     if engine_factory is not None:
         eng = engine_factory(K, rank)
@@ -311,8 +318,8 @@ def time_mode(stepper, precision, forcing_names, prog, dist, dev, K, Wm, graph, 
     if dump_dir is not None and rank == 0:
         dump_outputs(eng, K, dump_dir)
 
-    stages = None
-    if rank == 0:  # per-stage HIP-event timing of the forward, on the stream the kernels are launched on
+    stages = x_cpu = y_gpu = None
+    if rank == 0 and stage_times:  # per-stage HIP-event timing of the forward, on the stream the kernels are launched on
         L = _lib.lib()
         ns = L.ace_sfno_num_stages()
         ms = (ctypes.c_float * ns)()
@@ -338,8 +345,8 @@ def time_mode(stepper, precision, forcing_names, prog, dist, dev, K, Wm, graph, 
             stages[nm] = dict(ms_per_step=round(acc[i], 4), launches=calls[i], us_per_launch=round(per_launch_ms * 1e3, 2),
                               tflops=round(fl / per_launch_ms / 1e9, 2), gbps=round(by / per_launch_ms / 1e6, 1),
                               moved_bytes=int(moved), moved_gbps=round(moved / per_launch_ms / 1e6, 1))
-    x_cpu = eng.x.detach().cpu() if rank == 0 else None
-    y_gpu = eng.y.detach().cpu() if rank == 0 else None
+        x_cpu = eng.x.detach().cpu()
+        y_gpu = eng.y.detach().cpu()
     del eng
     torch.cuda.empty_cache()
     return dict(dt=dt, stages=stages, x_cpu=x_cpu, y_gpu=y_gpu, allreduce_ms=allreduce_ms, allreduce_bytes=ens.buf.numel() * 4)
@@ -502,10 +509,13 @@ def main(argv=None, engine_factory=None, device=None):
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--graph", default="step", choices=["none", "step", "window"])
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the second precision mode, per-stage HIP-event times and rooflines, "
+                         "the CPU baseline and the extra legs")
     ap.add_argument("--precision", default="both", choices=["both", "f16x3", "fp32"],
-                    help="'both': time the default (f16x3) and the exact-fp32 arithmetic in the same run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the 1460-step and the S80 (44 in / 72 out) legs")
+                    help="'both': the default (f16x3) is the headline; with --full the exact-fp32 arithmetic is timed in the same run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the 1460-step and the S80 (44 in / 72 out) legs")
     ap.add_argument("--zero-data", action="store_true",
                     help="DIAGNOSTIC (DVFS give-back check, MI355X_MICROARCH.md): all weights and all inputs zero - same kernels, same "
                          "instruction streams, no operand switching; the line is marked invalid as a result")
@@ -550,10 +560,11 @@ def main(argv=None, engine_factory=None, device=None):
     modes = [DEFAULT_PRECISION] + (["fp32" if DEFAULT_PRECISION != "fp32" else "f16x3"] if args.precision == "both" else [])
     if args.precision in ("f16x3", "fp32"):
         modes = [args.precision]
-    if engine_factory is not None:
+    if engine_factory is not None or not args.full:
         modes = modes[:1]
     runs = {m: time_mode(stepper, m, forcing, prog, dist, dev, K, Wm, args.graph, world, rank, zero=args.zero_data,
-                         engine_factory=engine_factory, dump_dir=args.dump_outputs if m == modes[0] else None) for m in modes}
+                         engine_factory=engine_factory, dump_dir=args.dump_outputs if m == modes[0] else None,
+                         stage_times=args.full) for m in modes}
     ranks_info = gather_rank_records(dist, dev, rank, local_rank, world, runs[modes[0]]["allreduce_ms"])
 
     result = None
@@ -589,7 +600,7 @@ def main(argv=None, engine_factory=None, device=None):
         for m in modes[1:]:
             result[f"mode_{m}"] = {"value": round(world * K / runs[m]["dt"], 3), "unit": "steps/s",
                                    "ms_per_step": round(runs[m]["dt"] / K * 1e3, 4), "stages": runs[m]["stages"]}
-    if engine_factory is None and world == 1 and not args.no_extra_legs and not args.zero_data:
+    if engine_factory is None and world == 1 and args.full and not args.no_extra_legs and not args.zero_data:
         stepper.modules[0].set_precision(modes[0])
         try:
             legs = extra_legs(stepper, forcing, prog, dist, dev, K, rank, args.hooks)
