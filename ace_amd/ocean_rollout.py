@@ -16,15 +16,16 @@ Per step s the engine enqueues, in the order of ``Stepper.step`` and ``step_with
 Every handle, hit plane and workspace is made at construction or in a warm-up outside capture; nothing is allocated and the host
 never synchronises inside a window.  The masking kernels only select (their hit planes are computed with the reference's own
 torch expression), the corrector and the glue are the kernels ``Stepper.predict`` runs, so the engine differs from it only by the
-normalisation's rounding (torch division against ``__fdiv_rn``) - see tests/test_gpu_ocean_rollout.py."""
+normalisation's rounding (torch division against ``__fdiv_rn``) - see tests/test_gpu_ocean_rollout.py.
+The buffers, the window layout, the tail of the forward (3.), the graph modes and load / predict are rollout.WindowEngine's."""
 
-import ctypes
-from typing import Dict, Mapping, Optional, Tuple
+from typing import Optional
 
 import torch
 
 from . import _lib
-from .masking import StaticSpatialMasking
+from .masking import StaticSpatialMasking, _check
+from .rollout import WindowEngine, _nan_to_zero
 from .stepper import Stepper
 
 
@@ -49,10 +50,9 @@ def _refuse(what: str) -> NotImplementedError:
     return NotImplementedError(f"OceanRolloutEngine: {what}; run this stepper through Stepper.predict")
 
 
-class OceanRolloutEngine:
+class OceanRolloutEngine(WindowEngine):
     def __init__(self, stepper: Stepper, batch: int, n_forward_steps: int, graph: Optional[str] = "step"):
-        if graph not in (None, "step", "window"):
-            raise ValueError("graph must be None, 'step' or 'window'")
+        self._check_graph(graph)
         from .ocean_corrector import OceanCorrector
         from .samudra import Samudra
         step = stepper._step_obj
@@ -84,45 +84,13 @@ class OceanRolloutEngine:
                 for k, t in m._mask.masks.items():
                     if tuple(t.shape) != tuple(step._img_shape):
                         raise _refuse(f"the mask '{k}' of shape {tuple(t.shape)} is not a 2-D {tuple(step._img_shape)} plane")
-        dev = next(net.parameters()).device
-        if dev.type != "cuda":
+        if next(net.parameters()).device.type != "cuda":
             raise RuntimeError("OceanRolloutEngine runs on an MI355X: load the stepper onto a 'cuda' device (there is no CPU path)")
 
-        self.stepper, self.net, self.device = stepper, net, dev
-        self.graph_mode = graph
-        self.B, self.T = batch, n_forward_steps
-        self.H, self.W = step._img_shape
-        self.HW = self.H * self.W
-        B, T, H, W, HW = batch, n_forward_steps, self.H, self.W, self.HW
-        self.in_names, self.out_names = list(cfg.in_names), list(cfg.out_names)
-        self.prognostic = [n for n in self.out_names if n in self.in_names]
-        self.forcing_names = [n for n in self.in_names if n not in self.out_names]
-        self.next_step_forcing = set(cfg.next_step_forcing_names)
+        super().__init__(stepper, net, batch, n_forward_steps, graph)
+        dev, B, T, H, W, HW = self.device, batch, n_forward_steps, self.H, self.W, self.HW
         f32 = dict(dtype=torch.float32, device=dev)
         i64 = dict(dtype=torch.int64, device=dev)
-        self.x = torch.zeros(B, len(self.in_names), H, W, **f32)
-        self.ic = {n: torch.zeros(B, 1, H, W, **f32) for n in self.prognostic}
-        self.forcing = {n: torch.zeros(B, T + 1, H, W, **f32) for n in self.forcing_names}
-        self.out = {n: torch.zeros(B, T, H, W, **f32) for n in self.out_names}
-        norm = step.normalizer
-        self._fill_in, self._fill_out = bool(norm.fill_nans_on_normalize), bool(norm.fill_nans_on_denormalize)
-        self.in_mean = torch.stack([norm.means[n].to(dev) for n in self.in_names]).contiguous()
-        self.in_std = torch.stack([norm.stds[n].to(dev) for n in self.in_names]).contiguous()
-        self.out_mean = torch.stack([norm.means[n].to(dev) for n in self.out_names]).contiguous()
-        self.out_std = torch.stack([norm.stds[n].to(dev) for n in self.out_names]).contiguous()
-        self._res_in = self._res_out = None
-        if cfg.residual_prediction:
-            self._res_in = torch.tensor([self.in_names.index(n) for n in self.prognostic], **i64)
-            self._res_out = torch.tensor([self.out_names.index(n) for n in self.prognostic], **i64)
-
-        # ---- where step s reads its inputs and next-step data (before masking)
-        def src_in(n, s):
-            if n in self.ic:
-                return self.ic[n][:, 0] if s == 0 else self.out[n][:, s - 1]
-            return self.forcing[n][:, s + 1 if n in self.next_step_forcing else s]
-
-        def src_next(n, s):
-            return self.forcing[n][:, s + 1]
 
         # ---- the corrector: which masked planes it reads (probed once on the unmasked views), staged by the pack
         in_plan = in_mask.plan(self.in_names) if in_mask is not None else [(None, None)] * len(self.in_names)
@@ -133,9 +101,9 @@ class OceanRolloutEngine:
         if corrector is not None and corrector.corrections:
             from .ocean_phys import FusedOceanCorrector
             diag = [n for n in self.out_names if n not in self.in_names]
-            inp = _Reads({**{n: src_in(n, 0) for n in self.in_names}, **{n: self.out[n][:, 0] for n in diag}})
-            nxt = _Reads({n: src_next(n, 0) for n in self.forcing_names})
-            gen = {n: self.out[n][:, 0] for n in self.out_names}
+            inp = _Reads({**{n: self.in_plane(n, 0) for n in self.in_names}, **{n: self.out_plane(n, 0) for n in diag}})
+            nxt = _Reads({n: self.next_plane(n, 0) for n in self.forcing_names})
+            gen = {n: self.out_plane(n, 0) for n in self.out_names}
             try:
                 fc = FusedOceanCorrector(corrector, B, (H, W), dev)
                 fc.fields(inp, gen, nxt)
@@ -156,37 +124,30 @@ class OceanRolloutEngine:
 
         # ---- step tables of ace_mask_pack_normalize: planes = the inputs (packed), then the extra staged next-step planes
         planes = self.in_names + extra
-        self._nplanes = len(planes)
+        self._nplanes = n = len(planes)
         if in_mask is not None:
             self._in_idx, self._in_fill = in_mask.device_tables(planes, dev, (H, W))
             _, self._in_hits = in_mask.hit_planes(dev, (H, W))
         else:
-            self._in_idx = torch.full((len(planes),), -1, dtype=torch.int32, device=dev)
-            self._in_fill = torch.zeros(len(planes), **f32)
+            self._in_idx = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            self._in_fill = torch.zeros(n, **f32)
             self._in_hits = None
         rows = []
         for s in range(T):
-            srcs = [src_in(n, s) for n in self.in_names] + [src_next(n, s) for n in extra]
-            stages = [self.stage.get(n) for n in self.in_names] + [self.stage_next[n] for n in extra]
+            srcs = [self.in_plane(o, s) for o in self.in_names] + [self.next_plane(o, s) for o in extra]
+            stages = [self.stage.get(o) for o in self.in_names] + [self.stage_next[o] for o in extra]
             rows.append([t.data_ptr() for t in srcs] + [t.stride(0) if B > 1 else HW for t in srcs]
                         + [t.data_ptr() if t is not None else 0 for t in stages] + [HW] * len(stages))
-        self._pack_tab = torch.tensor(rows, **i64)
-        n = self._nplanes
-        base = self._pack_tab.data_ptr()
-        self._pack_addr = [(base + 8 * (4 * n * s), base + 8 * (4 * n * s + n), base + 8 * (4 * n * s + 2 * n),
-                            base + 8 * (4 * n * s + 3 * n)) for s in range(T)]
-        # unpack tables (as RolloutEngine's)
-        self._dst_ptrs = torch.tensor([[self.out[o].data_ptr() + 4 * s * HW for o in self.out_names] for s in range(T)], **i64)
-        self._dst_strides = torch.full((len(self.out_names),), T * HW, **i64)
-        self._dst_ptr_addr = [self._dst_ptrs.data_ptr() + 8 * s * len(self.out_names) for s in range(T)]
+        self._pack_tab, addr = self._table(rows)
+        self._pack_addr = [(a, a + 8 * n, a + 16 * n, a + 24 * n) for a in addr]
 
         # ---- the corrector's planes per step (static: resolved once)
         self._fields = []
         if self._fused_corrector is not None:
             for s in range(T):
-                inp = {o: (self.stage[o] if o in self.stage else src_in(o, s)) for o in self.in_names}
-                nxt = {o: (self.stage_next[o] if o in self.stage_next else src_next(o, s)) for o in self.forcing_names}
-                gen = {o: self.out[o][:, s] for o in self.out_names}
+                inp = {o: (self.stage[o] if o in self.stage else self.in_plane(o, s)) for o in self.in_names}
+                nxt = {o: (self.stage_next[o] if o in self.stage_next else self.next_plane(o, s)) for o in self.forcing_names}
+                gen = {o: self.out_plane(o, s) for o in self.out_names}
                 self._fields.append(self._fused_corrector.fields(inp, gen, nxt))
 
         # ---- the output masker, in place on out[:, s]
@@ -197,119 +158,51 @@ class OceanRolloutEngine:
         if self._out_names_masked:
             self._out_idx, self._out_fill = out_mask.device_tables(self._out_names_masked, dev, (H, W))
             _, self._out_hits = out_mask.hit_planes(dev, (H, W))
-            m = len(self._out_names_masked)
-            ptrs = [[self.out[o].data_ptr() + 4 * s * HW for o in self._out_names_masked] for s in range(T)]
-            self._omask_ptrs = torch.tensor(ptrs, **i64)
-            self._omask_strides = torch.full((m,), T * HW, **i64)
-            self._omask_addr = [self._omask_ptrs.data_ptr() + 8 * s * m for s in range(T)]
+            self._omask_ptrs, self._omask_addr = self._table([[self.out_plane(o, s).data_ptr() for o in self._out_names_masked]
+                                                              for s in range(T)])
+            self._omask_strides = torch.full((len(self._out_names_masked),), T * HW, **i64)
 
         self._captured = None          # graph="step": CapturedSamudraForward on self.x
-        self._window_graph = None
-        self._weights_key = None       # the parameters a captured graph was made with
 
     # -- one step, enqueued on the current stream
     def _enqueue_step(self, s: int, replay_forward: bool):
         L = _lib.lib()
         stream = _lib.current_stream()
-        B, HW, nin, nout = self.B, self.HW, len(self.in_names), len(self.out_names)
+        B, HW = self.B, self.HW
         srcs, src_strides, stage, stage_strides = self._pack_addr[s]
         hits = self._in_hits
-        _check_mask(L.ace_mask_pack_normalize(srcs, src_strides, self._in_idx.data_ptr(), hits.data_ptr() if hits is not None else None,
-                                              hits.shape[0] if hits is not None else 0, self._in_fill.data_ptr(), stage, stage_strides,
-                                              self.in_mean.data_ptr(), self.in_std.data_ptr(), self.x.data_ptr(), nin,
-                                              self._nplanes, B, HW, stream))
+        _check(L.ace_mask_pack_normalize(srcs, src_strides, self._in_idx.data_ptr(), hits.data_ptr() if hits is not None else None,
+                                         hits.shape[0] if hits is not None else 0, self._in_fill.data_ptr(), stage, stage_strides,
+                                         self.in_mean.data_ptr(), self.in_std.data_ptr(), self.x.data_ptr(), len(self.in_names),
+                                         self._nplanes, B, HW, stream))
         if self._fill_in:
-            torch.nan_to_num_(self.x, nan=0.0, posinf=float("inf"), neginf=float("-inf"))
+            _nan_to_zero(self.x)
         if replay_forward:
             self._captured.graph.replay()
             y = self._captured.y
         else:
             y = self.net(self.x)
-        if self._res_in is not None:
-            y.index_add_(1, self._res_out, self.x.index_select(1, self._res_in))
-        if self._fill_out:
-            torch.nan_to_num_(y, nan=0.0, posinf=float("inf"), neginf=float("-inf"))
-        _lib.check(L.ace_unpack_denormalize(y.data_ptr(), self.out_mean.data_ptr(), self.out_std.data_ptr(), self._dst_ptr_addr[s],
-                                            self._dst_strides.data_ptr(), B, nout, HW, stream))
+        self._unpack(L, stream, y, self._dst_ptr_addr[s], self._dst_strides)
         if self._fused_corrector is not None:
             self._fused_corrector.apply(self._fields[s], stream)
         if self._out_names_masked:
             a = self._omask_addr[s]
             st = self._omask_strides.data_ptr()
-            _check_mask(L.ace_mask_planes(a, st, a, st, self._out_idx.data_ptr(), self._out_hits.data_ptr(), self._out_hits.shape[0],
-                                          self._out_fill.data_ptr(), len(self._out_names_masked), B, HW, stream))
+            _check(L.ace_mask_planes(a, st, a, st, self._out_idx.data_ptr(), self._out_hits.data_ptr(), self._out_hits.shape[0],
+                                     self._out_fill.data_ptr(), len(self._out_names_masked), B, HW, stream))
 
-    def _weights_stamp(self) -> tuple:
-        return tuple((t.data_ptr(), t._version) for t in list(self.net.parameters()) + list(self.net.buffers()))
+    def _prepare_window(self):
+        step = self.stepper._step_obj
+        if step._corrector is not self._corrector or step._ocean is not None:
+            raise RuntimeError("the stepper's corrector / ocean was replaced after this OceanRolloutEngine was built: build a new one")
+        # the parameters a captured graph was made with: a change (load_state) drops the graphs holding the old weight handles
+        key = tuple((t.data_ptr(), t._version) for t in list(self.net.parameters()) + list(self.net.buffers()))
+        if self.graph_mode == "step" and (self._captured is None or key != self._graph_key):
+            from .samudra import CapturedSamudraForward
+            self._captured = CapturedSamudraForward(self.net, self.x)       # warm-up outside capture, then capture
+            self.x = self._captured.x
+        return key
 
     def set_labels(self, labels) -> None:
         if labels is not None:
             raise TypeError("Labels are not allowed for unconditional models")
-
-    def load(self, initial_condition: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor]):
-        for n in self.prognostic:
-            self.ic[n].copy_(initial_condition[n].reshape(self.B, 1, self.H, self.W))
-        for n in self.forcing_names:
-            self.forcing[n].copy_(forcing[n][:, : self.T + 1])
-
-    def run_window(self):
-        """Enqueue the T steps of the window on the current stream (no host synchronisation)."""
-        step = self.stepper._step_obj
-        if step._corrector is not self._corrector or step._ocean is not None:
-            raise RuntimeError("the stepper's corrector / ocean was replaced after this OceanRolloutEngine was built: build a new one")
-        key = self._weights_stamp()
-        if key != self._weights_key:      # parameters changed (load_state): the captured graphs hold the old weight handles
-            self._captured = None
-            self._window_graph = None
-        with torch.no_grad():
-            if self.graph_mode == "step":
-                if self._captured is None:
-                    from .samudra import CapturedSamudraForward
-                    self._captured = CapturedSamudraForward(self.net, self.x)       # warm-up outside capture, then capture
-                    self.x = self._captured.x
-                    self._weights_key = self._weights_stamp()
-                for s in range(self.T):
-                    self._enqueue_step(s, True)
-            elif self.graph_mode == "window":
-                if self._window_graph is None:
-                    # warm-up outside capture (Samudra workspace, weight handles, first-touch allocations), then one capture
-                    side = torch.cuda.Stream(device=self.device)
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        self._enqueue_step(0, False)
-                    torch.cuda.current_stream().wait_stream(side)
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        for s in range(self.T):
-                            self._enqueue_step(s, False)
-                    self._window_graph = g
-                    self._weights_key = self._weights_stamp()
-                self._window_graph.replay()
-            else:
-                for s in range(self.T):
-                    self._enqueue_step(s, False)
-
-    def predict(self, initial_condition, forcing, time=None) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
-        """Same contract as Stepper.predict for one window of n_forward_steps: (out name -> (B, T, H, W) static buffers, the final
-        prognostic state).  ``time``: the window's TimeAxis when the stepper derives forcings from it."""
-        from .stepper import PrognosticState
-        deriver = self.stepper.forcing_deriver
-        if deriver.needs_time and not getattr(forcing, "derived", False):
-            forcing = deriver(forcing, time, device=self.device)
-        with torch.no_grad():
-            self.load(initial_condition, forcing)
-            self.run_window()
-        state = PrognosticState({n: self.out[n][:, -1:] for n in self.prognostic})
-        state.stepper_state = getattr(initial_condition, "stepper_state", None)     # the ocean corrector carries no state
-        return self.out, state
-
-    def continue_from_last(self):
-        """Carry the final prognostic state into the initial-condition slot (next window of a long rollout)."""
-        for n in self.prognostic:
-            self.ic[n].copy_(self.out[n][:, -1:])
-
-
-def _check_mask(rc: int) -> None:
-    if rc != 0:
-        msg = _lib.lib().ace_mask_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)

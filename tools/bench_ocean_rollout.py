@@ -85,22 +85,22 @@ def launches(mode, B, T):
 def masking_kernels(eng, iters):
     """ms of one step's ace_mask_pack_normalize and ace_mask_planes (kernels only, the engine's own tables), bytes moved"""
     from ace_amd import _lib
-    from ace_amd.ocean_rollout import _check_mask
+    from ace_amd.masking import _check
     L = _lib.lib()
     B, HW = eng.B, eng.HW
     srcs, src_strides, stage, stage_strides = eng._pack_addr[0]
     hits = eng._in_hits
 
     def pack():
-        _check_mask(L.ace_mask_pack_normalize(srcs, src_strides, eng._in_idx.data_ptr(), hits.data_ptr(), hits.shape[0],
-                                              eng._in_fill.data_ptr(), stage, stage_strides, eng.in_mean.data_ptr(),
-                                              eng.in_std.data_ptr(), eng.x.data_ptr(), len(eng.in_names), eng._nplanes, B, HW,
-                                              _lib.current_stream()))
+        _check(L.ace_mask_pack_normalize(srcs, src_strides, eng._in_idx.data_ptr(), hits.data_ptr(), hits.shape[0],
+                                         eng._in_fill.data_ptr(), stage, stage_strides, eng.in_mean.data_ptr(),
+                                         eng.in_std.data_ptr(), eng.x.data_ptr(), len(eng.in_names), eng._nplanes, B, HW,
+                                         _lib.current_stream()))
     a, st = eng._omask_addr[0], eng._omask_strides.data_ptr()
 
     def outmask():
-        _check_mask(L.ace_mask_planes(a, st, a, st, eng._out_idx.data_ptr(), eng._out_hits.data_ptr(), eng._out_hits.shape[0],
-                                      eng._out_fill.data_ptr(), len(eng._out_names_masked), B, HW, _lib.current_stream()))
+        _check(L.ace_mask_planes(a, st, a, st, eng._out_idx.data_ptr(), eng._out_hits.data_ptr(), eng._out_hits.shape[0],
+                                 eng._out_fill.data_ptr(), len(eng._out_names_masked), B, HW, _lib.current_stream()))
     idx = eng._in_idx.cpu()
     n_masked_in = int((idx >= 0).sum())
     # pack: every source read, every packed plane written, staged planes written, hit bytes of the masked planes
