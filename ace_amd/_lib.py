@@ -173,6 +173,14 @@ SIGNATURES = {
     # srcs, src_strides, mask_idx, hits, nmask, fill, stage, stage_strides, mean, std, dst, npack, nplanes, batch, hw, stream
     "ace_mask_pack_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    "ace_diag_last_error": (c_char_p, []),
+    "ace_diag_partial_doubles": (c_long, [c_int, c_int, c_int, c_long]),
+    # srcs, strides, rows, wrows, weights, nw, partial, tsum, series, nrows, n_time, t0, t_begin, do_tsum, nplanes, batch, steps,
+    # hw, stream
+    "ace_diag_window": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_void_p]),
+    # coeffs, rows, spec, nrows, nnames, planes, lmax, mmax, stream
+    "ace_diag_spectrum": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_int, c_int, c_void_p]),
 }
 
 _lib = None

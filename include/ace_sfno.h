@@ -247,6 +247,28 @@ int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, c
                             const float* std_, float* dst, int npack, int nplanes, int batch, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Inference diagnostics (fme/ace/aggregator/inference: reduced.py, time_mean.py, spectrum.py), ace_amd/aggregator.py.
+ * Deterministic: no float atomics, a fixed partition and combine order, fp64 accumulators; stream-ordered, no allocation
+ * or host synchronisation.
+ *   diag_window:   srcs: DEVICE array of nplanes pointers to (batch, steps, hw) fp32 fields; strides: DEVICE long
+ *                  [nplanes][2], the sample and step strides in floats (rows of a plane contiguous).  rows: DEVICE int
+ *                  [nplanes], the accumulator row of each plane; wrows: DEVICE int [nplanes], its row of weights
+ *                  (DEVICE fp32 [nw][hw]; a pixel of weight 0 is skipped, NaN included).  partial: DEVICE fp64 scratch of
+ *                  ace_diag_partial_doubles(nplanes, batch, steps, hw) values.  series: DEVICE fp64 [2][nrows][n_time]
+ *                  += the batch mean of the per-sample weighted mean (0) and weighted std sqrt(wmean((x - wmean x)^2)) (1)
+ *                  at t0 + t.  do_tsum: tsum (DEVICE fp64 [nrows][hw]) += the sum over samples and steps t >= t_begin.
+ *   diag_spectrum: coeffs: DEVICE complex64 [nnames][planes][lmax][mmax] (the forward SHT of each plane);
+ *                  spec (DEVICE fp64 [nrows][lmax]) [rows[j]][l] += sum over planes and m of |c|^2.
+ * ------------------------------------------------------------------------------------------ */
+const char* ace_diag_last_error(void);
+long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
+int ace_diag_window(const float* const* srcs, const long* strides, const int* rows, const int* wrows, const float* weights, int nw,
+                    double* partial, double* tsum, double* series, int nrows, int n_time, int t0, int t_begin, int do_tsum,
+                    int nplanes, int batch, int steps, long hw, void* stream);
+int ace_diag_spectrum(const void* coeffs, const int* rows, double* spec, int nrows, int nnames, long planes, int lmax, int mmax,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
  * (fme/core/corrector/atmosphere.py:349-398 order, 404-700 corrections), the prescribed-SST Ocean
  * (fme/core/ocean.py:167-222, fme/core/prescriber.py:54-117) and the prescribed prognostics, applied in place on the
