@@ -7,7 +7,8 @@
 //                  which each thread adds to the persistent fp64 accumulator of its own pixels (no two threads share one).
 //   diag_combine   one wave per (t, j): the partials of each sample merged by Chan's parallel update in a fixed order (lane
 //                  strides, then a butterfly), the per-sample weighted mean and std averaged over the batch in sample order and
-//                  added to the fp64 series at i_time_start + t.
+//                  added to the fp64 series at i_time_start + t.  A plane whose accumulator row or weight row is out of range
+//                  is skipped by both kernels: it contributes to nothing.
 //   diag_spectrum  one workgroup per (l, name): sum over (plane, m) of |c_lm|^2 in fp64 from the complex64 output of the
 //                  forward SHT, a fixed-order block sum, added to the fp64 spectrum accumulator.
 // No float atomics, no host synchronisation, no allocation: two identical runs are bitwise identical.
@@ -75,7 +76,8 @@ __global__ __launch_bounds__(NT) void diag_window_kernel(const float* const* src
     const float* base = srcs[j];
     const long sb = strides[2 * j], st = strides[2 * j + 1];
     const bool vec = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0 && (sb & 3) == 0 && (st & 3) == 0;
-    const float4 w4 = load4(weights + (long)wr * HW, p, HW, (HW & 3) == 0);
+    const float* wrow = weights + (long)wr * HW;
+    const float4 w4 = load4(wrow, p, HW, (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(wrow) & 15u) == 0);
     const float wv[PIX] = {w4.x, w4.y, w4.z, w4.w};
     double acc[PIX] = {0.0, 0.0, 0.0, 0.0};
     const long nparts = (long)nchunk * WAVES;
@@ -122,11 +124,12 @@ __global__ __launch_bounds__(NT) void diag_window_kernel(const float* const* src
 }
 
 __global__ __launch_bounds__(64) void diag_combine_kernel(const double* __restrict__ partial, const int* __restrict__ rows,
-                                                          double* __restrict__ series, int nrows, int n_time, int B, int T,
-                                                          int t0, long nparts) {
+                                                          const int* __restrict__ wrows, int nw, double* __restrict__ series,
+                                                          int nrows, int n_time, int B, int T, int t0, long nparts) {
     const int t = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
-    const int r = rows[j];
-    if (r < 0 || r >= nrows || t0 + t < 0 || t0 + t >= n_time) return;
+    const int r = rows[j], wr = wrows[j];
+    // a plane without a weight row has no partials (diag_window_kernel skipped it): it contributes to nothing
+    if (r < 0 || r >= nrows || wr < 0 || wr >= nw || t0 + t < 0 || t0 + t >= n_time) return;
     double sm = 0.0, ss = 0.0;
     for (int b = 0; b < B; ++b) {
         const double* q = partial + (((long)j * B + b) * T + t) * nparts * NMOM;
@@ -182,9 +185,12 @@ extern "C" long ace_diag_partial_doubles(int nplanes, int batch, int steps, long
 extern "C" int ace_diag_window(const float* const* srcs, const long* strides, const int* rows, const int* wrows,
                                const float* weights, int nw, double* partial, double* tsum, double* series, int nrows, int n_time,
                                int t0, int t_begin, int do_tsum, int nplanes, int batch, int steps, long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535 || batch < 1 || steps < 1 || steps > 65535 || hw < 1 || nw < 1 || nrows < 1 ||
-        t0 < 0 || t0 + steps > n_time || t_begin < 0)
-        return dfail(ACE_ERR_INVALID, "ace_diag_window: bad shape (need 0 <= t0, t0 + steps <= n_time)");
+    if (nplanes < 0 || nplanes > 65535) return dfail(ACE_ERR_INVALID, "ace_diag_window: need 0 <= nplanes <= 65535");
+    if (steps < 1 || steps > 65535) return dfail(ACE_ERR_INVALID, "ace_diag_window: need 1 <= steps <= 65535");
+    if (batch < 1 || hw < 1 || nw < 1 || nrows < 1)
+        return dfail(ACE_ERR_INVALID, "ace_diag_window: need batch >= 1, hw >= 1, nw >= 1, nrows >= 1");
+    if (t0 < 0 || t0 + (long)steps > n_time || t_begin < 0)
+        return dfail(ACE_ERR_INVALID, "ace_diag_window: need 0 <= t0, t0 + steps <= n_time, 0 <= t_begin");
     if (nplanes == 0) return ACE_OK;
     if (!srcs || !strides || !rows || !wrows || !weights || !partial || !series || (do_tsum && !tsum))
         return dfail(ACE_ERR_INVALID, "ace_diag_window: null argument");
@@ -194,16 +200,17 @@ extern "C" int ace_diag_window(const float* const* srcs, const long* strides, co
     hipLaunchKernelGGL(diag_window_kernel, dim3((unsigned)nchunk, nplanes), dim3(NT), 0, s, srcs, strides, rows, wrows, weights, nw,
                        partial, tsum, nrows, batch, steps, t_begin, do_tsum, hw, (int)nchunk);
     DIAG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(diag_combine_kernel, dim3(steps, nplanes), dim3(64), 0, s, partial, rows, series, nrows, n_time, batch, steps,
-                       t0, nchunk * WAVES);
+    hipLaunchKernelGGL(diag_combine_kernel, dim3(steps, nplanes), dim3(64), 0, s, partial, rows, wrows, nw, series, nrows, n_time, batch,
+                       steps, t0, nchunk * WAVES);
     DIAG_TRY(hipGetLastError());
     return ACE_OK;
 }
 
 extern "C" int ace_diag_spectrum(const void* coeffs, const int* rows, double* spec, int nrows, int nnames, long planes, int lmax,
                                  int mmax, void* stream) {
-    if (nnames < 0 || nnames > 65535 || planes < 1 || lmax < 1 || mmax < 1 || nrows < 1)
-        return dfail(ACE_ERR_INVALID, "ace_diag_spectrum: bad shape");
+    if (nnames < 0 || nnames > 65535) return dfail(ACE_ERR_INVALID, "ace_diag_spectrum: need 0 <= nnames <= 65535");
+    if (planes < 1 || lmax < 1 || mmax < 1 || nrows < 1)
+        return dfail(ACE_ERR_INVALID, "ace_diag_spectrum: need planes >= 1, lmax >= 1, mmax >= 1, nrows >= 1");
     if (nnames == 0) return ACE_OK;
     if (!coeffs || !rows || !spec) return dfail(ACE_ERR_INVALID, "ace_diag_spectrum: null argument");
     hipLaunchKernelGGL(diag_spectrum_kernel, dim3(lmax, nnames), dim3(NT), 0, static_cast<hipStream_t>(stream),

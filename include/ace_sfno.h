@@ -256,7 +256,12 @@ int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, c
  *                  (DEVICE fp32 [nw][hw]; a pixel of weight 0 is skipped, NaN included).  partial: DEVICE fp64 scratch of
  *                  ace_diag_partial_doubles(nplanes, batch, steps, hw) values.  series: DEVICE fp64 [2][nrows][n_time]
  *                  += the batch mean of the per-sample weighted mean (0) and weighted std sqrt(wmean((x - wmean x)^2)) (1)
- *                  at t0 + t.  do_tsum: tsum (DEVICE fp64 [nrows][hw]) += the sum over samples and steps t >= t_begin.
+ *                  at t0 + t; NaN where a sample has no pixel of non-zero weight.  do_tsum: tsum (DEVICE fp64 [nrows][hw]) +=
+ *                  acc, where acc = 0, then += x[b][t] in fp64 for every sample b (outer) and step t >= t_begin (inner): every
+ *                  pixel, whatever its weight.  tsum may be NULL when do_tsum is 0.  A plane whose rows[j] or wrows[j] is out
+ *                  of range contributes to nothing: no accumulator changes for it.  rows must not name one row twice (the +=
+ *                  on tsum and series are not atomic); this is not checked.  The weight table and the planes may start at any
+ *                  4-byte boundary.
  *   diag_spectrum: coeffs: DEVICE complex64 [nnames][planes][lmax][mmax] (the forward SHT of each plane);
  *                  spec (DEVICE fp64 [nrows][lmax]) [rows[j]][l] += sum over planes and m of |c|^2.
  * ------------------------------------------------------------------------------------------ */

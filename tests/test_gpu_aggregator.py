@@ -239,3 +239,199 @@ def test_launches_per_window_are_bounded(dev):
     small.spectrum_chunk_bytes = 1                  # one name per SHT chunk: 1 + 2 launches per chunk
     small.record_batch({k: v for k, v in fields(g, 1, 3, dev).items() if k in ("a", "q", "sst")})
     assert small.launches() == 1 + 2 * 2
+
+
+# ---- other grids, strided fields, chunked spectra, late names ------------------------------------------------------------------
+def grid_info(nlat, nlon):
+    lat = torch.tensor([-90 + (i + 0.5) * 180 / nlat for i in range(nlat)], dtype=torch.float64)
+    lon = torch.tensor([(j + 0.5) * 360 / nlon for j in range(nlon)], dtype=torch.float64)
+    mask = torch.ones(nlat, nlon)
+    mask[nlat // 4:nlat // 2, nlon // 3:nlon // 2] = 0.0
+    return DatasetInfo((nlat, nlon), lat=lat, lon=lon, mask_provider=SpatialMaskProvider({"mask_sst": mask}))
+
+
+GRID_NAMES = ("a", "PRESsfc", "sst", "static")
+
+
+def grid_packed(g, B, T, nlat, nlon):
+    """one packed (B, T, C, H, W) CPU tensor, C in the order of GRID_NAMES; "sst" is NaN on land, "static" the same at every step"""
+    p = torch.randn(B, T, len(GRID_NAMES), nlat, nlon, generator=g)
+    p[:, :, 1] = 1e5 + 1e2 * p[:, :, 1]
+    mask = grid_info(nlat, nlon).mask_provider.get_mask_tensor_for("sst")
+    p[:, :, 2] = (290 + 5 * p[:, :, 2]).where(mask != 0, torch.tensor(float("nan")))
+    p[:, :, 3] = p[:, :1, 3]
+    return p
+
+
+def strided_window(packed, dev):
+    """channel slices of the packed device tensor, an expanded static field, rows that are not contiguous"""
+    p = packed.to(dev)
+    win = {n: p[:, :, c] for c, n in enumerate(GRID_NAMES)}
+    win["static"] = p[:, :1, 3].expand(-1, p.shape[1], -1, -1)
+    win["a"] = p[:, :, 0].transpose(-1, -2).contiguous().transpose(-1, -2)
+    assert not win["PRESsfc"].is_contiguous() and win["static"].stride(1) == 0 and win["a"].stride(-1) != 1
+    return win
+
+
+def _bitwise(a, b):
+    assert set(a) == set(b)
+    for sub, d in a.items():
+        assert set(d) == set(b[sub]), sub
+        for k, v in d.items():
+            assert torch.equal(v.view(torch.int32), b[sub][k].view(torch.int32)), (sub, k)
+
+
+@pytest.mark.parametrize("nlat,nlon", [(45, 90), (13, 27), (NLAT, NLON)])
+def test_grids_and_strided_fields(dev, nlat, nlon):
+    """45 x 90 (hw % 4 == 2) and 13 x 27 (odd nlat, odd hw) beside 180 x 360: the fused path on channel slices of a packed tensor,
+    an expanded static field and non-contiguous rows gives the contiguous run's bits, which agree with the fp64 restatement"""
+    info = grid_info(nlat, nlon)
+    g = torch.Generator().manual_seed(nlat)
+    B = 2
+    ic_p = grid_packed(g, B, 1, nlat, nlon)
+    packs = [grid_packed(g, B, T, nlat, nlon) for T in (3, 2)]
+    ic = {n: ic_p[:, :, c].contiguous().to(dev) for c, n in enumerate(GRID_NAMES)}
+    plain = [{n: p[:, :, c].contiguous().to(dev) for c, n in enumerate(GRID_NAMES)} for p in packs]
+    strided = [strided_window(p, dev) for p in packs]
+    aggs = []
+    for wins in (plain, strided):
+        agg = build(info, 6)
+        agg.record_initial_condition(ic)
+        for win in wins:
+            assert agg.route(win) == "fused"
+            agg.record_batch(win)
+        assert agg._path == "fused"
+        aggs.append(agg)
+    ds = aggs[0].get_dataset()
+    _bitwise(ds, aggs[1].get_dataset())
+    series = {n: torch.cat([p[:, :, c] for p in packs], dim=1) for c, n in enumerate(GRID_NAMES)}
+    want, _ = _fp64_of_writer(aggs[0], {n: v.cpu() for n, v in ic.items()}, series, 6)
+    assert aggs[0].omitted == ["sst"]
+    _agree(ds, want)
+
+
+def _three_windows(dev, nlat=45, nlon=90, B=2):
+    g = torch.Generator().manual_seed(11)
+    info = grid_info(nlat, nlon)
+    wins = []
+    for T in (2, 3, 2):
+        p = grid_packed(g, B, T, nlat, nlon)
+        wins.append({n: p[:, :, c].contiguous().to(dev) for c, n in enumerate(GRID_NAMES)})
+    return info, wins
+
+
+@pytest.mark.parametrize("nlat,nlon", [(45, 90), (NLAT, NLON)])
+def test_chunked_spectrum_is_bitwise_the_unchunked_one(dev, nlat, nlon):
+    """each (row, l) is one workgroup's fixed-order sum over one name's coefficients: one name per SHT chunk changes no bit"""
+    info, wins = _three_windows(dev, nlat, nlon)
+    out = []
+    for chunk in (None, 1):
+        agg = build(info, 7)
+        if chunk:
+            agg.spectrum_chunk_bytes = chunk
+        for win in wins:
+            agg.record_batch(win)
+        assert agg.launches() == (3 * (1 + 2 * 3) if chunk else 3 * 3)          # "sst" is omitted: three names in the spectrum
+        out.append(agg.get_dataset())
+    _bitwise({"power_spectrum": out[0]["power_spectrum"]}, {"power_spectrum": out[1]["power_spectrum"]})
+    _bitwise(out[0], out[1])
+
+
+def test_name_that_first_appears_in_the_third_window(dev):
+    """the accumulators grow and are copied: the late name reads 0 before it appears and its own values are right; every earlier
+    name's series, map and spectrum keep the bits of a run without it"""
+    info, wins = _three_windows(dev)
+    g = torch.Generator().manual_seed(12)
+    late = (3.0 + torch.randn(2, 2, 45, 90, generator=g)).to(dev)
+    base = build(info, 7)
+    grown = build(info, 7)
+    for i, win in enumerate(wins):
+        base.record_batch(win)
+        grown.record_batch({**win, "late": late} if i == 2 else win)
+    assert grown._path == "fused" and len(grown._rows) == len(base._rows) + 1
+    a, b = base.get_dataset(), grown.get_dataset()
+    for sub in a:
+        _bitwise({sub: a[sub]}, {sub: {k: v for k, v in b[sub].items() if not k.endswith("late")}})
+    m64, s64 = moments64(late, grown.weights_for("late", "cpu"))
+    gm, gs = b["mean"]["weighted_mean_gen-late"].double(), b["mean"]["weighted_std_gen-late"].double()
+    assert bool((gm[:5] == 0).all()) and bool((gs[:5] == 0).all())
+    assert float(((gm[5:] - m64).abs() / m64.abs()).max()) <= 1e-6 and float(((gs[5:] - s64).abs() / s64.abs()).max()) <= 1e-5
+    sht = OracleSHT(45, 90, grid="legendre-gauss", dtype=torch.float64)
+    c = sht(late.double().cpu())
+    want = (c.real ** 2 + c.imag ** 2).sum(-1).mean((0, 1))
+    assert float((b["power_spectrum"]["late"].double() - want).abs().max() / want.abs().max()) <= 1e-5
+
+
+def test_fused_without_time_series(dev):
+    """log_global_mean_time_series=False on the fused path (the window's series go to scratch): no "mean", and the maps and spectra
+    keep the bits of the run with the series on"""
+    info, wins = _three_windows(dev)
+    ic = {n: x[:, :1] for n, x in wins[0].items()}
+    out = []
+    for log in (True, False):
+        agg = InferenceAggregatorConfig(log_global_mean_time_series=log).build(info, 8)
+        agg.record_initial_condition(ic)
+        for win in wins:
+            assert agg.route(win) == "fused"
+            agg.record_batch(win)
+        assert agg._path == "fused"
+        out.append(agg.get_dataset())
+    assert set(out[0]) == {"mean", "time_mean", "power_spectrum"} and set(out[1]) == {"time_mean", "power_spectrum"}
+    _bitwise({k: out[0][k] for k in out[1]}, out[1])
+
+
+def test_torch_window_after_a_fused_one_is_refused(dev):
+    info, wins = _three_windows(dev)
+    agg = build(info, 7)
+    agg.record_batch(wins[0])
+    assert agg._path == "fused"
+    with pytest.raises(ValueError, match="fused path.*torch path"):
+        agg.record_batch({n: x.double() for n, x in wins[1].items()})
+
+
+# ---- the spectrum's tail, degree by degree --------------------------------------------------------------------------------
+def temperature_like(nlat, nlon, seed=0):
+    """two samples, one step, fp32: power per degree about (l + 1)^-3 (coefficients randn * (l + 1)^-2, zero for m > l, real at
+    m = 0, through the fp64 inverse transform) plus 250"""
+    from oracle.sht import InverseRealSHT
+    g = torch.Generator().manual_seed(seed)
+    L, M = nlat, nlon // 2 + 1
+    c = torch.complex(torch.randn(2, 1, L, M, generator=g, dtype=torch.float64), torch.randn(2, 1, L, M, generator=g, dtype=torch.float64))
+    l, m = torch.arange(L)[:, None], torch.arange(M)[None, :]
+    c = c * (l + 1.0) ** -2 * (m <= l)
+    c[..., 0] = c[..., 0].real + 0j
+    x = InverseRealSHT(nlat, nlon, grid="legendre-gauss", dtype=torch.float64)(c) + 250.0
+    return x.float()
+
+
+@pytest.mark.parametrize("nlat,nlon", [(45, 90), (NLAT, NLON)])
+def test_spectrum_tail_per_degree(dev, nlat, nlon):
+    """e(l) = |S(l) - S64(l)| / S64(l) per degree, not normalised by the spectrum's peak: the fused spectrum (native fp32 SHT +
+    ace_diag_spectrum) and the torch path on the device (native SHT + torch sums) are held to 4x the error of the reference's own
+    formula in fp32 (the CPU oracle), in the maximum and in the median over the degrees.  The factor is a margin for two fp32
+    computations that round in different orders, over the reference's error, not the kernel's."""
+    x = temperature_like(nlat, nlon)
+
+    def spectrum(dtype):
+        c = OracleSHT(nlat, nlon, grid="legendre-gauss", dtype=dtype)(x)
+        return (c.real.double() ** 2 + c.imag.double() ** 2).sum(-1).mean((0, 1))
+
+    s64 = spectrum(torch.float64)
+    e32 = (spectrum(torch.float32) - s64).abs() / s64
+    print(f"DIAGACC tail {nlat}x{nlon} fp32 oracle: max {float(e32.max()):.3e} (l = {int(e32.argmax())}) median "
+          f"{float(e32.median()):.3e}, spectrum range {float(s64.max() / s64.min()):.1e}")
+    assert float(e32.max()) <= 2e-2                      # the yardstick itself resolves every degree
+    info = grid_info(nlat, nlon)
+    failures = []
+    for fused in (True, False):
+        agg = build(info, 2, fused)
+        agg.record_initial_condition({"t": x[:, 0].to(dev)})
+        agg.record_batch({"t": x.to(dev)})
+        assert agg._path == ("fused" if fused else "torch")
+        e = (agg.get_dataset()["power_spectrum"]["t"].double() - s64).abs() / s64
+        print(f"DIAGACC tail {nlat}x{nlon} {'fused' if fused else 'torch path on the device'}: max {float(e.max()):.3e} "
+              f"(l = {int(e.argmax())}) median {float(e.median()):.3e}; ratios to the oracle {float(e.max() / e32.max()):.2f} "
+              f"{float(e.median() / e32.median()):.2f}")
+        if not (float(e.max()) <= 4 * float(e32.max()) and float(e.median()) <= 4 * float(e32.median())):
+            failures.append(("fused" if fused else "torch", float(e.max() / e32.max()), float(e.median() / e32.median())))
+    assert not failures, failures

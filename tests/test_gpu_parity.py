@@ -176,6 +176,7 @@ def test_sht_golden_regression(dev):
 @pytest.mark.parametrize("nlat,nlon,lmax,mmax,grid,n", [
     (9, 18, None, None, "lobatto", 1), (9, 18, None, None, "equiangular", 5), (6, 12, None, None, "legendre-gauss", 3),
     (12, 24, 8, 9, "legendre-gauss", 4), (45, 90, None, None, "legendre-gauss", 16), (13, 27, None, None, "equiangular", 2),
+    (13, 27, None, None, "legendre-gauss", 2),
     (64, 128, 40, 50, "legendre-gauss", 7),
     # widths with an instantiated two-level FFT (csrc/fft.hip: 16, 24, 48, 360, 720, 1440), truncated mmax, channel counts that
     # leave the last 8 / 16 / 32-row channel block ragged
