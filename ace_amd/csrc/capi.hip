@@ -734,9 +734,7 @@ struct ace_sfno {
     int H = 0, W = 0, C = 0, L = 0, Mm = 0, hid = 0, Bmax = 1;
     long HW = 0;
     // scale_factor != 1 (sfnonet.py:467-515): the blocks between the first filter's inverse transform and the last filter's work on
-    // the (nlat / sf) x (nlon / sf) Gauss-Legendre grid; hw_now is the resolution of the launches being enqueued (the 1x1-convolution
-    // helpers read it), HWs the inner one
-    mutable long hw_now = 0;
+    // the (nlat / sf) x (nlon / sf) Gauss-Legendre grid, HWs pixels
     long HWs = 0;
     int Hs = 0, Ws = 0;
     std::unique_ptr<ace_sht_plan> plan_lg, plan_data_own;
@@ -774,11 +772,6 @@ struct ace_sfno {
     std::vector<DevBuf> taps;
     std::map<GraphKey, hipGraphExec_t> graphs;
     hipStream_t capture_stream = nullptr;
-#ifdef ACE_MEASUREMENT_SWITCHES   // fork experiment (profiles/r06_skip_fork.txt): ACE_SKIP_FORK=1 the inner skip's bias-only GEMM on a side
-    int skip_fork = 0;            // stream beside the spectral chain (an EXTRA kernel: results unchanged), 2 the same kernel in line
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-#endif
     long weights_generation = 0; // bumped by every ace_sfno_set_weight (ace_sfno_weights_generation)
     bool graphs_stale = false;   // a parameter was uploaded since the graphs were captured: re-capture lazily
     Switches sw;                 // measurement switches, read once at ace_sfno_create
@@ -805,6 +798,19 @@ static void add_conv_weight(ace_sfno* n, const std::string& name, int rows, int 
     add_weight(n, name, (long)rows * cols);
     Weight& w = *n->weights.back();
     w.rows = rows; w.cols = cols; w.pitch = (cols + 31) & ~31;
+}
+
+// Does role R of a K -> M 1x1 convolution at resolution HW leave the tile engines for conv_ws.hip / conv_wl.hip?  One function per
+// question, asked by ace_sfno_create (which buffers exist), ace_sfno_set_weight (which fragments are packed) and plan_route (which
+// kernel runs).  The last encoder convolution counts as an fc2 (static weights, fp32 residual, planes + statistics out).
+static bool skip_on_conv_ws(const Switches& sw, int K, int M, long HW) { return conv_ws_eligible(K, M, HW, 0, sw.conv_ws_roles); }
+static bool fc1_on_conv_ws(const Switches& sw, int K, int M, long HW) { return conv_ws_eligible(K, M, HW, 1, sw.conv_ws_roles); }
+static bool fc2_on_conv_ws(const Switches& sw, int K, int M, long HW) { return conv_ws_eligible(K, M, HW, 2, sw.conv_ws_roles); }
+static bool fc1_on_conv_wl(const Switches& sw, int K, int M, long HW) { return sw.conv_wl && conv_wl_eligible(K, M, HW); }
+// the inner skip of a noise-conditioned net (conv_ws.hip mode 6: no per-step weight fold, any K of that file): the "skip" bit of
+// ACE_CONV_WS switches it
+static bool cln_skip_on_conv_ws(const Switches& sw, int K, int M, long HW) {
+    return (sw.conv_ws_roles & 1) && conv_ws_eligible(K, M, HW, -1, sw.conv_ws_roles);
 }
 
 extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
@@ -839,7 +845,6 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
     n->cfg = c;
     n->sw = read_switches();
     n->H = c.nlat; n->W = c.nlon; n->C = c.embed_dim; n->HW = (long)c.nlat * c.nlon;
-    n->hw_now = n->HW;
     n->Bmax = c.max_batch > 0 ? c.max_batch : 1;
     // sfnonet.py:467-472: the downscaled image and the modes kept
     const int sf = c.scale_factor;
@@ -945,16 +950,6 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
         n->wx_native[i] = (n->wx_compact[i] && cln && c.filter_num_groups > 1 && !n->sw.dense_grouped_filter && !n->sw.no_dhconv_strip &&
                            strip_rows_ok && dhconv_native_groups_ok(n->C, c.filter_num_groups)) ? 1 : 0;
     }
-#ifdef ACE_MEASUREMENT_SWITCHES
-    if (const char* e = std::getenv("ACE_SKIP_FORK")) {
-        n->skip_fork = std::atoi(e);
-        if (n->skip_fork) {
-            HIP_TRY(hipStreamCreateWithFlags(&n->side_stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&n->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&n->ev_join, hipEventDisableTiming));
-        }
-    }
-#endif
     if (c.operator_type == 1 && c.precision == 1 && n->C % 128 == 0) {   // dhconv_strip.hip's work lists (depend on the batch size)
         n->dh_units.resize(n->Bmax);
         n->dh_units_per_xcd.assign(n->Bmax, 0);
@@ -976,9 +971,11 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
         if (c.normalization_layer == 1 && c.use_mlp) {
             HIP_TRY(n->P2.alloc(act, true));
             n->nstrips = (int)((HW + 31) / 32) + 8;     // >= tilesN * WN of either tile shape and conv_ws's 32-pixel tiles
-            if (conv_ws_eligible((int)C, n->hid, HW, 1, n->sw.conv_ws_roles) || (n->sw.conv_wl && conv_wl_eligible((int)C, n->hid, HW)))
+            // Asked with the DATA grid, while plan_route asks with each block's own: a known gap for scale_factor != 1, whose inner
+            // blocks may then find no buffer and stay on the tile engine
+            if (fc1_on_conv_ws(n->sw, (int)C, n->hid, HW) || fc1_on_conv_wl(n->sw, (int)C, n->hid, HW))
                 HIP_TRY(n->Wq1.alloc((size_t)n->Bmax * n->hid * C, true));   // hi + lo halves = one float per element
-            if (conv_ws_eligible((int)C, (int)C, HW, 0, n->sw.conv_ws_roles)) HIP_TRY(n->Wq0.alloc((size_t)n->Bmax * C * C, true));
+            if (skip_on_conv_ws(n->sw, (int)C, (int)C, HW)) HIP_TRY(n->Wq0.alloc((size_t)n->Bmax * C * C, true));
             HIP_TRY(n->zero_c.alloc((size_t)C, true));
             HIP_TRY(n->inP.alloc((size_t)n->Bmax * ((c.in_chans + 7) / 8 * 8) * n->HW, true));   // two planes of halves = one float per element
             HIP_TRY(n->pe_slot.alloc(64, true));
@@ -1014,11 +1011,6 @@ extern "C" void ace_sfno_destroy(ace_sfno* n) {
     if (!n) return;
     for (auto& kv : n->graphs) (void)hipGraphExecDestroy(kv.second);
     if (n->capture_stream) (void)hipStreamDestroy(n->capture_stream);
-#ifdef ACE_MEASUREMENT_SWITCHES
-    if (n->side_stream) (void)hipStreamDestroy(n->side_stream);
-    if (n->ev_fork) (void)hipEventDestroy(n->ev_fork);
-    if (n->ev_join) (void)hipEventDestroy(n->ev_join);
-#endif
     delete n;
 }
 
@@ -1064,12 +1056,6 @@ extern "C" const char* ace_sfno_weight_name(const ace_sfno* n, int i) {
 extern "C" long ace_sfno_weight_numel(const ace_sfno* n, int i) {
     if (!n || i < 0 || i >= (int)n->weights.size()) return -1;
     return n->weights[i]->ext_numel ? n->weights[i]->ext_numel : n->weights[i]->numel;
-}
-
-// The inner skip of a noise-conditioned net on conv_ws.hip (mode 6: no per-step weight fold, any K of that file).  ONE predicate for
-// the upload (which packs the static fragments) and the forward (which reads them): the "skip" bit of ACE_CONV_WS switches it.
-static bool cln_skip_on_conv_ws(const ace_sfno* n, int K, int M) {
-    return (n->sw.conv_ws_roles & 1) && conv_ws_eligible(K, M, n->HW, -1, n->sw.conv_ws_roles);
 }
 
 extern "C" int ace_sfno_set_weight(ace_sfno* n, const char* name, const float* src, long numel, void* stream) {
@@ -1167,15 +1153,16 @@ extern "C" int ace_sfno_set_weight(ace_sfno* n, const char* name, const float* s
         const bool is_fc2 = wn.size() > 16 && wn.compare(wn.size() - 16, 16, "mlp.fwd.2.weight") == 0;
         // fc1 without an instance norm in front of it (nothing to fold per step): static fragments for conv_wl.hip
         const bool is_fc1 = wn.size() > 16 && wn.compare(wn.size() - 16, 16, "mlp.fwd.0.weight") == 0;
-        if (is_fc1 && n->cfg.normalization_layer != 1 && n->sw.conv_wl && conv_wl_eligible(w.cols, w.rows, n->HW)) {
+        // (every question below is asked with the DATA grid, plan_route asks with the block's own: the known gap noted in ace_sfno_create)
+        if (is_fc1 && n->cfg.normalization_layer != 1 && fc1_on_conv_wl(n->sw, w.cols, w.rows, n->HW)) {
             if (!w.frag0.p) HIP_TRY(w.frag0.alloc((size_t)w.rows * w.cols, false));
             HIP_TRY(launch_pack_conv_frag(w.buf.p, w.pitch, w.rows, w.cols, 0, nullptr, 0.f, w.ascale, nullptr, w.frag0.p,
                                           0, 1, s));
         }
-        // (the inner skip of a noise-conditioned net has no per-step weight fold and any K of conv_ws.hip: its mode 6)
         const bool cln_skip = is_skip && n->cfg.normalization_layer == 2;
-        const bool ws_ok = cln_skip ? cln_skip_on_conv_ws(n, w.cols, w.rows)
-                                    : conv_ws_eligible(w.cols, w.rows, n->HW, is_skip ? 0 : 2, n->sw.conv_ws_roles);
+        const bool ws_ok = cln_skip ? cln_skip_on_conv_ws(n->sw, w.cols, w.rows, n->HW)
+                           : is_skip ? skip_on_conv_ws(n->sw, w.cols, w.rows, n->HW)
+                                     : fc2_on_conv_ws(n->sw, w.cols, w.rows, n->HW);
         if ((is_skip || is_fc2 || is_enc2) && ws_ok) {
             if (!w.frag0.p) HIP_TRY(w.frag0.alloc((size_t)w.rows * w.cols, false));
             HIP_TRY(launch_pack_conv_frag(w.buf.p, w.pitch, w.rows, w.cols, 0, nullptr, 0.f, w.ascale, nullptr, w.frag0.p,
@@ -1231,115 +1218,218 @@ extern "C" int ace_sfno_set_weight(ace_sfno* n, const char* name, const float* s
     return ACE_OK;
 }
 
-// one 1x1 convolution = one batched GEMM launch.  A operand: (ptr, pitch, per-sample stride); bias: (ptr, per-sample stride)
-struct ConvW { const float* w; int pitch; long sw; const float* bias; long sbias; const float* hi; const float* lo; float ascale; };
-static ConvW conv_weight(const ace_sfno* n, const std::string& wname, const std::string& bname) {
-    const Weight& w = *n->weights[n->index.at(wname)];
-    return ConvW{w.buf.p, w.pitch, 0, bname.empty() ? nullptr : n->w(bname), 0, w.hi.p, w.lo.p, w.ascale};
-}
-static int conv(const ace_sfno* n, const ConvW& cw, const float* in, long in_bstride, int cin, const float* in2,
-                long in2_bstride, int K1, float* out, int cout, const float* R, long r_bstride, const float* rsc,
-                const float* rsh, int act, int batch, hipStream_t s, const float* bsc = nullptr,
-                const float* bsh = nullptr, const unsigned* bmax = nullptr, const unsigned* bmax2 = nullptr,
-                unsigned* omax = nullptr) {
-    GemmArgs g;
-    g.bsc = bsc; g.bsh = bsh; g.sbs = bsc ? cin : 0;
-    g.omax = omax;
-    g.A = cw.w; g.lda = cw.pitch; g.sA = cw.sw; g.a_kpad = cw.pitch;
-    g.B = in; g.ldb = n->hw_now; g.sB = in_bstride;
-    g.B2 = in2; g.ldb2 = n->hw_now; g.sB2 = in2_bstride; g.K1 = in2 ? K1 : -1;
-    g.C = out; g.ldc = n->hw_now; g.sC = (long)cout * n->hw_now;
-    g.bias = cw.bias; g.sbias = cw.sbias;
-    g.R = R; g.ldr = n->hw_now; g.sR = r_bstride;
-    g.rsc = rsc; g.rsh = rsh; g.srs = rsc ? cout : 0;
-    g.M = cout; g.N = (int)n->hw_now; g.K = cin; g.nbatch = batch; g.act = act;
-    if (n->cfg.precision == 1 && cw.hi && cw.sw == 0 && bmax && gemm_f16x3_eligible(g)) {
-        // compensated fp16 with the B scale derived in-kernel from max|B| (slot written by B's producer)
-        if (g.act == ACT_GELU) g.act = ACT_GELU_FAST;  // the epilogue is on the critical path of this engine
-        HIP_TRY(launch_gemm_f16x3(g, cw.hi, cw.lo, cw.ascale, 1.0f, s, bmax, omax, (in2 ? bmax2 : nullptr)));
-        return ACE_OK;
-    }
-    if (bsc && g.sA == 0 && n->cfg.precision == 1) {
-        // f16x3 configuration but this launch fell back to fp32 with an un-folded affine: the register-staged
-        // engine applies it on load
-    }
-    HIP_TRY(launch_gemm(g, s));
-    return ACE_OK;
-}
-// the instance-norm affine (a, b) of the conv input folded into its weight: returns the per-sample operand
-static int fold(const ace_sfno* n, const ConvW& cw, int O, int I, const float* a, const float* b, float* Wf, float* bf,
-                int batch, hipStream_t s, ConvW* out) {
-    HIP_TRY(launch_fold_affine(cw.w, cw.pitch, a, b, cw.bias, Wf, bf, batch, O, I, s));
-    *out = ConvW{Wf, cw.pitch, (long)O * cw.pitch, bf, O};
-    return ACE_OK;
-}
+// ---------------------------------------------------------------------------------------------
+// the forward schedule.  plan_route() decides which engine serves every role of every block; the enqueue_* functions below it
+// fill argument structs and launch what the plan says, and decide nothing.
+// ---------------------------------------------------------------------------------------------
+enum FilterEngine { FLT_DHCONV_STRIP, FLT_PACKED_TILE, FLT_ADYN_F16X3, FLT_FP32, FLT_DIAGONAL };
+enum ConvEngine { CONV_NONE, CONV_TILE, CONV_PACKED, CONV_WS, CONV_WL };   // v3 / fp32 tile engine, packed tile engine, conv_ws.hip, conv_wl.hip
+enum BlockBody { BODY_PLAIN, BODY_PACKED, BODY_FUSED };
 
-// f16x3 "v4": 1x1 convolution whose input already is in P format (fp16 hi/lo planes [cin/8][HW][8] per sample, scaled
-// from the bound in `in_slot`).  Output: fp32 (+ omax) and/or P-format planes for the next convolution.
-static bool packed_ok(const ace_sfno* n, int cin) {
-    return !n->sw.no_pk && n->cfg.precision == 1 && n->P.p && cin % 8 == 0 && n->hw_now % 4 == 0;
-}
-static int pack_act(const ace_sfno* n, const float* x, long x_bs, int cin, const float* sc, const float* sh,
-                    const unsigned* slot, void* hi, void* lo, int batch, hipStream_t s) {
-    HIP_TRY(launch_pack_pformat(x, n->hw_now, x_bs, cin, (int)n->hw_now, batch, sc, sh, sc ? cin : 0, slot, hi, lo, n->hw_now,
-                                (long)cin * n->hw_now, s));
-    return ACE_OK;
-}
-static int conv_pk(const ace_sfno* n, const Weight& w, const float* bias, const void* bhi, const void* blo, int cin,
-                   const unsigned* in_slot, float* out, int cout, const float* R, long r_bs, const float* rsc,
-                   const float* rsh, int act, int batch, hipStream_t s, unsigned* omax, void* ohi = nullptr,
-                   void* olo = nullptr, float cb = 0.f, unsigned* cslot = nullptr) {
-    Gemm4Args a;
-    a.Ahi = static_cast<const _Float16*>((const void*)w.thi.p); a.Alo = static_cast<const _Float16*>((const void*)w.tlo.p);
-    a.lda = w.pitch; a.sA = 0; a.ascale = w.ascale; a.a_tiled = 1;
-    a.Bhi = static_cast<const _Float16*>(bhi); a.Blo = static_cast<const _Float16*>(blo);
-    a.ldn = n->hw_now; a.sB = (long)cin * n->hw_now; a.bmax = in_slot;
-    a.C = out; a.ldc = n->hw_now; a.sC = (long)cout * n->hw_now; a.omax = omax;
-    a.Chi = static_cast<_Float16*>(ohi); a.Clo = static_cast<_Float16*>(olo); a.ldnc = n->hw_now; a.sCp = (long)cout * n->hw_now;
-    a.cw = w.winf; a.cb = cb; a.cslot = cslot;
-    a.bias = bias; a.sbias = 0;
-    a.R = R; a.ldr = n->hw_now; a.sR = r_bs; a.rsc = rsc; a.rsh = rsh; a.srs = rsc ? cout : 0;
-    a.M = cout; a.N = (int)n->hw_now; a.K = cin; a.nbatch = batch;
-    a.act = act == ACT_GELU ? ACT_GELU_FAST : act;
-    HIP_TRY(launch_gemm_f16x3_packed(a, s));
-    return ACE_OK;
-}
-
-struct PkOpts {
-    // A: static tiled planes of `w`, or per-sample folded planes (fhi/flo with scale slot fslot)
-    const Weight* w = nullptr;
-    const void* fhi = nullptr; const void* flo = nullptr; const unsigned* fslot = nullptr; long f_stride = 0;
-    const float* bias = nullptr; long sbias = 0;
-    const void* bhi = nullptr; const void* blo = nullptr; int cin = 0; const unsigned* in_slot = nullptr;
-    float* out = nullptr; int cout = 0; unsigned* omax = nullptr;
-    const float* R = nullptr; long r_bs = 0; const float* rsc = nullptr; const float* rsh = nullptr;
-    int act = ACT_NONE;
-    void* ohi = nullptr; void* olo = nullptr; float cb = 0.f; unsigned* cslot = nullptr;
-    const unsigned* cinb = nullptr; const unsigned* rmax = nullptr;
-    float* part = nullptr;
+struct BlockRoute {
+    const ace_sht_plan* fwd = nullptr; const ace_sht_plan* inv = nullptr;   // the filter's two transforms
+    long hw_in = 0, hw_out = 0;      // resolution in front of / behind the filter (they differ where scale_residual)
+    bool scale_residual = false;     // grids differ (s2convolutions.py:82-86): the residual is the spectrally round-tripped input
+    // block input, as the producer (last encoder convolution / previous block's fc2) left it
+    bool in_planes = false;          // P2 holds the RAW input as planes (bound in hslot(i)) and `part` its row statistics: norm0 finalises
+    int in_nparts = 0;               // those partials (so many per row) instead of running a statistics pass
+    bool in_planes_only = false;     // ... and no fp32 copy exists: the longitude FFT reads the planes
+    bool n0_to_planes = false, n1_to_planes = false;   // the conditional norms are asked for P-format planes (norm1: planes only)
+    bool ride_skip_pack = false;     // the inner skip's folded weights are offered to the forward FFT launch as rider workgroups
+    // spectral filter
+    bool dplanes = false;            // D goes from the Legendre epilogue to the contraction as fp16 planes (never fp32)
+    FilterEngine filter = FLT_FP32;
+    // behind the filter
+    BlockBody body = BODY_PLAIN;
+    ConvEngine skip = CONV_TILE, fc1 = CONV_NONE, fc2 = CONV_NONE;
+    int skip_slot = -1, t_slot = -1; // range slots of the inner skip's input (-1: none, fp32 engine) and of the MLP's input
+    bool fold_skip = false, fold_fc1 = false;   // plain body, fp32 mode: the instance-norm affine folded into a per-sample fp32 weight
+    bool pfold = false;              // fused body: fc1 folds its norm affine in the kernel's own prologue (conv_wl.hip at the ACE2 width)
+    int t_nparts = 0;                // fused body: statistics partials per row the inner skip writes
+    // fused body, fc2
+    bool res_planes = false;         // the outer-skip residual comes from the input planes
+    bool out_f32 = true;             // h' is written as fp32
+    bool out_planes = false;         // ... as planes with statistics for the next block (every block but the last)
+    int out_nparts = 0;
 };
-static int conv_pk2(const ace_sfno* n, const PkOpts& o, int batch, hipStream_t s) {
-    Gemm4Args a;
-    if (o.fhi) {
-        a.Ahi = static_cast<const _Float16*>(o.fhi); a.Alo = static_cast<const _Float16*>(o.flo);
-        a.sA = o.f_stride; a.amax = o.fslot;
-    } else {
-        a.Ahi = reinterpret_cast<const _Float16*>(o.w->thi.p); a.Alo = reinterpret_cast<const _Float16*>(o.w->tlo.p);
-        a.sA = 0; a.ascale = o.w->ascale;
+struct FwdRoute {
+    const char* err = nullptr;       // a handle whose stored operands no engine can read for this launch (ACE_ERR_STATE)
+    bool stream_ok = false;          // residual stream of the blocks as planes only where a conv_ws fc2 feeds the next block
+    bool noise_range = false;        // the conditioning field's range is taken (f16x3 noise-conditioned nets)
+    bool enc_hidden_planes = false;  // first encoder convolution on the packed engine: P holds the hidden activation as planes
+    bool enc_planes = false;         // last encoder convolution on conv_ws.hip: h0 as planes + the statistics of block 0's norm0
+    bool enc_planes_only = false;    // ... and not as fp32
+    int enc_nparts = 0;
+    std::vector<BlockRoute> blk;
+};
+
+// f16x3 "v4" engine: can a 1x1 convolution read a cin-channel input as P-format planes at resolution hw?
+static bool packed_ok(const ace_sfno* n, int cin, long hw) {
+    return !n->sw.no_pk && n->cfg.precision == 1 && n->P.p && cin % 8 == 0 && hw % 4 == 0;
+}
+static int ws_stat_parts(int K, int M, long HW) {   // statistics partials per row of a conv_ws.hip launch of that shape
+    ConvStripArgs k;
+    k.C = K; k.M = M; k.HW = (int)HW;
+    return conv_ws_stat_parts(k);
+}
+// the filter contraction on dhconv_strip.hip (compact or native operand, coefficient planes in D)
+static DhconvStripArgs dhconv_strip_args(const ace_sfno* n, int i, int B, const unsigned* dmax, unsigned* emax) {
+    const int C = n->C;
+    const long N2 = (long)B * 2 * C;
+    DhconvStripArgs ds;
+    ds.Dhi = reinterpret_cast<const _Float16*>(n->D.p);
+    ds.Dlo = ds.Dhi + (size_t)n->L * n->Mm * N2;
+    ds.sD = (long)n->Mm * N2; ds.amax = dmax;
+    ds.Whi = reinterpret_cast<const _Float16*>(n->wx_hi[i].p);
+    ds.Wlo = reinterpret_cast<const _Float16*>(n->wx_lo[i].p);
+    ds.sW = (long)2 * C * C; ds.bscale = n->wx_scale[i];
+    ds.E = n->E.p; ds.sE = (long)n->Mm * N2; ds.omax = emax;
+    ds.C = C; ds.L = n->L; ds.Mrows = n->Mm * B; ds.trimul = B;
+    ds.groups = n->cfg.normalization_layer == 2 ? n->cfg.filter_num_groups : 1;
+    if (n->wx_native[i]) { ds.kstore = C / ds.groups; ds.sW = (long)2 * ds.kstore * C; }
+    if ((int)n->dh_units.size() >= B) { ds.units = reinterpret_cast<const int*>(n->dh_units[B - 1].p); ds.units_per_xcd = n->dh_units_per_xcd[B - 1]; }
+    return ds;
+}
+// dynamic-range slots of the f16x3 engine (AMAX_SHARDS words each): 0 network input, 1..7 encoder/decoder hidden,
+// 8 + i % 8 block input h_i, 16 + 12 i + {0 X, 1 D, 2 E, 3 N0, 4 T, 5 N1, 6 U, 7 Y, 8 folded skip weight, 9 folded fc1 weight},
+// 16 + 12 num_layers the conditioning field
+static unsigned* range_slot(const ace_sfno* n, int k) {
+    return n->cfg.precision == 1 && k >= 0 ? reinterpret_cast<unsigned*>(n->amax.p) + (size_t)k * AMAX_SHARDS : nullptr;
+}
+
+// Which kernel serves which role of a forward at batch size B.  Reads the configuration, the switches and which buffers / packed
+// fragments exist; makes no HIP call and changes nothing.
+static FwdRoute plan_route(const ace_sfno* n, int B, bool has_noise) {
+    const ace_sfno_config& c = n->cfg;
+    const Switches& sw = n->sw;
+    const int C = n->C, hid = n->hid, nl = c.num_layers;
+    const long N2 = (long)B * 2 * C;
+    const bool f16 = c.precision == 1, gelu = c.activation_function == ACT_GELU;
+    const bool norm = c.normalization_layer == 1, cln = c.normalization_layer == 2, lnrm = c.normalization_layer == 3;
+    auto wt = [&](const std::string& name) -> const Weight& { return *n->weights[n->index.at(name)]; };
+    FwdRoute r;
+    r.noise_range = cln && f16 && has_noise;
+    // Residual stream as planes only: once a block's fc2 (conv_ws mode 4) has written h' as P-format planes, the next block reads
+    // them everywhere - longitude FFT, inner skip, outer-skip residual - and no fp32 copy of h' exists (fc2: 520 -> 420 MB)
+    r.stream_ok = sw.planes_stream && f16 && !n->taps_on && n->plan_data == n->plan_lg.get() && C % 16 == 0 &&
+                  !n->plan_lg->sw.no_fft && dft_fft_has_width(n->W);
+    r.blk.resize(nl);
+
+    // ---- engines of each block (sfnonet.py:217-252): functions of the block's grids and of what was uploaded
+    for (int i = 0; i < nl; ++i) {
+        BlockRoute& b = r.blk[i];
+        const std::string p = "blocks." + std::to_string(i) + ".";
+        const int sb = 16 + 12 * i;
+        b.fwd = i == 0 ? n->plan_data : n->plan_lg.get();
+        b.inv = i == nl - 1 ? n->plan_data : n->plan_lg.get();
+        b.scale_residual = b.fwd != b.inv;
+        b.hw_in = (long)b.fwd->nlat * b.fwd->nlon;
+        // everything behind the filter works on ITS output grid (the skips, norm1 and the MLP see what the inverse transform
+        // produced) - the inner grid after the first block of a scale_factor != 1 net, the data grid after the last
+        const long hw = b.hw_out = (long)b.inv->nlat * b.inv->nlon;
+
+        // spectral filter (s2convolutions.py:162-197)
+        b.dplanes = f16 && !sw.no_pk_sht && c.operator_type == 1 && n->wx_hi[i].p && !b.scale_residual && b.fwd->f16 &&
+                    N2 % 4 == 0 && (2 * C) % 32 == 0;
+        if (c.operator_type != 1) {
+            b.filter = FLT_DIAGONAL;
+        } else {
+            bool strip_ok = false;
+            if (b.dplanes && n->wx_compact[i]) {
+                const DhconvStripArgs ds = dhconv_strip_args(n, i, B, range_slot(n, sb + 1), range_slot(n, sb + 2));
+                strip_ok = ds.units && dhconv_strip_eligible(ds);
+            }
+            const char* err = nullptr;
+            if (n->wx_native[i] && !strip_ok) err = "grouped filter stored as diagonal blocks, but the strip kernel cannot run this launch";
+            else if (strip_ok && !sw.no_dhconv_strip) b.filter = FLT_DHCONV_STRIP;
+            else if (b.dplanes) b.filter = FLT_PACKED_TILE;
+            else if (f16 && n->wx_hi[i].p && n->wx_compact[i]) err = "compact dhconv operand without the packed path";
+            else if (f16 && n->wx_hi[i].p) b.filter = FLT_ADYN_F16X3;
+            else b.filter = FLT_FP32;
+            if (err && !r.err) r.err = err;
+        }
+
+        // Input of the inner skip: the normalised block input (bound from the norm statistics) or, without a norm, the raw block
+        // input; the spectrally round-tripped residual of mixed-grid blocks has no range slot -> fp32 engine
+        b.skip_slot = b.scale_residual ? -1 : ((norm || cln || lnrm) ? sb + 3 : 8 + i % 8);
+        b.t_slot = (norm || cln || lnrm) ? sb + 5 : sb + 4;
+        const bool pk = f16 && !b.scale_residual && packed_ok(n, C, hw) && (!c.use_mlp || hid % 8 == 0);
+        const bool fused = pk && norm && c.use_mlp && n->P2.p;
+        b.body = fused ? BODY_FUSED : pk ? BODY_PACKED : BODY_PLAIN;
+        const ConvEngine other = pk ? CONV_PACKED : CONV_TILE;
+        b.skip = other;
+        if (c.use_mlp) b.fc1 = b.fc2 = other;
+        if (fused) {
+            // Instance norms fused away: every conv input is P-format planes written by its producer's epilogue, the norm affine is
+            // folded into the consumer's weights.  Which of the three convolutions run on the weight-stationary kernels:
+            const Weight& w1 = wt(p + "mlp.fwd.0.weight");
+            if (gelu && n->Wq0.p && wt(p + "inner_skip.weight").frag0.p && skip_on_conv_ws(sw, C, C, hw)) b.skip = CONV_WS;
+            if (gelu && n->Wq1.p && fc1_on_conv_wl(sw, C, hid, hw)) b.fc1 = CONV_WL;
+            else if (gelu && n->Wq1.p && fc1_on_conv_ws(sw, C, hid, hw)) b.fc1 = CONV_WS;
+            b.pfold = sw.fused_pack && b.fc1 == CONV_WL && C == 384 && w1.pitch % 4 == 0;
+            // (C <= 1024: the fp32 output of conv_ws.hip)
+            if (wt(p + "mlp.fwd.2.weight").frag0.p && C <= 1024 && fc2_on_conv_ws(sw, hid, C, hw)) b.fc2 = CONV_WS;
+            b.t_nparts = b.skip == CONV_WS ? ws_stat_parts(C, C, hw) : gemm4_strips(C, (int)hw);
+        } else if (pk) {
+            // conv_ws.hip mode 6: GELU(W . planes + bias + Y) -> fp32 T (the conditional norm that follows reads fp32)
+            if (cln && gelu && wt(p + "inner_skip.weight").frag0.p && cln_skip_on_conv_ws(sw, C, C, hw)) b.skip = CONV_WS;
+            // conv_wl.hip: the noise-conditioned nets' fc1 (no norm affine to fold, static fragments)
+            if (c.use_mlp && !norm && gelu && wt(p + "mlp.fwd.0.weight").frag0.p && fc1_on_conv_wl(sw, C, hid, hw)) b.fc1 = CONV_WL;
+            b.n0_to_planes = cln;
+            b.n1_to_planes = cln && c.use_mlp && !n->taps_on;   // followed by the packed MLP, norm1's output exists as planes only
+        } else {
+            b.fold_skip = norm && !b.scale_residual && !f16;
+            b.fold_fc1 = norm && c.use_mlp && !f16;
+        }
     }
-    a.lda = o.w->pitch; a.a_tiled = 1;
-    a.Bhi = static_cast<const _Float16*>(o.bhi); a.Blo = static_cast<const _Float16*>(o.blo);
-    a.ldn = n->hw_now; a.sB = (long)o.cin * n->hw_now; a.bmax = o.in_slot;
-    a.C = o.out; a.ldc = n->hw_now; a.sC = (long)o.cout * n->hw_now; a.omax = o.omax;
-    a.Chi = static_cast<_Float16*>(o.ohi); a.Clo = static_cast<_Float16*>(o.olo); a.ldnc = n->hw_now; a.sCp = (long)o.cout * n->hw_now;
-    a.cw = o.w->winf; a.cb = o.cb; a.cslot = o.cslot; a.cinb = o.cinb; a.rmax = o.rmax;
-    a.part = reinterpret_cast<float4*>(o.part);
-    a.bias = o.bias; a.sbias = o.sbias;
-    a.R = o.R; a.ldr = n->hw_now; a.sR = o.r_bs; a.rsc = o.rsc; a.rsh = o.rsh; a.srs = o.rsc ? o.cout : 0;
-    a.M = o.cout; a.N = (int)n->hw_now; a.K = o.cin; a.nbatch = batch;
-    a.act = o.act == ACT_GELU ? ACT_GELU_FAST : o.act;
-    HIP_TRY(launch_gemm_f16x3_packed(a, s));
-    return ACE_OK;
+
+    // ---- encoder (sfnonet.py:721-733).  Its last convolution (C -> C, no bias, + pos_embed) runs on conv_ws.hip when block 0
+    // takes the fused body: the epilogue then writes h0 as fp32 AND as P-format planes with the row statistics of norm0, so block 0
+    // starts like every other block (no pack pass, no statistics pass over h0).
+    const Weight& we = wt("encoder." + std::to_string(2 * c.encoder_layers) + ".weight");
+    r.enc_planes = !sw.no_enc_ws && r.blk[0].body == BODY_FUSED && c.encoder_layers >= 1 && c.pos_embed && we.frag0.p && n->zero_c.p &&
+                   n->pe_slot.p && n->part.p && fc2_on_conv_ws(sw, C, C, n->HW);
+    if (r.enc_planes) r.enc_nparts = ws_stat_parts(C, C, n->HW);
+    // Then a ONE-hidden-layer encoder (the ACE2 shape) never materialises its hidden activation as fp32: the network input is packed
+    // to P-format planes (in_chans rounded up to a k-group, 11 MB) and the first convolution runs on the packed-operand engine, whose
+    // epilogue writes GELU(W x + b) straight as the planes the last one reads (r03: fp32 write + pack pass = 55 + 41 us per step).
+    if (r.enc_planes && c.encoder_layers == 1 && n->inP.p && !sw.no_enc_pk) {
+        const Weight& w0 = wt("encoder.0.weight");
+        r.enc_hidden_planes = w0.thi.p && w0.pitch >= (c.in_chans + 7) / 8 * 8;
+    }
+    // fp32 copy of h0: only where something reads it - with the residual stream as planes and block 0's fc2 on conv_ws.hip (whose
+    // residual comes from the planes) block 0 takes its input from the planes everywhere and the 100 MB write is dropped
+    r.enc_planes_only = r.enc_planes && r.stream_ok && r.blk[0].fc2 == CONV_WS;
+
+    // ---- what each block finds of its input, threaded from producer to consumer
+    bool have_ph = r.enc_planes, planes_only = r.enc_planes_only;
+    int nparts = r.enc_nparts;
+    for (int i = 0; i < nl; ++i) {
+        BlockRoute& b = r.blk[i];
+        const bool last = i + 1 == nl;
+        b.in_planes = have_ph; b.in_planes_only = planes_only; b.in_nparts = nparts;
+        if (b.body == BODY_FUSED) {
+            // The folded weights of the inner skip (W diag(a0), bs + W b0) depend on norm0's affine only: the ~300 workgroups that
+            // pack them ride in the forward FFT launch instead of a dependent 7 us launch of their own
+            b.ride_skip_pack = sw.fused_pack && have_ph && b.skip == CONV_WS;
+            b.out_planes = !last;
+            if (b.fc2 == CONV_WS) {
+                // residual = a0 h + b0: from the fp32 h, or - when the block input came as planes from a producer epilogue - from
+                // those planes; then a mid block writes h' as planes only
+                b.res_planes = r.stream_ok && have_ph;
+                b.out_f32 = last || !b.res_planes;
+                nparts = ws_stat_parts(hid, C, b.hw_out);   // one partial per workgroup and row (accumulated in LDS)
+            } else {
+                nparts = gemm4_strips(C, (int)b.hw_out);
+            }
+            b.out_nparts = nparts;
+            planes_only = !b.out_f32;
+            have_ph = !last;
+        } else if (b.body == BODY_PACKED) {
+            have_ph = false;
+        }
+    }
+    return r;
 }
 
 // hipEvent stage timer: one event after each launch group; the elapsed time between consecutive events
@@ -1383,633 +1473,681 @@ struct StageTimer {
     }
     ~StageTimer() { for (auto e : ev) (void)hipEventDestroy(e); }
 };
-#define MARK(st) do { if (tm) tm->push(st); } while (0)
+#define MARK(st) do { if (f.tm) f.tm->push(st); } while (0)
 
-static int forward_impl(ace_sfno* n, const float* in, float* out, int B, hipStream_t s, StageTimer* tm = nullptr,
-                        const float* noise = nullptr) {
-    const ace_sfno_config& c = n->cfg;
-    const int C = n->C, Cin = c.in_chans, act = c.activation_function;
-    long HW = n->HW;                 // resolution of the launches being enqueued: the data grid, or (scale_factor != 1, between the
-    n->hw_now = HW;                  // first filter's inverse transform and the last one's) the inner grid - see the blocks
-    const long N2 = (long)B * 2 * C;
-    long actB = (long)C * HW;        // per-sample stride of a C-channel activation
-    auto W = [&](const std::string& name) { return n->w(name); };
-    // dynamic-range slots of the f16x3 engine (AMAX_SHARDS words each): 0 network input, 1..7 encoder/decoder hidden,
-    // 8 + i block input h_i, 16 + 12 i + {0 X, 1 D, 2 E, 3 N0, 4 T, 5 N1, 6 U, 7 Y, 8 folded skip weight, 9 folded fc1 weight}
-    const bool f16 = c.precision == 1;
-    unsigned* amax = reinterpret_cast<unsigned*>(n->amax.p);
-    auto slot = [&](int k) -> unsigned* { return f16 ? amax + (size_t)k * AMAX_SHARDS : nullptr; };
-    if (f16) {
-        HIP_TRY(launch_zero_u32(amax, (long)n->amax.n, s));
-        HIP_TRY(launch_absmax(in, (long)B * Cin * HW, slot(0), s));
+// What the enqueue steps of one forward share: the handle, where to launch, views of the workspace, and the few values one step
+// leaves for the next.
+struct Fwd {
+    const ace_sfno* n; int B; hipStream_t s; StageTimer* tm; const float* noise;
+    const FwdRoute* route;
+    // resolution of the launches being enqueued: the data grid, or (scale_factor != 1, between the first filter's inverse transform
+    // and the last one's) the inner grid
+    long HW;
+    float *h, *hn;                   // block input / output
+    float *sc0, *sh0, *sc1, *sh1;    // instance-norm affines of norm0 / norm1, per (sample, channel)
+    _Float16 *PAh, *PAl, *PBh, *PBl; // planes of P (T / pack passes) and P2 (block input h)
+    float *part_h, *part_t;          // row-statistics partials of h and T
+    const float* skip_in; const unsigned* skip_in_slot;   // second source of the big-skip concat
+    // left by a block's norm0 / transforms for its body
+    const float *a0, *b0;            // norm0 as an affine applied on load by every consumer (never materialised)
+    const float *res, *ra, *rb;      // the residual: x_norm as (h, a0, b0), or the round-tripped input of a mixed-grid block
+    bool n0_planes, skip_pack_rode;  // reported by the conditional norm / the forward FFT launch
+
+    unsigned* slot(int k) const { return range_slot(n, k); }
+    unsigned* hslot(int i) const { return slot(8 + i % 8); }   // block-input slots are shared cyclically for deep nets
+    long actB() const { return (long)n->C * HW; }              // per-sample stride of a C-channel activation
+    const float* W(const std::string& name) const { return n->w(name); }
+    const Weight& wt(const std::string& name) const { return *n->weights[n->index.at(name)]; }
+    // lo planes at the resolution being enqueued (the hi plane starts the buffer)
+    _Float16* Pl() const { return PAh ? PAh + (size_t)n->Bmax * n->C * HW : nullptr; }
+    _Float16* Uh() const { return reinterpret_cast<_Float16*>(n->U.p); }
+    _Float16* Ul() const { return Uh() + (size_t)n->Bmax * n->hid * HW; }
+};
+
+// one 1x1 convolution = one batched GEMM launch.  A operand: (ptr, pitch, per-sample stride); bias: (ptr, per-sample stride)
+struct ConvW { const float* w; int pitch; long sw; const float* bias; long sbias; const float* hi; const float* lo; float ascale; };
+static ConvW conv_weight(const ace_sfno* n, const std::string& wname, const std::string& bname) {
+    const Weight& w = *n->weights[n->index.at(wname)];
+    return ConvW{w.buf.p, w.pitch, 0, bname.empty() ? nullptr : n->w(bname), 0, w.hi.p, w.lo.p, w.ascale};
+}
+static int conv(const Fwd& f, const ConvW& cw, const float* in, long in_bstride, int cin, const float* in2,
+                long in2_bstride, int K1, float* out, int cout, const float* R, long r_bstride, const float* rsc,
+                const float* rsh, int act, const float* bsc = nullptr, const float* bsh = nullptr,
+                const unsigned* bmax = nullptr, const unsigned* bmax2 = nullptr, unsigned* omax = nullptr) {
+    GemmArgs g;
+    g.bsc = bsc; g.bsh = bsh; g.sbs = bsc ? cin : 0;
+    g.omax = omax;
+    g.A = cw.w; g.lda = cw.pitch; g.sA = cw.sw; g.a_kpad = cw.pitch;
+    g.B = in; g.ldb = f.HW; g.sB = in_bstride;
+    g.B2 = in2; g.ldb2 = f.HW; g.sB2 = in2_bstride; g.K1 = in2 ? K1 : -1;
+    g.C = out; g.ldc = f.HW; g.sC = (long)cout * f.HW;
+    g.bias = cw.bias; g.sbias = cw.sbias;
+    g.R = R; g.ldr = f.HW; g.sR = r_bstride;
+    g.rsc = rsc; g.rsh = rsh; g.srs = rsc ? cout : 0;
+    g.M = cout; g.N = (int)f.HW; g.K = cin; g.nbatch = f.B; g.act = act;
+    if (f.n->cfg.precision == 1 && cw.hi && cw.sw == 0 && bmax && gemm_f16x3_eligible(g)) {
+        // compensated fp16 with the B scale derived in-kernel from max|B| (slot written by B's producer)
+        if (g.act == ACT_GELU) g.act = ACT_GELU_FAST;  // the epilogue is on the critical path of this engine
+        HIP_TRY(launch_gemm_f16x3(g, cw.hi, cw.lo, cw.ascale, 1.0f, f.s, bmax, omax, (in2 ? bmax2 : nullptr)));
+        return ACE_OK;
     }
-    if (c.num_layers + 8 > 16) { /* block-input slots 8..15 are shared cyclically for deep nets */ }
-    auto hslot = [&](int i) { return slot(8 + (i % 8)); };
+    HIP_TRY(launch_gemm(g, f.s));
+    return ACE_OK;
+}
+// the instance-norm affine (a, b) of the conv input folded into its weight: returns the per-sample operand
+static int fold(const Fwd& f, const ConvW& cw, int O, int I, const float* a, const float* b, float* Wf, float* bf, ConvW* out) {
+    HIP_TRY(launch_fold_affine(cw.w, cw.pitch, a, b, cw.bias, Wf, bf, f.B, O, I, f.s));
+    *out = ConvW{Wf, cw.pitch, (long)O * cw.pitch, bf, O};
+    return ACE_OK;
+}
 
-    // Residual stream as planes only (see the block loop): the condition is needed by the encoder already
-    const bool stream_ok = n->sw.planes_stream && f16 && !n->taps_on && n->plan_data == n->plan_lg.get() && C % 16 == 0 &&
-                           !n->plan_lg->sw.no_fft && dft_fft_has_width(n->W);
-    // ---- encoder (sfnonet.py:721-733): [conv+bias, act] x encoder_layers, conv (no bias), + pos_embed
+// f16x3 "v4": 1x1 convolution whose input already is in P format (fp16 hi/lo planes [cin/8][HW][8] per sample, scaled
+// from the bound in `in_slot`).  Output: fp32 (+ omax) and/or P-format planes for the next convolution.
+static int pack_act(const Fwd& f, const float* x, long x_bs, int cin, const float* sc, const float* sh, const unsigned* slot,
+                    void* hi, void* lo) {
+    HIP_TRY(launch_pack_pformat(x, f.HW, x_bs, cin, (int)f.HW, f.B, sc, sh, sc ? cin : 0, slot, hi, lo, f.HW, (long)cin * f.HW, f.s));
+    return ACE_OK;
+}
+struct PkOpts {
+    // A: static tiled planes of `w`, or per-sample folded planes (fhi/flo with scale slot fslot)
+    const Weight* w = nullptr;
+    const void* fhi = nullptr; const void* flo = nullptr; const unsigned* fslot = nullptr; long f_stride = 0;
+    const float* bias = nullptr; long sbias = 0;
+    const void* bhi = nullptr; const void* blo = nullptr; int cin = 0; const unsigned* in_slot = nullptr;
+    float* out = nullptr; int cout = 0; unsigned* omax = nullptr;
+    const float* R = nullptr; long r_bs = 0; const float* rsc = nullptr; const float* rsh = nullptr;
+    int act = ACT_NONE;
+    void* ohi = nullptr; void* olo = nullptr; float cb = 0.f; unsigned* cslot = nullptr;
+    const unsigned* cinb = nullptr; const unsigned* rmax = nullptr;
+    float* part = nullptr;
+};
+static int conv_packed(const Fwd& f, const PkOpts& o) {
+    Gemm4Args a;
+    if (o.fhi) {
+        a.Ahi = static_cast<const _Float16*>(o.fhi); a.Alo = static_cast<const _Float16*>(o.flo);
+        a.sA = o.f_stride; a.amax = o.fslot;
+    } else {
+        a.Ahi = reinterpret_cast<const _Float16*>(o.w->thi.p); a.Alo = reinterpret_cast<const _Float16*>(o.w->tlo.p);
+        a.sA = 0; a.ascale = o.w->ascale;
+    }
+    a.lda = o.w->pitch; a.a_tiled = 1;
+    a.Bhi = static_cast<const _Float16*>(o.bhi); a.Blo = static_cast<const _Float16*>(o.blo);
+    a.ldn = f.HW; a.sB = (long)o.cin * f.HW; a.bmax = o.in_slot;
+    a.C = o.out; a.ldc = f.HW; a.sC = (long)o.cout * f.HW; a.omax = o.omax;
+    a.Chi = static_cast<_Float16*>(o.ohi); a.Clo = static_cast<_Float16*>(o.olo); a.ldnc = f.HW; a.sCp = (long)o.cout * f.HW;
+    a.cw = o.w->winf; a.cb = o.cb; a.cslot = o.cslot; a.cinb = o.cinb; a.rmax = o.rmax;
+    a.part = reinterpret_cast<float4*>(o.part);
+    a.bias = o.bias; a.sbias = o.sbias;
+    a.R = o.R; a.ldr = f.HW; a.sR = o.r_bs; a.rsc = o.rsc; a.rsh = o.rsh; a.srs = o.rsc ? o.cout : 0;
+    a.M = o.cout; a.N = (int)f.HW; a.K = o.cin; a.nbatch = f.B;
+    a.act = o.act == ACT_GELU ? ACT_GELU_FAST : o.act;
+    HIP_TRY(launch_gemm_f16x3_packed(a, f.s));
+    return ACE_OK;
+}
+// conv_ws.hip / conv_wl.hip: what every launch shares - a cin-channel input as planes at the resolution being enqueued
+static ConvStripArgs strip_args(const Fwd& f, const _Float16* xhi, const _Float16* xlo, const unsigned* xslot, int cin, int cout, int act) {
+    ConvStripArgs k;
+    k.Xhi = xhi; k.Xlo = xlo; k.ldn = f.HW; k.sX = (long)cin * f.HW; k.xslot = xslot;
+    k.C = cin; k.M = cout; k.HW = (int)f.HW; k.nbatch = f.B; k.act = act;
+    return k;
+}
+static void static_frags(ConvStripArgs& k, const Weight& w, const float* bias) {   // ... with the fragments packed at upload
+    k.A = reinterpret_cast<const _Float16*>(w.frag0.p); k.sA = 0; k.ascale = w.ascale;
+    k.bias = bias; k.sbias = 0;
+}
+
+// One conditional layer norm (layers.py:245-318): a single MFMA pass (cln_mfma.hip) where the shape allows it and the
+// conditioning weights were packed at upload, else statistics + apply (kernels.hip).
+// planes (optional): where the single-pass kernel can, it also writes y as the P-format operand of the packed convolutions
+// (scaled by a bound it publishes to omax) - *planes_done says so, the caller then skips its pack pass; with
+// fp32_needed = false that is the ONLY output (y untouched).
+static int cond_norm(const Fwd& f, const float* x, float* y, const std::string& q, int Cc, unsigned* omax, _Float16* phi = nullptr,
+                     _Float16* plo = nullptr, bool fp32_needed = true, bool* planes_done = nullptr) {
+    const ace_sfno* n = f.n;
+    const int J = n->cfg.noise_embed_dim;
+    const Weight* wsc = n->find(q + "W_scale_2d.weight");
+    const Weight* wbi = n->find(q + "W_bias_2d.weight");
+    const Weight* wga = n->find(q + "norm.weight");
+    const Weight* wbe = n->find(q + "norm.bias");
+    if (planes_done) *planes_done = false;
+    ClnMfmaArgs a;
+    a.x = x; a.y = y; a.sx = (long)Cc * f.HW; a.C = Cc; a.HW = f.HW; a.nbatch = f.B; a.eps = 1e-5f; a.omax = omax;
+    a.gamma = f.W(q + "norm.weight"); a.beta = f.W(q + "norm.bias");
+    if (n->cfg.precision == 1 && f.noise && wsc && wbi && wsc->frag0.p && wbi->frag0.p && !n->sw.no_cln_mfma) {
+        a.cond = f.noise; a.scond = (long)J * f.HW; a.J = J; a.cslot = f.slot(16 + 12 * n->cfg.num_layers);
+        a.As = reinterpret_cast<const _Float16*>(wsc->frag0.p); a.Ab = reinterpret_cast<const _Float16*>(wbi->frag0.p);
+        a.ascale_s = wsc->ascale; a.ascale_b = wbi->ascale;
+        if (phi && plo && omax && !n->sw.no_cln_planes && cln_mfma_planes_ok(a) && (!a.gamma || (wga && wbe))) {
+            a.Phi = phi; a.Plo = plo; a.sP = (long)Cc * f.HW;
+            a.gmax = a.gamma ? wga->absmax : 1.f; a.bmax = a.gamma ? wbe->absmax : 0.f;
+            a.ws_inf = wsc->winf; a.wb_inf = wbi->winf;
+            if (!fp32_needed) a.y = nullptr;
+        }
+        if (cln_mfma_eligible(a)) {
+            HIP_TRY(launch_cln_mfma(a, f.s));
+            if (planes_done) *planes_done = a.Phi != nullptr;
+            return ACE_OK;
+        }
+        a.Phi = a.Plo = nullptr; a.y = y;
+    }
+    HIP_TRY(launch_cond_layer_norm(x, f.noise, a.gamma, a.beta, f.W(q + "W_scale_2d.weight"), f.W(q + "W_bias_2d.weight"), 1e-5f,
+                                   n->cln_stats.p, y, f.B, Cc, J, f.HW, f.s, omax));
+    return ACE_OK;
+}
+
+// ---- encoder (sfnonet.py:721-733): [conv+bias, act] x encoder_layers, conv (no bias), + pos_embed -> f.h
+static int enqueue_encoder(Fwd& f, const float* in) {
+    const ace_sfno* n = f.n;
+    const ace_sfno_config& c = n->cfg;
+    const FwdRoute& r = *f.route;
+    const int C = n->C, Cin = c.in_chans, act = c.activation_function;
+    const long HW = f.HW, actB = f.actB();
+    if (c.precision == 1) {
+        HIP_TRY(launch_zero_u32(f.slot(0), (long)n->amax.n, f.s));
+        HIP_TRY(launch_absmax(in, (long)f.B * Cin * HW, f.slot(0), f.s));
+    }
     const float* cur = in;
     long cur_bs = (long)Cin * HW;
     int curC = Cin;
     float* ping[2] = {n->Y.p, n->T.p};
-    // Will the last encoder convolution run on conv_ws.hip (below)?  Then a ONE-hidden-layer encoder (the ACE2 shape) never
-    // materialises its hidden activation as fp32: the network input is packed to P-format planes (in_chans rounded up to a k-group,
-    // 11 MB) and the first convolution runs on the packed-operand engine, whose epilogue writes GELU(W x + b) straight as the
-    // planes that convolution reads (r03: fp32 write + pack pass = 55 + 41 us per step).
-    const bool enc_ws_ok = [&] {
-        const Weight& we = *n->weights[n->index.at("encoder." + std::to_string(2 * c.encoder_layers) + ".weight")];
-        const bool block0_fused = f16 && c.normalization_layer == 1 && c.use_mlp && n->P2.p && packed_ok(n, C) && n->hid % 8 == 0 &&
-                                  (n->plan_data == n->plan_lg.get() || c.num_layers == 1);
-        return !n->sw.no_enc_ws && block0_fused && c.encoder_layers >= 1 && c.pos_embed && we.frag0.p && n->zero_c.p &&
-               n->pe_slot.p && n->part.p && conv_ws_eligible(C, C, HW, 2, n->sw.conv_ws_roles);
-    }();
-    bool enc_hidden_planes = false;   // n->P holds the last hidden activation of the encoder as planes scaled from slot(encoder_layers)
-    if (enc_ws_ok && c.encoder_layers == 1 && n->inP.p && !n->sw.no_enc_pk) {
-        const Weight& w0 = *n->weights[n->index.at("encoder.0.weight")];
-        const Weight& b0 = *n->weights[n->index.at("encoder.0.bias")];
+    if (r.enc_hidden_planes) {   // P holds the hidden activation as planes scaled from slot(1)
+        const Weight& b0 = f.wt("encoder.0.bias");
         const int cin8 = (Cin + 7) / 8 * 8;
-        if (w0.thi.p && w0.pitch >= cin8) {
-            _Float16* Ih = reinterpret_cast<_Float16*>(n->inP.p);
-            _Float16* Il = Ih + (size_t)n->Bmax * cin8 * HW;
-            HIP_TRY(launch_pack_pformat(in, HW, (long)Cin * HW, Cin, (int)HW, B, nullptr, nullptr, 0, slot(0), Ih, Il, HW, (long)cin8 * HW, s));
-            _Float16* Th = reinterpret_cast<_Float16*>(n->P.p);
-            _Float16* Tl = Th + (size_t)n->Bmax * C * HW;
-            ACE_TRY(conv_pk(n, w0, b0.buf.p, Ih, Il, cin8, slot(0), nullptr, C, nullptr, 0, nullptr, nullptr, act, B, s, nullptr, Th, Tl,
-                            b0.absmax, slot(1)));
-            enc_hidden_planes = true;
-            curC = C;
+        _Float16* Ih = reinterpret_cast<_Float16*>(n->inP.p);
+        _Float16* Il = Ih + (size_t)n->Bmax * cin8 * HW;
+        HIP_TRY(launch_pack_pformat(in, HW, (long)Cin * HW, Cin, (int)HW, f.B, nullptr, nullptr, 0, f.slot(0), Ih, Il, HW, (long)cin8 * HW, f.s));
+        PkOpts o;
+        o.w = &f.wt("encoder.0.weight"); o.bias = b0.buf.p;
+        o.bhi = Ih; o.blo = Il; o.cin = cin8; o.in_slot = f.slot(0);
+        o.cout = C; o.act = act;
+        o.ohi = f.PAh; o.olo = f.PAl; o.cb = b0.absmax; o.cslot = f.slot(1);
+        ACE_TRY(conv_packed(f, o));
+    } else {
+        for (int j = 0; j < c.encoder_layers; ++j) {
+            const std::string p = "encoder." + std::to_string(2 * j);
+            ACE_TRY(conv(f, conv_weight(n, p + ".weight", p + ".bias"), cur, cur_bs, curC, nullptr, 0, -1, ping[j & 1], C,
+                         nullptr, 0, nullptr, nullptr, act, nullptr, nullptr, f.slot(j), nullptr, f.slot(1 + j)));
+            cur = ping[j & 1]; cur_bs = actB; curC = C;
         }
     }
-    for (int j = 0; j < c.encoder_layers && !enc_hidden_planes; ++j) {
-        const std::string p = "encoder." + std::to_string(2 * j);
-        ACE_TRY(conv(n, conv_weight(n, p + ".weight", p + ".bias"), cur, cur_bs, curC, nullptr, 0, -1, ping[j & 1], C,
-                     nullptr, 0, nullptr, nullptr, act, B, s, nullptr, nullptr, slot(j == 0 ? 0 : j), nullptr,
-                     slot(1 + j)));
-        cur = ping[j & 1]; cur_bs = actB; curC = C;
+    const std::string last = "encoder." + std::to_string(2 * c.encoder_layers) + ".weight";
+    if (r.enc_planes) {
+        const Weight& we = f.wt(last);
+        if (!r.enc_hidden_planes) ACE_TRY(pack_act(f, cur, cur_bs, C, nullptr, nullptr, f.slot(c.encoder_layers), f.PAh, f.PAl));
+        ConvStripArgs k = strip_args(f, f.PAh, f.PAl, f.slot(c.encoder_layers), C, C, ACT_NONE);
+        static_frags(k, we, n->zero_c.p);
+        k.R = f.W("pos_embed"); k.sR = 0;
+        if (!r.enc_planes_only) { k.Cf = f.h; k.sCf = actB; }
+        k.Chi = f.PBh; k.Clo = f.PBl; k.sCp = (long)C * HW; k.cslot = f.hslot(0);
+        k.cw = we.winf; k.cb = 0.f; k.rmax = reinterpret_cast<const unsigned*>(n->pe_slot.p);
+        k.part = reinterpret_cast<float4*>(f.part_h); k.nstrips32 = r.enc_nparts;
+        HIP_TRY(launch_conv_ws(k, f.s));
+    } else {
+        ACE_TRY(conv(f, conv_weight(n, last, ""), cur, cur_bs, curC, nullptr, 0, -1, f.h, C, c.pos_embed ? f.W("pos_embed") : nullptr, 0,
+                     nullptr, nullptr, ACT_NONE, nullptr, nullptr, f.slot(c.encoder_layers), nullptr, f.hslot(0)));
     }
-    float* h = n->h0.p;
-    float* hn = n->h1.p;
-    // The last encoder convolution (C -> C, no bias, + pos_embed) on the weight-stationary strip kernel when block 0 takes the
-    // packed path: its epilogue then writes h0 as fp32 AND as P-format planes with the row statistics of norm0, so block 0
-    // starts like every other block (no pack pass, no statistics pass over h0).
-    bool enc_planes = false, enc_planes_only = false;
-    int enc_nparts = 0;          // statistics partials per row the last encoder convolution wrote
-    {
-        const Weight& we = *n->weights[n->index.at("encoder." + std::to_string(2 * c.encoder_layers) + ".weight")];
-        const bool enc_off = n->sw.no_enc_ws;
-        const bool block0_fused = f16 && c.normalization_layer == 1 && c.use_mlp && n->P2.p && packed_ok(n, C) && n->hid % 8 == 0 &&
-                                  (n->plan_data == n->plan_lg.get() || c.num_layers == 1);
-        if (!enc_off && block0_fused && c.encoder_layers >= 1 && c.pos_embed && curC == C && we.frag0.p && n->zero_c.p &&
-            n->pe_slot.p && n->part.p && conv_ws_eligible(C, C, HW, 2, n->sw.conv_ws_roles)) {
-            _Float16* Th = reinterpret_cast<_Float16*>(n->P.p);
-            _Float16* Tl = Th + (size_t)n->Bmax * C * HW;
-            _Float16* Hh = reinterpret_cast<_Float16*>(n->P2.p);
-            _Float16* Hl = Hh + (size_t)n->Bmax * C * HW;
-            if (!enc_hidden_planes) ACE_TRY(pack_act(n, cur, cur_bs, C, nullptr, nullptr, slot(c.encoder_layers), Th, Tl, B, s));
-            ConvStripArgs k;
-            k.Xhi = Th; k.Xlo = Tl; k.ldn = HW; k.sX = (long)C * HW; k.xslot = slot(c.encoder_layers);
-            k.A = reinterpret_cast<const _Float16*>(we.frag0.p); k.sA = 0; k.ascale = we.ascale;
-            k.bias = n->zero_c.p; k.sbias = 0;
-            k.R = W("pos_embed"); k.sR = 0;
-            // fp32 copy of h0: only where something reads it - with the residual stream as planes (stream_ok below) block 0 takes its
-            // input from the planes everywhere (longitude FFT, inner skip, outer-skip residual) and the 100 MB write is dropped
-            // (block 0 is on the fused path here - block0_fused above - and its fc2 must be the conv_ws one, whose residual comes from the planes)
-            if (stream_ok && c.num_layers >= 1) {
-                const Weight& w2b0 = *n->weights[n->index.at("blocks.0.mlp.fwd.2.weight")];
-                enc_planes_only = w2b0.frag0.p && C <= 1024 && conv_ws_eligible(n->hid, C, HW, 2, n->sw.conv_ws_roles);
-            }
-            if (!enc_planes_only) { k.Cf = h; k.sCf = actB; }
-            k.Chi = Hh; k.Clo = Hl; k.sCp = (long)C * HW; k.cslot = hslot(0);
-            k.cw = we.winf; k.cb = 0.f; k.rmax = reinterpret_cast<const unsigned*>(n->pe_slot.p);
-            k.C = C; k.M = C; k.HW = (int)HW; k.nbatch = B; k.act = ACT_NONE;
-            k.part = reinterpret_cast<float4*>(n->part.p); k.nstrips32 = conv_ws_stat_parts(k); enc_nparts = k.nstrips32;
-            HIP_TRY(launch_conv_ws(k, s));
-            enc_planes = true;
-        }
-    }
-    if (!enc_planes)
-    ACE_TRY(conv(n, conv_weight(n, "encoder." + std::to_string(2 * c.encoder_layers) + ".weight", ""), cur, cur_bs, curC,
-                 nullptr, 0, -1, h, C, c.pos_embed ? W("pos_embed") : nullptr, 0, nullptr, nullptr, ACT_NONE, B, s,
-                 nullptr, nullptr, slot(c.encoder_layers), nullptr, hslot(0)));
     MARK(ST_ENCODER);
-    if (n->taps_on) HIP_TRY(hipMemcpyAsync(n->taps[0].p, h, sizeof(float) * B * actB, hipMemcpyDeviceToDevice, s));
+    if (n->taps_on) HIP_TRY(hipMemcpyAsync(n->taps[0].p, f.h, sizeof(float) * f.B * actB, hipMemcpyDeviceToDevice, f.s));
+    return ACE_OK;
+}
 
-    float* sc0 = n->stats.p;
-    float* sh0 = sc0 + (size_t)n->Bmax * C;
-    float* sc1 = sh0 + (size_t)n->Bmax * C;
-    float* sh1 = sc1 + (size_t)n->Bmax * C;
-    const bool norm = c.normalization_layer == 1;
-    // NoiseConditionedSFNO: conditional layer norms are materialised in place (fp32) with their true max in the slot of
-    // the instance-norm bound; the convolutions then run on the packed-operand engine (one pack pass per conv input)
-    const bool cln = c.normalization_layer == 2;
-    // "layer_norm": nn.LayerNorm over (H, W) with an (H, W) affine (sfnonet.py:584-592) - a per-PIXEL affine does not fold into the
-    // consumers' weights, so it is materialised in place like the conditional norms (statistics + apply in one launch per norm,
-    // kernels.hip: spatial_layer_norm_kernel) and the convolutions run on the packed-operand engine
-    const bool lnrm = c.normalization_layer == 3;
-    const float* skip_in = in;               // second source of the big-skip concat
-    const unsigned* skip_in_slot = slot(0);
-    // one conditional layer norm (layers.py:245-318): a single MFMA pass (cln_mfma.hip) where the shape allows it and the
-    // conditioning weights were packed at upload, else statistics + apply (kernels.hip)
-    unsigned* noise_slot = slot(16 + 12 * c.num_layers);
-    if (cln && f16 && noise) HIP_TRY(launch_absmax(noise, (long)B * c.noise_embed_dim * HW, noise_slot, s));
-    // planes (optional): where the single-pass kernel can, it also writes y as the P-format operand of the packed convolutions
-    // (scaled by a bound it publishes to omax) - *planes_done says so, the caller then skips its pack pass; with
-    // fp32_needed = false that is the ONLY output (y untouched).
-    auto cond_norm = [&](const float* x, float* y, const std::string& q, int Cc, unsigned* omax, _Float16* phi = nullptr,
-                         _Float16* plo = nullptr, bool fp32_needed = true, bool* planes_done = nullptr) -> int {
-        const Weight* wsc = n->find(q + "W_scale_2d.weight");
-        const Weight* wbi = n->find(q + "W_bias_2d.weight");
-        const Weight* wga = n->find(q + "norm.weight");
-        const Weight* wbe = n->find(q + "norm.bias");
-        if (planes_done) *planes_done = false;
-        ClnMfmaArgs a;
-        a.x = x; a.y = y; a.sx = (long)Cc * HW; a.C = Cc; a.HW = HW; a.nbatch = B; a.eps = 1e-5f; a.omax = omax;
-        a.gamma = W(q + "norm.weight"); a.beta = W(q + "norm.bias");
-        if (f16 && noise && wsc && wbi && wsc->frag0.p && wbi->frag0.p && !n->sw.no_cln_mfma) {
-            a.cond = noise; a.scond = (long)c.noise_embed_dim * HW; a.J = c.noise_embed_dim; a.cslot = noise_slot;
-            a.As = reinterpret_cast<const _Float16*>(wsc->frag0.p); a.Ab = reinterpret_cast<const _Float16*>(wbi->frag0.p);
-            a.ascale_s = wsc->ascale; a.ascale_b = wbi->ascale;
-            if (phi && plo && omax && !n->sw.no_cln_planes && cln_mfma_planes_ok(a) && (!a.gamma || (wga && wbe))) {
-                a.Phi = phi; a.Plo = plo; a.sP = (long)Cc * HW;
-                a.gmax = a.gamma ? wga->absmax : 1.f; a.bmax = a.gamma ? wbe->absmax : 0.f;
-                a.ws_inf = wsc->winf; a.wb_inf = wbi->winf;
-                if (!fp32_needed) a.y = nullptr;
-            }
-            if (cln_mfma_eligible(a)) {
-                HIP_TRY(launch_cln_mfma(a, s));
-                if (planes_done) *planes_done = a.Phi != nullptr;
-                return ACE_OK;
-            }
-            a.Phi = a.Plo = nullptr; a.y = y;
-        }
-        HIP_TRY(launch_cond_layer_norm(x, noise, a.gamma, a.beta, W(q + "W_scale_2d.weight"), W(q + "W_bias_2d.weight"), 1e-5f,
-                                       n->cln_stats.p, y, B, Cc, c.noise_embed_dim, HW, s, omax));
-        return ACE_OK;
-    };
+// second source of the decoder's big-skip concat: the input, band-limited (residual_filter_factor) or normalised (normalize_big_skip)
+static int enqueue_big_skip_source(Fwd& f, const float* in) {
+    const ace_sfno* n = f.n;
+    const ace_sfno_config& c = n->cfg;
+    const int Cin = c.in_chans;
+    f.skip_in = in;
+    f.skip_in_slot = f.slot(0);
+    if (f.route->noise_range)
+        HIP_TRY(launch_absmax(f.noise, (long)f.B * c.noise_embed_dim * f.HW, f.slot(16 + 12 * c.num_layers), f.s));
     if (n->plan_res) {   // residual = residual_filter_up(residual_filter_down(x)) (sfnonet.py:715-716), exact fp32; its range into slot 7
-        const long NR = (long)B * 2 * Cin;
-        ACE_TRY(run_dft_forward(*n->plan_res, in, nullptr, nullptr, n->resX.p, B, Cin, s));
-        ACE_TRY(run_legendre_forward(*n->plan_res, n->resX.p, n->resD.p, NR, s));
-        ACE_TRY(run_legendre_inverse(*n->plan_res, n->resD.p, n->resX.p, NR, s));
-        ACE_TRY(run_dft_inverse(*n->plan_res, n->resX.p, nullptr, n->inF.p, B, Cin, s, slot(7)));
-        skip_in = n->inF.p;
-        skip_in_slot = slot(7);
+        const long NR = (long)f.B * 2 * Cin;
+        ACE_TRY(run_dft_forward(*n->plan_res, in, nullptr, nullptr, n->resX.p, f.B, Cin, f.s));
+        ACE_TRY(run_legendre_forward(*n->plan_res, n->resX.p, n->resD.p, NR, f.s));
+        ACE_TRY(run_legendre_inverse(*n->plan_res, n->resD.p, n->resX.p, NR, f.s));
+        ACE_TRY(run_dft_inverse(*n->plan_res, n->resX.p, nullptr, n->inF.p, f.B, Cin, f.s, f.slot(7)));
+        f.skip_in = n->inF.p;
+        f.skip_in_slot = f.slot(7);
     }
-    if (cln && c.big_skip && c.normalize_big_skip) {
-        ACE_TRY(cond_norm(in, n->inN.p, "norm_big_skip.", Cin, slot(7)));
-        skip_in = n->inN.p;
-        skip_in_slot = slot(7);
+    if (c.normalization_layer == 2 && c.big_skip && c.normalize_big_skip) {
+        ACE_TRY(cond_norm(f, in, n->inN.p, "norm_big_skip.", Cin, f.slot(7)));
+        f.skip_in = n->inN.p;
+        f.skip_in_slot = f.slot(7);
     }
+    return ACE_OK;
+}
 
-    // fused-norm state of the packed-operand path: does P2 hold the block input in P format / `part_h` its statistics?
-    bool have_ph = enc_planes, have_hstats = enc_planes;
-    int h_nparts = enc_planes ? enc_nparts : 0;   // statistics partials per row in part_h (depends on which kernel produced them)
-    float* part_h = n->part.p;
-    float* part_t = n->part.p ? n->part.p + (size_t)n->Bmax * n->nstrips * C * 4 : nullptr;
-    _Float16* PAh = reinterpret_cast<_Float16*>(n->P.p);                  // T planes / pack fallback
-    _Float16* PAl = PAh ? PAh + (size_t)n->Bmax * C * HW : nullptr;
-    _Float16* PBh = reinterpret_cast<_Float16*>(n->P2.p);                 // h planes
-    _Float16* PBl = PBh ? PBh + (size_t)n->Bmax * C * HW : nullptr;
-
-    // Residual stream as planes only: once a block's fc2 (conv_ws mode 4) has written h' as P-format planes, the next block reads
-    // them everywhere - longitude FFT, inner skip, outer-skip residual - and no fp32 copy of h' exists (fc2: 520 -> 420 MB).
-    bool h_planes_only = enc_planes && enc_planes_only;   // the encoder wrote h0 as planes only (implies stream_ok)
-    // ---- blocks (sfnonet.py:217-252)
-    for (int i = 0; i < c.num_layers; ++i) {
-        const std::string p = "blocks." + std::to_string(i) + ".";
-        const ace_sht_plan& fwd = (i == 0) ? *n->plan_data : *n->plan_lg;
-        const ace_sht_plan& inv = (i == c.num_layers - 1) ? *n->plan_data : *n->plan_lg;
-        const bool scale_residual = (&fwd != &inv);  // grids differ (s2convolutions.py:82-86)
-
-        // norm0 as an affine applied on load by every consumer (never materialised)
-        const int sb = 16 + 12 * i;  // slot base of this block
-        if (f16 && i + 1 >= 8) HIP_TRY(launch_zero_u32(hslot(i + 1), AMAX_SHARDS, s));
-        const float *a0 = nullptr, *b0 = nullptr;
-        bool n0_planes = false, n1_planes = false;   // the conditional norms wrote their output as the packed convolutions' operand
-        if (cln) {   // x_norm = CLN0(h; noise), in place: the block never needs the un-normalised h again (sfnonet.py:388-437)
-            const bool pk_ahead = f16 && !scale_residual && packed_ok(n, C) && (!c.use_mlp || n->hid % 8 == 0);   // = `pk` below
-            _Float16* P0 = reinterpret_cast<_Float16*>(n->P.p);
-            ACE_TRY(cond_norm(h, h, p + "norm0.", C, slot(sb + 3), pk_ahead ? P0 : nullptr,
-                              pk_ahead ? P0 + (size_t)n->Bmax * C * HW : nullptr, true, &n0_planes));
-            MARK(ST_NORM0);
-        }
-        if (lnrm) {   // x_norm = LayerNorm_(H, W)(h), in place
-            HIP_TRY(launch_spatial_layer_norm(h, W(p + "norm0.weight"), W(p + "norm0.bias"), 1e-6f, (long)B * C, HW, h, slot(sb + 3), s));
-            MARK(ST_NORM0);
-        }
-        if (norm) {
-            if (have_hstats)   // statistics of h came out of the previous block's fc2 epilogue
-                HIP_TRY(launch_instnorm_finalize(reinterpret_cast<const float4*>(part_h), h_nparts, B, C, HW,
-                                                 W(p + "norm0.weight"), W(p + "norm0.bias"), 1e-6f, sc0, sh0, slot(sb + 3), s));
-            else
-                HIP_TRY(launch_instnorm_stats(h, W(p + "norm0.weight"), W(p + "norm0.bias"), 1e-6f, B, C, HW, sc0, sh0, s,
-                                              slot(sb + 3)));
-            a0 = sc0; b0 = sh0;
-            MARK(ST_NORM0);
-        }
-        // (Round 4 tried packing the inner skip's folded weights on a side stream beside the SHT chain - they depend on norm0's
-        // statistics only.  Same box, whole step in a hipGraph: 5.76 -> 5.86 ms; the fork / join edges cost more than the 7 us
-        // kernel they hide.  profiles/r04_s3_kdur_side_pack_*.txt)
-        // spectral filter (s2convolutions.py:162-197): SHT -> contraction -> inverse SHT + bias
-        unsigned *xmax = slot(sb + 0), *dmax = slot(sb + 1), *emax = slot(sb + 2);
-        // The folded weights of this block's inner skip (W diag(a0), bs + W b0: conv_ws.hip reads them as packed fragments) depend on
-        // norm0's affine only: where that convolution will run on the weight-stationary kernel (the conditions of `ws_skip` below),
-        // the ~300 workgroups that pack them ride in the forward FFT launch instead of a dependent 7 us launch of their own.
-        PackFragArgs skip_pack;
-        bool skip_pack_rode = false, skip_pack_wanted = false;
-        if (n->sw.fused_pack && f16 && norm && !scale_residual && have_ph && c.use_mlp && n->P2.p && packed_ok(n, C) && n->hid % 8 == 0 &&
-            c.activation_function == ACT_GELU && n->Wq0.p) {
-            const Weight& wsk = *n->weights[n->index.at(p + "inner_skip.weight")];
-            const Weight& bsk = *n->weights[n->index.at(p + "inner_skip.bias")];
-            if (wsk.frag0.p && conv_ws_eligible(C, C, HW, 0, n->sw.conv_ws_roles)) {
-                skip_pack.W = wsk.buf.p; skip_pack.ldw = wsk.pitch; skip_pack.O = C; skip_pack.I = C; skip_pack.order = 0;
-                skip_pack.a = a0; skip_pack.wmax = wsk.wabs; skip_pack.scale_static = 1.f; skip_pack.wslot = slot(sb + 8);
-                skip_pack.dst = reinterpret_cast<_Float16*>(n->Wq0.p); skip_pack.sDst = (long)C * C * 2;
-                skip_pack.b = b0; skip_pack.bias = bsk.buf.p; skip_pack.bf = n->bf0.p; skip_pack.nsamples = B;
-                skip_pack_wanted = true;
-            }
-        }
-        const PackFragArgs* ride = skip_pack_wanted ? &skip_pack : nullptr;
-#ifdef ACE_MEASUREMENT_SWITCHES
-        bool forked = false, packed_early = false;
-        if (n->skip_fork && skip_pack_wanted && !tm) {
-            // the skip GEMM without its epilogue (mode 7: S = W diag(a0) h + bias, fp32 into the unused T buffer) beside the chain
-            const Weight& wsk = *n->weights[n->index.at(p + "inner_skip.weight")];
-            hipStream_t q = n->skip_fork == 1 ? n->side_stream : s;
-            if (n->skip_fork == 1) { HIP_TRY(hipEventRecord(n->ev_fork, s)); HIP_TRY(hipStreamWaitEvent(q, n->ev_fork, 0)); }
-            HIP_TRY(launch_pack_conv_frag(wsk.buf.p, wsk.pitch, C, C, 0, a0, wsk.wabs, 1.f, slot(sb + 8), n->Wq0.p, (long)C * C * 2, B, q,
-                                          b0, skip_pack.bias, n->bf0.p));
-            ConvStripArgs k;
-            k.Xhi = PBh; k.Xlo = PBl; k.ldn = HW; k.sX = (long)C * HW; k.xslot = hslot(i);
-            k.A = reinterpret_cast<const _Float16*>(n->Wq0.p); k.sA = (long)C * C * 2; k.aslot = slot(sb + 8);
-            k.bias = n->bf0.p; k.sbias = C;
-            k.Cf = n->T.p; k.sCf = actB;
-            k.C = C; k.M = C; k.HW = (int)HW; k.nbatch = B; k.act = ACT_NONE;
-            HIP_TRY(launch_conv_ws(k, q));
-            forked = n->skip_fork == 1;
-            ride = nullptr;   // (packed above)
-            packed_early = true;
-        }
-#endif
-        if (h_planes_only)   // the block input exists as planes only (written by the previous block's fc2, mode 4)
-            ACE_TRY(run_dft_forward(fwd, nullptr, a0, b0, n->X.p, B, C, s, xmax, PBh, PBl, (long)C * HW, hslot(i), ride, &skip_pack_rode));
+// norm0.  Instance norm: an affine (f.a0, f.b0) applied on load by every consumer, never materialised.  Conditional layer norm
+// (NoiseConditionedSFNO) and "layer_norm" (nn.LayerNorm over (H, W) with an (H, W) affine, sfnonet.py:584-592 - a per-PIXEL affine
+// does not fold into the consumers' weights): materialised in place, with their true max in the slot of the instance-norm bound.
+static int enqueue_norm0(Fwd& f, int i, const BlockRoute& b) {
+    const ace_sfno* n = f.n;
+    const int C = n->C, sb = 16 + 12 * i, kind = n->cfg.normalization_layer;
+    const std::string p = "blocks." + std::to_string(i) + ".";
+    if (n->cfg.precision == 1 && i + 1 >= 8) HIP_TRY(launch_zero_u32(f.hslot(i + 1), AMAX_SHARDS, f.s));
+    f.a0 = f.b0 = nullptr;
+    f.n0_planes = false;
+    if (kind == 0) return ACE_OK;
+    if (kind == 2) {   // x_norm = CLN0(h; noise), in place: the block never needs the un-normalised h again (sfnonet.py:388-437)
+        ACE_TRY(cond_norm(f, f.h, f.h, p + "norm0.", C, f.slot(sb + 3), b.n0_to_planes ? f.PAh : nullptr,
+                          b.n0_to_planes ? f.Pl() : nullptr, true, &f.n0_planes));
+    } else if (kind == 3) {   // x_norm = LayerNorm_(H, W)(h), in place
+        HIP_TRY(launch_spatial_layer_norm(f.h, f.W(p + "norm0.weight"), f.W(p + "norm0.bias"), 1e-6f, (long)f.B * C, f.HW, f.h, f.slot(sb + 3), f.s));
+    } else {
+        if (b.in_planes)   // statistics of h came out of the producer's epilogue
+            HIP_TRY(launch_instnorm_finalize(reinterpret_cast<const float4*>(f.part_h), b.in_nparts, f.B, C, f.HW,
+                                             f.W(p + "norm0.weight"), f.W(p + "norm0.bias"), 1e-6f, f.sc0, f.sh0, f.slot(sb + 3), f.s));
         else
-            ACE_TRY(run_dft_forward(fwd, h, a0, b0, n->X.p, B, C, s, xmax, nullptr, nullptr, 0, nullptr, ride, &skip_pack_rode));
-#ifdef ACE_MEASUREMENT_SWITCHES
-        if (packed_early) skip_pack_rode = true;
-#endif
-        MARK(ST_DFT_FWD);
-        // packed dhconv: D goes from the Legendre epilogue to the filter GEMM as fp16 planes (never fp32)
-        const bool dplanes = f16 && !n->sw.no_pk_sht && c.operator_type == 1 && n->wx_hi[i].p && !scale_residual && fwd.f16 &&
-                             N2 % 4 == 0 && (2 * C) % 32 == 0;
-        ACE_TRY(run_legendre_forward(fwd, n->X.p, n->D.p, N2, s, xmax, dmax, dplanes));
-        MARK(ST_LEGENDRE_FWD);
-        const float* res = h;           // residual = x_norm, applied as (h, a0, b0)
-        const float *ra = a0, *rb = b0;
-        if (scale_residual) {           // residual = inverse(forward(x_norm)) on the output grid
-            ACE_TRY(run_legendre_inverse(inv, n->D.p, n->X.p, N2, s, dmax));
-            MARK(ST_LEGENDRE_INV);
-            ACE_TRY(run_dft_inverse(inv, n->X.p, nullptr, n->R.p, B, C, s));
-            MARK(ST_DFT_INV);
-            res = n->R.p; ra = nullptr; rb = nullptr;
-        }
-        if (c.operator_type == 1) {  // dhconv (contractions.py:183-195): per l, (m,b) x 2C times real 2C x 2C
-            GemmArgs g;
-            g.A = n->D.p; g.lda = 2 * C; g.sA = (long)n->Mm * N2;
-            g.B = n->wx[i].p; g.ldb = 2 * C; g.sB = (long)2 * C * 2 * C;
-            g.C = n->E.p; g.ldc = 2 * C; g.sC = (long)n->Mm * N2;
-            g.M = n->Mm * B; g.N = 2 * C; g.K = 2 * C; g.nbatch = n->L; g.a_kpad = 2 * C;
-            g.tri = TRI_ROWS_LE_BATCH; g.trimul = B;
-            g.omax = emax;
-            DhconvStripArgs ds;
-            if (dplanes && n->wx_compact[i]) {
-                ds.Dhi = reinterpret_cast<const _Float16*>(n->D.p);
-                ds.Dlo = ds.Dhi + (size_t)n->L * n->Mm * N2;
-                ds.sD = (long)n->Mm * N2; ds.amax = dmax;
-                ds.Whi = reinterpret_cast<const _Float16*>(n->wx_hi[i].p);
-                ds.Wlo = reinterpret_cast<const _Float16*>(n->wx_lo[i].p);
-                ds.sW = (long)2 * C * C; ds.bscale = n->wx_scale[i];
-                ds.E = n->E.p; ds.sE = (long)n->Mm * N2; ds.omax = emax;
-                ds.C = C; ds.L = n->L; ds.Mrows = n->Mm * B; ds.trimul = B;
-                ds.groups = cln ? c.filter_num_groups : 1;
-                if (n->wx_native[i]) { ds.kstore = C / ds.groups; ds.sW = (long)2 * ds.kstore * C; }
-                if ((int)n->dh_units.size() >= B) { ds.units = reinterpret_cast<const int*>(n->dh_units[B - 1].p); ds.units_per_xcd = n->dh_units_per_xcd[B - 1]; }
-            }
-            if (n->wx_native[i] && !(dplanes && ds.units && dhconv_strip_eligible(ds)))
-                return fail(ACE_ERR_STATE, "grouped filter stored as diagonal blocks, but the strip kernel cannot run this launch");
-            if (dplanes && n->wx_compact[i] && !n->sw.no_dhconv_strip && ds.units && dhconv_strip_eligible(ds)) {
-                HIP_TRY(launch_dhconv_strip(ds, s));
-            } else if (dplanes) {
-                Gemm4Args a;
-                a.Ahi = reinterpret_cast<const _Float16*>(n->D.p);
-                a.Alo = a.Ahi + (size_t)n->L * n->Mm * N2;
-                a.lda = 2 * C; a.sA = (long)n->Mm * N2; a.amax = dmax;
-                a.Bhi = reinterpret_cast<const _Float16*>(n->wx_hi[i].p);
-                a.Blo = reinterpret_cast<const _Float16*>(n->wx_lo[i].p);
-                a.ldn = 2 * C; a.sB = (long)2 * C * 2 * C; a.bscale = n->wx_scale[i];
-                if (n->wx_compact[i]) { a.cplx = C; a.ldn = C; a.sB = (long)2 * C * C; a.tile = 1; }
-                a.C = n->E.p; a.ldc = 2 * C; a.sC = (long)n->Mm * N2; a.omax = emax;
-                a.M = n->Mm * B; a.N = 2 * C; a.K = 2 * C; a.nbatch = n->L;
-                a.tri = TRI_ROWS_LE_BATCH; a.trimul = B;
-                HIP_TRY(launch_gemm_f16x3_packed(a, s));
-            } else if (f16 && n->wx_hi[i].p && n->wx_compact[i]) {
-                return fail(ACE_ERR_STATE, "compact dhconv operand without the packed path");
-            } else if (f16 && n->wx_hi[i].p) {
-                HIP_TRY(launch_gemm_f16x3_adyn(g, n->wx_hi[i].p, n->wx_lo[i].p, 2 * C, (long)2 * C * 2 * C, n->wx_scale[i],
-                                               dmax, emax, s));
-            } else {
-                HIP_TRY(launch_gemm(g, s));
-            }
-        } else {
-            HIP_TRY(launch_contract_diagonal(n->D.p, W(p + "filter.filter.weight"), n->E.p, B, C, C, n->L, n->Mm, s, emax));
-        }
-        MARK(ST_CONTRACT);
-        ACE_TRY(run_legendre_inverse(inv, n->E.p, n->X.p, N2, s, emax));
-        MARK(ST_LEGENDRE_INV);
-        ACE_TRY(run_dft_inverse(inv, n->X.p, W(p + "filter.filter.bias"), n->Y.p, B, C, s, slot(sb + 7)));
-        MARK(ST_DFT_INV);
-        // everything behind the filter works on ITS output grid (sfnonet.py:217-252: the skips, norm1 and the MLP see what the
-        // inverse transform produced) - the inner grid after the first block of a scale_factor != 1 net, the data grid after the last
-        HW = (long)inv.nlat * inv.nlon; actB = (long)C * HW; n->hw_now = HW;
-#ifdef ACE_MEASUREMENT_SWITCHES
-        if (forked) { HIP_TRY(hipEventRecord(n->ev_join, n->side_stream)); HIP_TRY(hipStreamWaitEvent(s, n->ev_join, 0)); }
-#endif
-
-        // x = act(filter + inner_skip(residual))   (sfnonet.py:229-232)
-        ConvW wskip = conv_weight(n, p + "inner_skip.weight", p + "inner_skip.bias");
-        // B of the inner skip: the normalised block input (bound from the norm statistics) or, without a norm, the raw
-        // block input; the spectrally round-tripped residual of mixed-grid blocks has no range slot -> fp32 engine
-        const unsigned* skip_max = scale_residual ? nullptr : ((norm || cln || lnrm) ? slot(sb + 3) : hslot(i));
-        const bool skip_f16 = f16 && skip_max != nullptr;
-        const bool pk = skip_f16 && packed_ok(n, C) && (!c.use_mlp || n->hid % 8 == 0);
-        _Float16* Ph = reinterpret_cast<_Float16*>(n->P.p);
-        _Float16* Pl = Ph + (size_t)n->Bmax * C * HW;
-        const bool fused = pk && norm && c.use_mlp && n->P2.p != nullptr;
-        const bool have_ph_in = have_ph;   // P2 holds the RAW block input as planes (bound in hslot(i)), from a producer epilogue
-        if (fused) {
-            // Packed-operand path with the instance norms fused away: every conv input is P-format planes written by
-            // its producer's epilogue, the norm affine is folded into the consumer's weights, the norm statistics come
-            // out of the producer's epilogue.  No pass over an activation other than the GEMMs themselves.
-            const Weight& ws = *n->weights[n->index.at(p + "inner_skip.weight")];
-            const Weight& bsw = *n->weights[n->index.at(p + "inner_skip.bias")];
-            const Weight& w1 = *n->weights[n->index.at(p + "mlp.fwd.0.weight")];
-            const Weight& b1w = *n->weights[n->index.at(p + "mlp.fwd.0.bias")];
-            const Weight& w2 = *n->weights[n->index.at(p + "mlp.fwd.2.weight")];
-            const Weight& b2w = *n->weights[n->index.at(p + "mlp.fwd.2.bias")];
-            const long cp = ws.pitch;
-            _Float16* F0h = reinterpret_cast<_Float16*>(n->Wp0.p);
-            const long f0s = (long)((C + 15) / 16 * 16) * cp;
-            _Float16* F0l = F0h + (size_t)n->Bmax * f0s;
-            _Float16* F1h = reinterpret_cast<_Float16*>(n->Wp1.p);
-            const long f1s = (long)((n->hid + 15) / 16 * 16) * cp;
-            _Float16* F1l = F1h + (size_t)n->Bmax * f1s;
-            _Float16* Uh = reinterpret_cast<_Float16*>(n->U.p);
-            _Float16* Ul = Uh + (size_t)n->Bmax * n->hid * HW;
-            const bool last = (i + 1 == c.num_layers);
-            // inner skip: T = act(Y + Ws norm0(h) + bs), written as P-format planes only (+ its row statistics)
-            PkOpts o;
-            o.w = &ws; o.cin = C; o.cout = C; o.act = act;
-            o.R = n->Y.p; o.r_bs = actB;
-            o.ohi = PAh; o.olo = PAl; o.cb = bsw.absmax; o.cslot = slot(sb + 4); o.cinb = slot(sb + 3); o.rmax = slot(sb + 7);
-            o.part = part_t;
-            const bool gelu = c.activation_function == ACT_GELU;
-            const int roles = n->sw.conv_ws_roles;
-            // which of the three convolutions run on the weight-stationary kernel (conv_ws.hip); the others on the tile engine
-            const bool ws_skip = gelu && n->Wq0.p && ws.frag0.p && conv_ws_eligible(C, C, HW, 0, roles);
-            const bool wl_fc1 = gelu && n->Wq1.p && n->sw.conv_wl && conv_wl_eligible(C, n->hid, HW);
-            const bool ws_fc1 = wl_fc1 || (gelu && n->Wq1.p && conv_ws_eligible(C, n->hid, HW, 1, roles));
-            const bool ws_fc2 = w2.frag0.p && C <= 1024 && conv_ws_eligible(n->hid, C, HW, 2, roles);
-            if (have_ph) {   // h planes from the previous fc2; the affine goes into the weights
-                if (!ws_skip)
-                    HIP_TRY(launch_fold_affine_f16(ws.buf.p, ws.pitch, ws.wabs, ra, rb, bsw.buf.p, F0h, F0l, n->bf0.p, B, C, C, cp,
-                                                   f0s, slot(sb + 8), s));
-                o.fhi = F0h; o.flo = F0l; o.fslot = slot(sb + 8); o.f_stride = f0s;
-                o.bias = n->bf0.p; o.sbias = C;
-                o.bhi = PBh; o.blo = PBl; o.in_slot = hslot(i);
-            } else {         // first block: normalise + split h in one pass
-                ACE_TRY(pack_act(n, res, actB, C, ra, rb, skip_max, PBh, PBl, B, s));
-                o.bias = bsw.buf.p;
-                o.bhi = PBh; o.blo = PBl; o.in_slot = skip_max;
-            }
-            int t_nparts = gemm4_strips(C, (int)HW);
-            if (ws_skip) {
-                ConvStripArgs k;
-                k.Xhi = PBh; k.Xlo = PBl; k.ldn = HW; k.sX = (long)C * HW; k.xslot = o.in_slot;
-                if (have_ph) {
-                    _Float16* Q0 = reinterpret_cast<_Float16*>(n->Wq0.p);
-                    if (!skip_pack_rode)   // (packed by rider workgroups of this block's forward FFT otherwise)
-                        HIP_TRY(launch_pack_conv_frag(ws.buf.p, ws.pitch, C, C, 0, ra, ws.wabs, 1.f, slot(sb + 8), Q0, (long)C * C * 2, B, s,
-                                                      rb, bsw.buf.p, n->bf0.p));
-                    k.A = Q0; k.sA = (long)C * C * 2; k.aslot = slot(sb + 8);
-                } else {
-                    k.A = reinterpret_cast<const _Float16*>(ws.frag0.p); k.sA = 0; k.ascale = ws.ascale;
-                }
-                k.bias = o.bias; k.sbias = o.sbias;
-                k.R = n->Y.p; k.sR = actB;
-                k.cw = ws.winf; k.cb = bsw.absmax; k.cinb = slot(sb + 3); k.rmax = slot(sb + 7);
-                k.Chi = PAh; k.Clo = PAl; k.sCp = (long)C * HW; k.cslot = slot(sb + 4);
-                k.part = reinterpret_cast<float4*>(part_t);
-                k.C = C; k.M = C; k.HW = (int)HW; k.nbatch = B; k.act = ACT_GELU;
-                k.nstrips32 = conv_ws_stat_parts(k);   // one partial per pixel group (statistics accumulated in registers)
-                HIP_TRY(launch_conv_ws(k, s));
-                t_nparts = k.nstrips32;
-            } else {
-                ACE_TRY(conv_pk2(n, o, B, s));
-            }
-            MARK(ST_INNER_SKIP);
-            // norm1 statistics -> affine -> folded fc1 weights
-            HIP_TRY(launch_instnorm_finalize(reinterpret_cast<const float4*>(part_t), t_nparts, B, C, HW,
-                                             W(p + "norm1.weight"), W(p + "norm1.bias"), 1e-6f, sc1, sh1, slot(sb + 5), s));
-            if (ws_fc1) {
-                _Float16* Q1 = reinterpret_cast<_Float16*>(n->Wq1.p);
-                const long q1s = (long)n->hid * C * 2;
-                // W1 diag(a1), b1 + W1 b1' folded in the convolution's own prologue (conv_wl.hip at the ACE2 width: +1.4 us against a 6.7 us launch)
-                const bool pfold = n->sw.fused_pack && wl_fc1 && C == 384 && w1.pitch % 4 == 0;
-                if (!pfold)
-                    HIP_TRY(launch_pack_conv_frag(w1.buf.p, w1.pitch, n->hid, C, 0, sc1, w1.wabs, 1.f, slot(sb + 9), Q1, q1s, B, s,
-                                                  sh1, b1w.buf.p, n->bf1.p));
-                MARK(ST_NORM1);
-                ConvStripArgs k;
-                k.Xhi = PAh; k.Xlo = PAl; k.ldn = HW; k.sX = (long)C * HW; k.xslot = slot(sb + 4);
-                if (pfold) {
-                    k.Wraw = w1.buf.p; k.ldw = w1.pitch; k.wabs = w1.wabs; k.fa = sc1; k.fb = sh1; k.sfa = C;
-                    k.bias = b1w.buf.p; k.sbias = 0;
-                } else {
-                    k.A = Q1; k.sA = q1s; k.aslot = slot(sb + 9);
-                    k.bias = n->bf1.p; k.sbias = n->hid;
-                }
-                k.cw = w1.winf; k.cb = b1w.absmax; k.cinb = slot(sb + 5);
-                k.Chi = Uh; k.Clo = Ul; k.sCp = (long)n->hid * HW; k.cslot = slot(sb + 6);
-                k.C = C; k.M = n->hid; k.HW = (int)HW; k.nbatch = B; k.act = ACT_GELU;
-                HIP_TRY(wl_fc1 ? launch_conv_wl(k, s) : launch_conv_ws(k, s));
-            } else {
-                HIP_TRY(launch_fold_affine_f16(w1.buf.p, w1.pitch, w1.wabs, sc1, sh1, b1w.buf.p, F1h, F1l, n->bf1.p, B, n->hid, C,
-                                               cp, f1s, slot(sb + 9), s));
-                MARK(ST_NORM1);
-                PkOpts f1;
-                f1.w = &w1; f1.fhi = F1h; f1.flo = F1l; f1.fslot = slot(sb + 9); f1.f_stride = f1s;
-                f1.bias = n->bf1.p; f1.sbias = n->hid;
-                f1.bhi = PAh; f1.blo = PAl; f1.cin = C; f1.in_slot = slot(sb + 4);
-                f1.cout = n->hid; f1.act = act;
-                f1.ohi = Uh; f1.olo = Ul; f1.cb = b1w.absmax; f1.cslot = slot(sb + 6); f1.cinb = slot(sb + 5);
-                ACE_TRY(conv_pk2(n, f1, B, s));
-            }
-            MARK(ST_MLP_FC1);
-            if (ws_fc2) {
-                // fc2 + outer skip: fp32 h' (+ planes and statistics for the next block)
-                ConvStripArgs k;
-                k.Xhi = Uh; k.Xlo = Ul; k.ldn = HW; k.sX = (long)n->hid * HW; k.xslot = slot(sb + 6);
-                k.A = reinterpret_cast<const _Float16*>(w2.frag0.p); k.sA = 0; k.ascale = w2.ascale;
-                k.bias = b2w.buf.p; k.sbias = 0;
-                // residual = a0 h + b0: from the fp32 h, or - when the block input came as planes from a producer epilogue (raw h,
-                // bound in hslot(i)) - from those planes; then a mid block writes h' as planes only
-                const bool rpl = stream_ok && have_ph_in;
-                k.rsc = ra; k.rsh = rb; k.srs = C;
-                if (rpl) { k.Rhi = PBh; k.Rlo = PBl; k.sRp = (long)C * HW; k.rslot = hslot(i); }
-                else { k.R = res; k.sR = actB; }
-                if (last || !rpl) { k.Cf = hn; k.sCf = actB; }
-                h_planes_only = !last && rpl;
-                k.C = n->hid; k.M = C; k.HW = (int)HW; k.nbatch = B; k.act = ACT_NONE;
-                const int nparts = conv_ws_stat_parts(k);   // one partial per workgroup and row (accumulated in LDS)
-                if (!last) {
-                    k.Chi = PBh; k.Clo = PBl; k.sCp = (long)C * HW; k.cslot = hslot(i + 1);
-                    k.cw = w2.winf; k.cb = b2w.absmax; k.rmax = slot(sb + 3);
-                    k.part = reinterpret_cast<float4*>(part_h); k.nstrips32 = nparts;
-                } else {
-                    k.omax = hslot(i + 1);
-                }
-                HIP_TRY(launch_conv_ws(k, s));
-                h_nparts = nparts;
-            } else {
-                PkOpts f2;
-                f2.w = &w2; f2.bias = b2w.buf.p;
-                f2.bhi = Uh; f2.blo = Ul; f2.cin = n->hid; f2.in_slot = slot(sb + 6);
-                f2.out = hn; f2.cout = C; f2.act = ACT_NONE;
-                f2.R = res; f2.r_bs = actB; f2.rsc = ra; f2.rsh = rb;
-                if (!last) {   // next block: h planes + statistics, bound instead of the true max in the h slot
-                    f2.ohi = PBh; f2.olo = PBl; f2.cb = b2w.absmax; f2.cslot = hslot(i + 1); f2.rmax = slot(sb + 3);
-                    f2.part = part_h;
-                } else {
-                    f2.omax = hslot(i + 1);
-                }
-                ACE_TRY(conv_pk2(n, f2, B, s));
-                h_nparts = gemm4_strips(C, (int)HW);
-                h_planes_only = false;
-            }
-            have_ph = have_hstats = !last;
-        } else if (pk) {
-            have_ph = have_hstats = false;
-            const Weight& ws = *n->weights[n->index.at(p + "inner_skip.weight")];
-            if (!n0_planes) ACE_TRY(pack_act(n, res, actB, C, ra, rb, skip_max, Ph, Pl, B, s));
-            const bool gelu0 = act == ACT_GELU || act == ACT_GELU_FAST;
-            if (cln && gelu0 && ws.frag0.p && cln_skip_on_conv_ws(n, C, C)) {
-                // weight-stationary kernel, mode 6: GELU(W . planes + bias + Y) -> fp32 T (the conditional norm that follows reads fp32)
-                ConvStripArgs k;
-                k.Xhi = Ph; k.Xlo = Pl; k.ldn = HW; k.sX = (long)C * HW; k.xslot = skip_max;
-                k.A = reinterpret_cast<const _Float16*>(ws.frag0.p); k.sA = 0; k.ascale = ws.ascale;
-                k.bias = W(p + "inner_skip.bias"); k.sbias = 0;
-                k.R = n->Y.p; k.sR = actB;
-                k.Cf = n->T.p; k.sCf = actB; k.omax = slot(sb + 4);
-                k.C = C; k.M = C; k.HW = (int)HW; k.nbatch = B; k.act = act;
-                HIP_TRY(launch_conv_ws(k, s));
-            } else {
-                ACE_TRY(conv_pk(n, ws, W(p + "inner_skip.bias"), Ph, Pl, C, skip_max, n->T.p, C, n->Y.p, actB, nullptr, nullptr,
-                                act, B, s, slot(sb + 4)));
-            }
-        } else {
-            if (ra && !skip_f16) ACE_TRY(fold(n, wskip, C, C, ra, rb, n->Wf0.p, n->bf0.p, B, s, &wskip));
-            ACE_TRY(conv(n, wskip, res, actB, C, nullptr, 0, -1, n->T.p, C, n->Y.p, actB, nullptr, nullptr, act, B, s,
-                         skip_f16 ? ra : nullptr, skip_f16 ? rb : nullptr, skip_max, nullptr, slot(sb + 4)));
-        }
-        if (!fused) MARK(ST_INNER_SKIP);
-        // norm1 -> MLP -> + residual   (sfnonet.py:234-250)
-        const float *a1 = nullptr, *b1 = nullptr;
-        if (cln) {   // followed by the packed MLP, norm1's output exists as planes only
-            const bool to_mlp = c.use_mlp && pk && !n->taps_on;
-            ACE_TRY(cond_norm(n->T.p, n->T.p, p + "norm1.", C, slot(sb + 5), to_mlp ? Ph : nullptr, to_mlp ? Pl : nullptr, false, &n1_planes));
-            MARK(ST_NORM1);
-        }
-        if (lnrm) {
-            HIP_TRY(launch_spatial_layer_norm(n->T.p, W(p + "norm1.weight"), W(p + "norm1.bias"), 1e-6f, (long)B * C, HW, n->T.p, slot(sb + 5), s));
-            MARK(ST_NORM1);
-        }
-        if (norm && !fused) {
-            HIP_TRY(launch_instnorm_stats(n->T.p, W(p + "norm1.weight"), W(p + "norm1.bias"), 1e-6f, B, C, HW, sc1, sh1, s,
-                                          slot(sb + 5)));
-            a1 = sc1; b1 = sh1;
-            MARK(ST_NORM1);
-        }
-        if (fused) {
-            // done above
-        } else if (c.use_mlp && pk) {
-            // fc1 reads norm1(T) packed; its epilogue writes U = act(.) straight in P format (bound-scaled), which fc2
-            // consumes by DMA: the hidden activation never exists in fp32
-            const Weight& w1 = *n->weights[n->index.at(p + "mlp.fwd.0.weight")];
-            const Weight& b1w = *n->weights[n->index.at(p + "mlp.fwd.0.bias")];
-            const Weight& w2 = *n->weights[n->index.at(p + "mlp.fwd.2.weight")];
-            const unsigned* tmax = (norm || cln || lnrm) ? slot(sb + 5) : slot(sb + 4);
-            _Float16* Uh = reinterpret_cast<_Float16*>(n->U.p);
-            _Float16* Ul = Uh + (size_t)n->Bmax * n->hid * HW;
-            if (!n1_planes) ACE_TRY(pack_act(n, n->T.p, actB, C, a1, b1, tmax, Ph, Pl, B, s));
-            const bool gelu1 = act == ACT_GELU || act == ACT_GELU_FAST;
-            if (w1.frag0.p && !a1 && gelu1 && n->sw.conv_wl && conv_wl_eligible(C, n->hid, HW)) {
-                // weights in LDS, unsynchronised waves (conv_wl.hip): the noise-conditioned nets' fc1 (no norm affine to fold)
-                ConvStripArgs k;
-                k.Xhi = Ph; k.Xlo = Pl; k.ldn = HW; k.sX = (long)C * HW; k.xslot = tmax;
-                k.A = reinterpret_cast<const _Float16*>(w1.frag0.p); k.sA = 0; k.ascale = w1.ascale;
-                k.bias = b1w.buf.p; k.sbias = 0;
-                k.cw = w1.winf; k.cb = b1w.absmax;
-                k.Chi = Uh; k.Clo = Ul; k.sCp = (long)n->hid * HW; k.cslot = slot(sb + 6);
-                k.C = C; k.M = n->hid; k.HW = (int)HW; k.nbatch = B; k.act = ACT_GELU;
-                HIP_TRY(launch_conv_wl(k, s));
-            } else {
-                ACE_TRY(conv_pk(n, w1, b1w.buf.p, Ph, Pl, C, tmax, nullptr, n->hid, nullptr, 0, nullptr, nullptr, act, B, s,
-                                nullptr, Uh, Ul, b1w.absmax, slot(sb + 6)));
-            }
-            MARK(ST_MLP_FC1);
-            ACE_TRY(conv_pk(n, w2, W(p + "mlp.fwd.2.bias"), Uh, Ul, n->hid, slot(sb + 6), hn, C, res, actB, ra, rb, ACT_NONE,
-                            B, s, hslot(i + 1)));
-        } else if (c.use_mlp) {
-            ConvW wfc1 = conv_weight(n, p + "mlp.fwd.0.weight", p + "mlp.fwd.0.bias");
-            if (a1 && !f16) ACE_TRY(fold(n, wfc1, n->hid, C, a1, b1, n->Wf1.p, n->bf1.p, B, s, &wfc1));
-            ACE_TRY(conv(n, wfc1, n->T.p, actB, C, nullptr, 0, -1, n->U.p, n->hid, nullptr, 0, nullptr, nullptr, act, B, s,
-                         f16 ? a1 : nullptr, f16 ? b1 : nullptr, (norm || cln || lnrm) ? slot(sb + 5) : slot(sb + 4), nullptr,
-                         slot(sb + 6)));
-            MARK(ST_MLP_FC1);
-            ACE_TRY(conv(n, conv_weight(n, p + "mlp.fwd.2.weight", p + "mlp.fwd.2.bias"), n->U.p, (long)n->hid * HW,
-                         n->hid, nullptr, 0, -1, hn, C, res, actB, ra, rb, ACT_NONE, B, s, nullptr, nullptr, slot(sb + 6),
-                         nullptr, hslot(i + 1)));
-        } else {
-            HIP_TRY(launch_rowaffine_add(n->T.p, a1, b1, res, ra, rb, hn, (long)B * C, HW, s));
-        }
-        MARK(ST_MLP_FC2);
-        std::swap(h, hn);
-        if (n->taps_on)
-            HIP_TRY(hipMemcpyAsync(n->taps[i + 1].p, h, sizeof(float) * B * actB, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(launch_instnorm_stats(f.h, f.W(p + "norm0.weight"), f.W(p + "norm0.bias"), 1e-6f, f.B, C, f.HW, f.sc0, f.sh0, f.s,
+                                          f.slot(sb + 3)));
+        f.a0 = f.sc0; f.b0 = f.sh0;
     }
+    MARK(ST_NORM0);
+    return ACE_OK;
+}
 
-    // ---- decoder on cat(x, input) (sfnonet.py:741-747); the concat is two row sources of one GEMM
-    cur = h; cur_bs = actB; curC = C;
+// spectral filter, first half (s2convolutions.py:162-197): longitude DFT and Legendre transform of x_norm; on a mixed-grid block
+// also the residual = inverse(forward(x_norm)) on the output grid
+static int enqueue_forward_transform(Fwd& f, int i, const BlockRoute& b) {
+    const ace_sfno* n = f.n;
+    const int C = n->C, sb = 16 + 12 * i, B = f.B;
+    const long N2 = (long)B * 2 * C;
+    unsigned *xmax = f.slot(sb + 0), *dmax = f.slot(sb + 1);
+    // (Round 4 tried packing the inner skip's folded weights on a side stream beside the SHT chain - they depend on norm0's
+    // statistics only.  Same box, whole step in a hipGraph: 5.76 -> 5.86 ms; the fork / join edges cost more than the 7 us
+    // kernel they hide.  profiles/r04_s3_kdur_side_pack_*.txt)
+    PackFragArgs skip_pack;
+    if (b.ride_skip_pack) {
+        const std::string p = "blocks." + std::to_string(i) + ".";
+        const Weight& wsk = f.wt(p + "inner_skip.weight");
+        skip_pack.W = wsk.buf.p; skip_pack.ldw = wsk.pitch; skip_pack.O = C; skip_pack.I = C; skip_pack.order = 0;
+        skip_pack.a = f.a0; skip_pack.wmax = wsk.wabs; skip_pack.scale_static = 1.f; skip_pack.wslot = f.slot(sb + 8);
+        skip_pack.dst = reinterpret_cast<_Float16*>(n->Wq0.p); skip_pack.sDst = (long)C * C * 2;
+        skip_pack.b = f.b0; skip_pack.bias = f.wt(p + "inner_skip.bias").buf.p; skip_pack.bf = n->bf0.p; skip_pack.nsamples = B;
+    }
+    const PackFragArgs* ride = b.ride_skip_pack ? &skip_pack : nullptr;
+    if (b.in_planes_only)
+        ACE_TRY(run_dft_forward(*b.fwd, nullptr, f.a0, f.b0, n->X.p, B, C, f.s, xmax, f.PBh, f.PBl, (long)C * f.HW, f.hslot(i), ride, &f.skip_pack_rode));
+    else
+        ACE_TRY(run_dft_forward(*b.fwd, f.h, f.a0, f.b0, n->X.p, B, C, f.s, xmax, nullptr, nullptr, 0, nullptr, ride, &f.skip_pack_rode));
+    MARK(ST_DFT_FWD);
+    ACE_TRY(run_legendre_forward(*b.fwd, n->X.p, n->D.p, N2, f.s, xmax, dmax, b.dplanes));
+    MARK(ST_LEGENDRE_FWD);
+    f.res = f.h; f.ra = f.a0; f.rb = f.b0;
+    if (b.scale_residual) {
+        ACE_TRY(run_legendre_inverse(*b.inv, n->D.p, n->X.p, N2, f.s, dmax));
+        MARK(ST_LEGENDRE_INV);
+        ACE_TRY(run_dft_inverse(*b.inv, n->X.p, nullptr, n->R.p, B, C, f.s));
+        MARK(ST_DFT_INV);
+        f.res = n->R.p; f.ra = nullptr; f.rb = nullptr;
+    }
+    return ACE_OK;
+}
+
+// the filter itself.  dhconv (contractions.py:183-195): per l, (m,b) x 2C times real 2C x 2C
+static int enqueue_contraction(Fwd& f, int i, const BlockRoute& b) {
+    const ace_sfno* n = f.n;
+    const int C = n->C, sb = 16 + 12 * i, B = f.B;
+    const long N2 = (long)B * 2 * C;
+    unsigned *dmax = f.slot(sb + 1), *emax = f.slot(sb + 2);
+    switch (b.filter) {
+    case FLT_DHCONV_STRIP:
+        HIP_TRY(launch_dhconv_strip(dhconv_strip_args(n, i, B, dmax, emax), f.s));
+        break;
+    case FLT_PACKED_TILE: {
+        Gemm4Args a;
+        a.Ahi = reinterpret_cast<const _Float16*>(n->D.p);
+        a.Alo = a.Ahi + (size_t)n->L * n->Mm * N2;
+        a.lda = 2 * C; a.sA = (long)n->Mm * N2; a.amax = dmax;
+        a.Bhi = reinterpret_cast<const _Float16*>(n->wx_hi[i].p);
+        a.Blo = reinterpret_cast<const _Float16*>(n->wx_lo[i].p);
+        a.ldn = 2 * C; a.sB = (long)2 * C * 2 * C; a.bscale = n->wx_scale[i];
+        if (n->wx_compact[i]) { a.cplx = C; a.ldn = C; a.sB = (long)2 * C * C; a.tile = 1; }
+        a.C = n->E.p; a.ldc = 2 * C; a.sC = (long)n->Mm * N2; a.omax = emax;
+        a.M = n->Mm * B; a.N = 2 * C; a.K = 2 * C; a.nbatch = n->L;
+        a.tri = TRI_ROWS_LE_BATCH; a.trimul = B;
+        HIP_TRY(launch_gemm_f16x3_packed(a, f.s));
+        break;
+    }
+    case FLT_ADYN_F16X3:
+    case FLT_FP32: {
+        GemmArgs g;
+        g.A = n->D.p; g.lda = 2 * C; g.sA = (long)n->Mm * N2;
+        g.B = n->wx[i].p; g.ldb = 2 * C; g.sB = (long)2 * C * 2 * C;
+        g.C = n->E.p; g.ldc = 2 * C; g.sC = (long)n->Mm * N2;
+        g.M = n->Mm * B; g.N = 2 * C; g.K = 2 * C; g.nbatch = n->L; g.a_kpad = 2 * C;
+        g.tri = TRI_ROWS_LE_BATCH; g.trimul = B;
+        g.omax = emax;
+        if (b.filter == FLT_ADYN_F16X3)
+            HIP_TRY(launch_gemm_f16x3_adyn(g, n->wx_hi[i].p, n->wx_lo[i].p, 2 * C, (long)2 * C * 2 * C, n->wx_scale[i], dmax, emax, f.s));
+        else
+            HIP_TRY(launch_gemm(g, f.s));
+        break;
+    }
+    case FLT_DIAGONAL:
+        HIP_TRY(launch_contract_diagonal(n->D.p, f.W("blocks." + std::to_string(i) + ".filter.filter.weight"), n->E.p, B, C, C, n->L, n->Mm, f.s, emax));
+        break;
+    }
+    MARK(ST_CONTRACT);
+    return ACE_OK;
+}
+
+// spectral filter, second half: inverse transforms + bias -> Y.  What follows works on the filter's OUTPUT grid.
+static int enqueue_inverse_transform(Fwd& f, int i, const BlockRoute& b) {
+    const ace_sfno* n = f.n;
+    const int sb = 16 + 12 * i;
+    ACE_TRY(run_legendre_inverse(*b.inv, n->E.p, n->X.p, (long)f.B * 2 * n->C, f.s, f.slot(sb + 2)));
+    MARK(ST_LEGENDRE_INV);
+    ACE_TRY(run_dft_inverse(*b.inv, n->X.p, f.W("blocks." + std::to_string(i) + ".filter.filter.bias"), n->Y.p, f.B, n->C, f.s, f.slot(sb + 7)));
+    MARK(ST_DFT_INV);
+    f.HW = b.hw_out;
+    return ACE_OK;
+}
+
+// Body of a block with the instance norms fused away: x = act(filter + inner_skip(residual)), norm1 -> MLP -> + residual
+// (sfnonet.py:229-250).  Every conv input is P-format planes written by its producer's epilogue, the norm affine is folded into the
+// consumer's weights, the norm statistics come out of the producer's epilogue: no pass over an activation other than the GEMMs.
+static int enqueue_fused_body(Fwd& f, int i, const BlockRoute& b) {
+    const ace_sfno* n = f.n;
+    const int C = n->C, hid = n->hid, B = f.B, act = n->cfg.activation_function, sb = 16 + 12 * i;
+    const long HW = f.HW, actB = f.actB();
+    hipStream_t s = f.s;
+    const std::string p = "blocks." + std::to_string(i) + ".";
+    const Weight &ws = f.wt(p + "inner_skip.weight"), &bsw = f.wt(p + "inner_skip.bias");
+    const Weight &w1 = f.wt(p + "mlp.fwd.0.weight"), &b1w = f.wt(p + "mlp.fwd.0.bias");
+    const Weight &w2 = f.wt(p + "mlp.fwd.2.weight"), &b2w = f.wt(p + "mlp.fwd.2.bias");
+    const long cp = ws.pitch;
+    _Float16* F0h = reinterpret_cast<_Float16*>(n->Wp0.p);
+    const long f0s = (long)((C + 15) / 16 * 16) * cp;
+    _Float16* F0l = F0h + (size_t)n->Bmax * f0s;
+    _Float16* F1h = reinterpret_cast<_Float16*>(n->Wp1.p);
+    const long f1s = (long)((hid + 15) / 16 * 16) * cp;
+    _Float16* F1l = F1h + (size_t)n->Bmax * f1s;
+    _Float16 *Uh = f.Uh(), *Ul = f.Ul();
+
+    // inner skip: T = act(Y + Ws norm0(h) + bs), written as P-format planes only (+ its row statistics)
+    const float* skip_bias = bsw.buf.p;
+    long skip_sbias = 0;
+    const unsigned* in_slot = f.slot(b.skip_slot);
+    if (b.in_planes) {   // h planes from the producer; the affine goes into the weights
+        if (b.skip != CONV_WS)
+            HIP_TRY(launch_fold_affine_f16(ws.buf.p, ws.pitch, ws.wabs, f.ra, f.rb, bsw.buf.p, F0h, F0l, n->bf0.p, B, C, C, cp, f0s, f.slot(sb + 8), s));
+        skip_bias = n->bf0.p; skip_sbias = C; in_slot = f.hslot(i);
+    } else {             // first block: normalise + split h in one pass
+        ACE_TRY(pack_act(f, f.res, actB, C, f.ra, f.rb, in_slot, f.PBh, f.PBl));
+    }
+    if (b.skip == CONV_WS) {
+        ConvStripArgs k = strip_args(f, f.PBh, f.PBl, in_slot, C, C, ACT_GELU);
+        if (b.in_planes) {
+            _Float16* Q0 = reinterpret_cast<_Float16*>(n->Wq0.p);
+            if (!f.skip_pack_rode)   // (packed by rider workgroups of this block's forward FFT otherwise)
+                HIP_TRY(launch_pack_conv_frag(ws.buf.p, ws.pitch, C, C, 0, f.ra, ws.wabs, 1.f, f.slot(sb + 8), Q0, (long)C * C * 2, B, s,
+                                              f.rb, bsw.buf.p, n->bf0.p));
+            k.A = Q0; k.sA = (long)C * C * 2; k.aslot = f.slot(sb + 8);
+        } else {
+            k.A = reinterpret_cast<const _Float16*>(ws.frag0.p); k.sA = 0; k.ascale = ws.ascale;
+        }
+        k.bias = skip_bias; k.sbias = skip_sbias;
+        k.R = n->Y.p; k.sR = actB;
+        k.cw = ws.winf; k.cb = bsw.absmax; k.cinb = f.slot(sb + 3); k.rmax = f.slot(sb + 7);
+        k.Chi = f.PAh; k.Clo = f.PAl; k.sCp = (long)C * HW; k.cslot = f.slot(sb + 4);
+        k.part = reinterpret_cast<float4*>(f.part_t); k.nstrips32 = b.t_nparts;   // one partial per pixel group (accumulated in registers)
+        HIP_TRY(launch_conv_ws(k, s));
+    } else {
+        PkOpts o;
+        o.w = &ws; o.cin = C; o.cout = C; o.act = act;
+        if (b.in_planes) { o.fhi = F0h; o.flo = F0l; o.fslot = f.slot(sb + 8); o.f_stride = f0s; }
+        o.bias = skip_bias; o.sbias = skip_sbias;
+        o.bhi = f.PBh; o.blo = f.PBl; o.in_slot = in_slot;
+        o.R = n->Y.p; o.r_bs = actB;
+        o.ohi = f.PAh; o.olo = f.PAl; o.cb = bsw.absmax; o.cslot = f.slot(sb + 4); o.cinb = f.slot(sb + 3); o.rmax = f.slot(sb + 7);
+        o.part = f.part_t;
+        ACE_TRY(conv_packed(f, o));
+    }
+    MARK(ST_INNER_SKIP);
+
+    // norm1 statistics -> affine -> folded fc1 weights; fc1 writes U = act(.) as planes
+    HIP_TRY(launch_instnorm_finalize(reinterpret_cast<const float4*>(f.part_t), b.t_nparts, B, C, HW, f.W(p + "norm1.weight"),
+                                     f.W(p + "norm1.bias"), 1e-6f, f.sc1, f.sh1, f.slot(sb + 5), s));
+    if (b.fc1 == CONV_WS || b.fc1 == CONV_WL) {
+        _Float16* Q1 = reinterpret_cast<_Float16*>(n->Wq1.p);
+        const long q1s = (long)hid * C * 2;
+        // (pfold: W1 diag(a1), b1 + W1 b1' folded in the convolution's own prologue: +1.4 us against a 6.7 us launch)
+        if (!b.pfold)
+            HIP_TRY(launch_pack_conv_frag(w1.buf.p, w1.pitch, hid, C, 0, f.sc1, w1.wabs, 1.f, f.slot(sb + 9), Q1, q1s, B, s, f.sh1,
+                                          b1w.buf.p, n->bf1.p));
+        MARK(ST_NORM1);
+        ConvStripArgs k = strip_args(f, f.PAh, f.PAl, f.slot(sb + 4), C, hid, ACT_GELU);
+        if (b.pfold) {
+            k.Wraw = w1.buf.p; k.ldw = w1.pitch; k.wabs = w1.wabs; k.fa = f.sc1; k.fb = f.sh1; k.sfa = C;
+            k.bias = b1w.buf.p; k.sbias = 0;
+        } else {
+            k.A = Q1; k.sA = q1s; k.aslot = f.slot(sb + 9);
+            k.bias = n->bf1.p; k.sbias = hid;
+        }
+        k.cw = w1.winf; k.cb = b1w.absmax; k.cinb = f.slot(sb + 5);
+        k.Chi = Uh; k.Clo = Ul; k.sCp = (long)hid * HW; k.cslot = f.slot(sb + 6);
+        HIP_TRY(b.fc1 == CONV_WL ? launch_conv_wl(k, s) : launch_conv_ws(k, s));
+    } else {
+        HIP_TRY(launch_fold_affine_f16(w1.buf.p, w1.pitch, w1.wabs, f.sc1, f.sh1, b1w.buf.p, F1h, F1l, n->bf1.p, B, hid, C, cp, f1s,
+                                       f.slot(sb + 9), s));
+        MARK(ST_NORM1);
+        PkOpts f1;
+        f1.w = &w1; f1.fhi = F1h; f1.flo = F1l; f1.fslot = f.slot(sb + 9); f1.f_stride = f1s;
+        f1.bias = n->bf1.p; f1.sbias = hid;
+        f1.bhi = f.PAh; f1.blo = f.PAl; f1.cin = C; f1.in_slot = f.slot(sb + 4);
+        f1.cout = hid; f1.act = act;
+        f1.ohi = Uh; f1.olo = Ul; f1.cb = b1w.absmax; f1.cslot = f.slot(sb + 6); f1.cinb = f.slot(sb + 5);
+        ACE_TRY(conv_packed(f, f1));
+    }
+    MARK(ST_MLP_FC1);
+
+    // fc2 + outer skip: h' as fp32 and / or as planes with statistics for the next block (then a bound instead of the true max
+    // goes into the h slot)
+    if (b.fc2 == CONV_WS) {
+        ConvStripArgs k = strip_args(f, Uh, Ul, f.slot(sb + 6), hid, C, ACT_NONE);
+        static_frags(k, w2, b2w.buf.p);
+        k.rsc = f.ra; k.rsh = f.rb; k.srs = C;
+        if (b.res_planes) { k.Rhi = f.PBh; k.Rlo = f.PBl; k.sRp = (long)C * HW; k.rslot = f.hslot(i); }
+        else { k.R = f.res; k.sR = actB; }
+        if (b.out_f32) { k.Cf = f.hn; k.sCf = actB; }
+        if (b.out_planes) {
+            k.Chi = f.PBh; k.Clo = f.PBl; k.sCp = (long)C * HW; k.cslot = f.hslot(i + 1);
+            k.cw = w2.winf; k.cb = b2w.absmax; k.rmax = f.slot(sb + 3);
+            k.part = reinterpret_cast<float4*>(f.part_h); k.nstrips32 = b.out_nparts;
+        } else {
+            k.omax = f.hslot(i + 1);
+        }
+        HIP_TRY(launch_conv_ws(k, s));
+    } else {
+        PkOpts f2;
+        f2.w = &w2; f2.bias = b2w.buf.p;
+        f2.bhi = Uh; f2.blo = Ul; f2.cin = hid; f2.in_slot = f.slot(sb + 6);
+        f2.out = f.hn; f2.cout = C; f2.act = ACT_NONE;
+        f2.R = f.res; f2.r_bs = actB; f2.rsc = f.ra; f2.rsh = f.rb;
+        if (b.out_planes) {
+            f2.ohi = f.PBh; f2.olo = f.PBl; f2.cb = b2w.absmax; f2.cslot = f.hslot(i + 1); f2.rmax = f.slot(sb + 3);
+            f2.part = f.part_h;
+        } else {
+            f2.omax = f.hslot(i + 1);
+        }
+        ACE_TRY(conv_packed(f, f2));
+    }
+    return ACE_OK;
+}
+
+// norm1 of the other two bodies, on T: materialised in place (conditional norm / "layer_norm"; *planes: the conditional norm wrote
+// the MLP's operand planes, and only them) or left as an affine (*a1, *b1) for the consumer (instance norm)
+static int enqueue_norm1(Fwd& f, int i, const BlockRoute& b, const float** a1, const float** b1, bool* planes) {
+    const ace_sfno* n = f.n;
+    const int C = n->C, sb = 16 + 12 * i, kind = n->cfg.normalization_layer;
+    const std::string p = "blocks." + std::to_string(i) + ".";
+    *a1 = *b1 = nullptr;
+    *planes = false;
+    if (kind == 0) return ACE_OK;
+    if (kind == 2) {
+        ACE_TRY(cond_norm(f, n->T.p, n->T.p, p + "norm1.", C, f.slot(sb + 5), b.n1_to_planes ? f.PAh : nullptr,
+                          b.n1_to_planes ? f.Pl() : nullptr, false, planes));
+    } else if (kind == 3) {
+        HIP_TRY(launch_spatial_layer_norm(n->T.p, f.W(p + "norm1.weight"), f.W(p + "norm1.bias"), 1e-6f, (long)f.B * C, f.HW, n->T.p, f.slot(sb + 5), f.s));
+    } else {
+        HIP_TRY(launch_instnorm_stats(n->T.p, f.W(p + "norm1.weight"), f.W(p + "norm1.bias"), 1e-6f, f.B, C, f.HW, f.sc1, f.sh1, f.s,
+                                      f.slot(sb + 5)));
+        *a1 = f.sc1; *b1 = f.sh1;
+    }
+    MARK(ST_NORM1);
+    return ACE_OK;
+}
+
+// Body of a block on the packed-operand engine with materialised norms (conditional / layer norm, or none): one pack pass per conv
+// input unless the norm wrote the planes itself; fc1's epilogue writes U = act(.) straight in P format (bound-scaled), which fc2
+// consumes by DMA - the hidden activation never exists in fp32
+static int enqueue_packed_body(Fwd& f, int i, const BlockRoute& b) {
+    const ace_sfno* n = f.n;
+    const int C = n->C, hid = n->hid, act = n->cfg.activation_function, sb = 16 + 12 * i;
+    const long HW = f.HW, actB = f.actB();
+    const std::string p = "blocks." + std::to_string(i) + ".";
+    const Weight& ws = f.wt(p + "inner_skip.weight");
+    const unsigned* skip_max = f.slot(b.skip_slot);
+    _Float16 *Ph = f.PAh, *Pl = f.Pl();
+    if (!f.n0_planes) ACE_TRY(pack_act(f, f.res, actB, C, f.ra, f.rb, skip_max, Ph, Pl));
+    if (b.skip == CONV_WS) {
+        ConvStripArgs k = strip_args(f, Ph, Pl, skip_max, C, C, act);
+        static_frags(k, ws, f.W(p + "inner_skip.bias"));
+        k.R = n->Y.p; k.sR = actB;
+        k.Cf = n->T.p; k.sCf = actB; k.omax = f.slot(sb + 4);
+        HIP_TRY(launch_conv_ws(k, f.s));
+    } else {
+        PkOpts o;
+        o.w = &ws; o.bias = f.W(p + "inner_skip.bias");
+        o.bhi = Ph; o.blo = Pl; o.cin = C; o.in_slot = skip_max;
+        o.out = n->T.p; o.cout = C; o.omax = f.slot(sb + 4);
+        o.R = n->Y.p; o.r_bs = actB; o.act = act;
+        ACE_TRY(conv_packed(f, o));
+    }
+    MARK(ST_INNER_SKIP);
+    const float *a1, *b1;
+    bool n1_planes;
+    ACE_TRY(enqueue_norm1(f, i, b, &a1, &b1, &n1_planes));
+    if (b.fc1 == CONV_NONE) {
+        HIP_TRY(launch_rowaffine_add(n->T.p, a1, b1, f.res, f.ra, f.rb, f.hn, (long)f.B * C, HW, f.s));
+        return ACE_OK;
+    }
+    const Weight &w1 = f.wt(p + "mlp.fwd.0.weight"), &b1w = f.wt(p + "mlp.fwd.0.bias");
+    const unsigned* tmax = f.slot(b.t_slot);
+    _Float16 *Uh = f.Uh(), *Ul = f.Ul();
+    if (!n1_planes) ACE_TRY(pack_act(f, n->T.p, actB, C, a1, b1, tmax, Ph, Pl));
+    if (b.fc1 == CONV_WL) {   // weights in LDS, unsynchronised waves
+        ConvStripArgs k = strip_args(f, Ph, Pl, tmax, C, hid, ACT_GELU);
+        static_frags(k, w1, b1w.buf.p);
+        k.cw = w1.winf; k.cb = b1w.absmax;
+        k.Chi = Uh; k.Clo = Ul; k.sCp = (long)hid * HW; k.cslot = f.slot(sb + 6);
+        HIP_TRY(launch_conv_wl(k, f.s));
+    } else {
+        PkOpts o;
+        o.w = &w1; o.bias = b1w.buf.p;
+        o.bhi = Ph; o.blo = Pl; o.cin = C; o.in_slot = tmax;
+        o.cout = hid; o.act = act;
+        o.ohi = Uh; o.olo = Ul; o.cb = b1w.absmax; o.cslot = f.slot(sb + 6);
+        ACE_TRY(conv_packed(f, o));
+    }
+    MARK(ST_MLP_FC1);
+    PkOpts o;
+    o.w = &f.wt(p + "mlp.fwd.2.weight"); o.bias = f.W(p + "mlp.fwd.2.bias");
+    o.bhi = Uh; o.blo = Ul; o.cin = hid; o.in_slot = f.slot(sb + 6);
+    o.out = f.hn; o.cout = C; o.omax = f.hslot(i + 1);
+    o.R = f.res; o.r_bs = actB; o.rsc = f.ra; o.rsh = f.rb;
+    ACE_TRY(conv_packed(f, o));
+    return ACE_OK;
+}
+
+// Body of a block on the tile engines (fp32 mode, mixed-grid blocks, shapes the packed engine does not take): the convolutions
+// read fp32 and apply the instance-norm affine on load (f16x3) or from a per-sample folded weight (fp32)
+static int enqueue_plain_body(Fwd& f, int i, const BlockRoute& b) {
+    const ace_sfno* n = f.n;
+    const int C = n->C, hid = n->hid, act = n->cfg.activation_function, sb = 16 + 12 * i;
+    const long actB = f.actB();
+    const std::string p = "blocks." + std::to_string(i) + ".";
+    ConvW wskip = conv_weight(n, p + "inner_skip.weight", p + "inner_skip.bias");
+    if (b.fold_skip) ACE_TRY(fold(f, wskip, C, C, f.ra, f.rb, n->Wf0.p, n->bf0.p, &wskip));
+    ACE_TRY(conv(f, wskip, f.res, actB, C, nullptr, 0, -1, n->T.p, C, n->Y.p, actB, nullptr, nullptr, act,
+                 b.fold_skip ? nullptr : f.ra, b.fold_skip ? nullptr : f.rb, f.slot(b.skip_slot), nullptr, f.slot(sb + 4)));
+    MARK(ST_INNER_SKIP);
+    const float *a1, *b1;
+    bool n1_planes;
+    ACE_TRY(enqueue_norm1(f, i, b, &a1, &b1, &n1_planes));
+    if (b.fc1 == CONV_NONE) {
+        HIP_TRY(launch_rowaffine_add(n->T.p, a1, b1, f.res, f.ra, f.rb, f.hn, (long)f.B * C, f.HW, f.s));
+        return ACE_OK;
+    }
+    ConvW wfc1 = conv_weight(n, p + "mlp.fwd.0.weight", p + "mlp.fwd.0.bias");
+    if (b.fold_fc1) ACE_TRY(fold(f, wfc1, hid, C, a1, b1, n->Wf1.p, n->bf1.p, &wfc1));
+    ACE_TRY(conv(f, wfc1, n->T.p, actB, C, nullptr, 0, -1, n->U.p, hid, nullptr, 0, nullptr, nullptr, act,
+                 b.fold_fc1 ? nullptr : a1, b.fold_fc1 ? nullptr : b1, f.slot(b.t_slot), nullptr, f.slot(sb + 6)));
+    MARK(ST_MLP_FC1);
+    ACE_TRY(conv(f, conv_weight(n, p + "mlp.fwd.2.weight", p + "mlp.fwd.2.bias"), n->U.p, (long)hid * f.HW, hid, nullptr, 0, -1, f.hn,
+                 C, f.res, actB, f.ra, f.rb, ACT_NONE, nullptr, nullptr, f.slot(sb + 6), nullptr, f.hslot(i + 1)));
+    return ACE_OK;
+}
+
+// ---- decoder on cat(x, input) (sfnonet.py:741-747); the concat is two row sources of one GEMM
+static int enqueue_decoder(Fwd& f, float* out) {
+    const ace_sfno* n = f.n;
+    const ace_sfno_config& c = n->cfg;
+    const int C = n->C, Cin = c.in_chans;
+    const long actB = f.actB();
+    float* ping[2] = {n->Y.p, n->T.p};
+    const float* cur = f.h;
+    const unsigned* h_slot = c.use_mlp ? f.hslot(c.num_layers) : nullptr;   // the last block's range slot
     for (int j = 0; j < c.encoder_layers; ++j) {
         const std::string p = "decoder." + std::to_string(2 * j);
         const bool cat = (j == 0 && c.big_skip);
-        ACE_TRY(conv(n, conv_weight(n, p + ".weight", p + ".bias"), cur, cur_bs, cat ? C + Cin : curC,
-                     cat ? skip_in : nullptr, (long)Cin * HW, C, ping[j & 1], C, nullptr, 0, nullptr, nullptr, act, B, s, nullptr,
-                     nullptr, j == 0 ? (c.use_mlp ? hslot(c.num_layers) : nullptr) : slot(3 + j), skip_in_slot, slot(4 + j)));
-        cur = ping[j & 1]; cur_bs = actB; curC = C;
+        ACE_TRY(conv(f, conv_weight(n, p + ".weight", p + ".bias"), cur, actB, cat ? C + Cin : C, cat ? f.skip_in : nullptr,
+                     (long)Cin * f.HW, C, ping[j & 1], C, nullptr, 0, nullptr, nullptr, c.activation_function, nullptr, nullptr,
+                     j == 0 ? h_slot : f.slot(3 + j), f.skip_in_slot, f.slot(4 + j)));
+        cur = ping[j & 1];
     }
-    {
-        // without hidden decoder layers the last convolution is the one that sees cat(x, input) and the last block's range slot
-        const bool first = c.encoder_layers == 0, cat = first && c.big_skip;
-        ACE_TRY(conv(n, conv_weight(n, "decoder." + std::to_string(2 * c.encoder_layers) + ".weight", ""), cur, cur_bs,
-                     cat ? C + Cin : curC, cat ? skip_in : nullptr, (long)Cin * HW, cat ? C : -1, out, c.out_chans, nullptr, 0, nullptr,
-                     nullptr, ACT_NONE, B, s, nullptr, nullptr,
-                     first ? (c.use_mlp ? hslot(c.num_layers) : nullptr) : slot(3 + c.encoder_layers), cat ? skip_in_slot : nullptr, nullptr));
-    }
+    // without hidden decoder layers the last convolution is the one that sees cat(x, input) and the last block's range slot
+    const bool first = c.encoder_layers == 0, cat = first && c.big_skip;
+    ACE_TRY(conv(f, conv_weight(n, "decoder." + std::to_string(2 * c.encoder_layers) + ".weight", ""), cur, actB, cat ? C + Cin : C,
+                 cat ? f.skip_in : nullptr, (long)Cin * f.HW, cat ? C : -1, out, c.out_chans, nullptr, 0, nullptr, nullptr, ACT_NONE,
+                 nullptr, nullptr, first ? h_slot : f.slot(3 + c.encoder_layers), cat ? f.skip_in_slot : nullptr, nullptr));
     MARK(ST_DECODER);
     return ACE_OK;
+}
+
+static int forward_impl(const ace_sfno* n, const float* in, float* out, int B, hipStream_t s, StageTimer* tm = nullptr,
+                        const float* noise = nullptr) {
+    const FwdRoute route = plan_route(n, B, noise != nullptr);
+    if (route.err) return fail(ACE_ERR_STATE, route.err);
+    const size_t bc = (size_t)n->Bmax * n->C;
+    Fwd f{};
+    f.n = n; f.B = B; f.s = s; f.tm = tm; f.noise = noise; f.route = &route;
+    f.HW = n->HW;
+    f.h = n->h0.p; f.hn = n->h1.p;
+    f.sc0 = n->stats.p; f.sh0 = f.sc0 + bc; f.sc1 = f.sh0 + bc; f.sh1 = f.sc1 + bc;
+    f.PAh = reinterpret_cast<_Float16*>(n->P.p);  f.PAl = f.PAh ? f.PAh + bc * n->HW : nullptr;
+    f.PBh = reinterpret_cast<_Float16*>(n->P2.p); f.PBl = f.PBh ? f.PBh + bc * n->HW : nullptr;
+    f.part_h = n->part.p;
+    f.part_t = n->part.p ? n->part.p + (size_t)n->Bmax * n->nstrips * n->C * 4 : nullptr;
+
+    ACE_TRY(enqueue_encoder(f, in));
+    ACE_TRY(enqueue_big_skip_source(f, in));
+    for (int i = 0; i < n->cfg.num_layers; ++i) {   // sfnonet.py:217-252
+        const BlockRoute& b = route.blk[i];
+        ACE_TRY(enqueue_norm0(f, i, b));
+        ACE_TRY(enqueue_forward_transform(f, i, b));
+        ACE_TRY(enqueue_contraction(f, i, b));
+        ACE_TRY(enqueue_inverse_transform(f, i, b));
+        if (b.body == BODY_FUSED) ACE_TRY(enqueue_fused_body(f, i, b));
+        else if (b.body == BODY_PACKED) ACE_TRY(enqueue_packed_body(f, i, b));
+        else ACE_TRY(enqueue_plain_body(f, i, b));
+        MARK(ST_MLP_FC2);
+        std::swap(f.h, f.hn);
+        if (n->taps_on)
+            HIP_TRY(hipMemcpyAsync(n->taps[i + 1].p, f.h, sizeof(float) * B * f.actB(), hipMemcpyDeviceToDevice, s));
+    }
+    return enqueue_decoder(f, out);
 }
 
 static int check_ready(ace_sfno* n, const float* in, float* out, int batch) {
