@@ -181,6 +181,10 @@ SIGNATURES = {
                                 c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_void_p]),
     # coeffs, rows, spec, nrows, nnames, planes, lmax, mmax, stream
     "ace_diag_spectrum": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_int, c_int, c_void_p]),
+    "ace_diag_paired_partial_doubles": (c_long, [c_int, c_int, c_int, c_int, c_int]),
+    # gen, gen_strides, target, target_strides, rows, wrows, weights, nw, partial, tsum, zonal, series, nrows, n_time, t0, t_begin,
+    # do_maps, zt0, factor, nslots, nplanes, batch, steps, nlat, nlon, stream
+    "ace_diag_paired_window": (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 4 + [c_int] * 13 + [c_void_p]),
 }
 
 _lib = None

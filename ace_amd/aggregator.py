@@ -6,7 +6,8 @@ xarray, netCDF, wandb and torch_harmonics are not on this stack: logs hold tenso
 figures, ``get_dataset`` returns plain dicts of tensors, ``flush_diagnostics`` writes ``torch.save`` archives with the reference's
 stems (``<sub-aggregator>_diagnostics.pt`` for its ``.nc``, as ``TensorFileWriter`` writes ``restart.pt``), and the spectrum's SHT
 is the project's own forward transform.  Not built: the ``annual`` and ``enso_index`` sub-aggregators, step diagnostics, reference
-time means, HEALPix grids and the NaN flood fill before the spectrum (a masked name is listed in ``omitted`` instead).
+time means, HEALPix grids and the NaN flood fill before the spectrum (a masked name is listed in ``omitted`` instead).  The
+evaluator that compares a rollout with a target record (``InferenceEvaluatorAggregator``) is ace_amd/evaluator.py.
 
 Two paths compute the same thing.  The torch path (``fused = False``, any device) is the reference's formulas in fp32 torch ops.
 On the GPU (fp32 (B, T, H, W) fields with contiguous rows) a window is reduced by the HIP kernels of csrc/diag.hip, reading every

@@ -1,0 +1,686 @@
+"""The inference evaluator aggregator on a lat-lon grid (fme/ace/aggregator/inference/main.py:186-361, 526-732): a rollout
+compared against a target record, for ``ace_amd.inference.run_evaluator``.  Built sub-aggregators, under the reference's labels:
+
+  * ``mean`` / ``mean_norm`` (reduced.py:221-348): per time index ``weighted_rmse``, ``weighted_bias``, ``weighted_mean_gen``,
+    ``weighted_mean_target``, ``weighted_std_gen`` and, denormalised only (reduced.py:248-255), ``weighted_grad_mag_percent_diff``;
+  * ``time_mean`` / ``time_mean_norm`` (time_mean.py:246-444): the time-mean maps of both sides, their bias map, RMSE and bias, and
+    ``time_mean_norm/rmse/channel_mean``, which ``get_summary`` returns as the inference ``loss`` (main.py:668-676);
+  * ``power_spectrum`` (spectrum.py:112-276): the mean spectra of prediction and target and their bias scores;
+  * ``zonal_mean`` (zonal_mean.py:50-355): time-latitude maps of both sides and of their difference, coarsened in time.
+
+Not built, skipped at build time with one warning and listed in ``skipped`` as the reference's non-strict path does
+(main.py:143-153): ``step_means``, ``ensembles``, ``annual``, ``enso_index``, ``enso_coefficient``, ``ipo_index``.  ``video``,
+``histogram``, ``seasonal``, ``trend``, ``near_zero_fraction``, the reference-data paths, a ``variables`` filter, HEALPix grids and
+``strict=True`` on a skipped metric raise ``NotImplementedError``.  As in ace_amd/aggregator.py, tensors and floats stand where the
+reference logs images and figures, and a name whose mask has zeros is left out of the spectrum and listed in ``omitted``.
+
+Paired metrics cover the names present in both mappings, ``weighted_mean_gen`` / ``weighted_std_gen`` every generated name; a target
+name without a prediction is refused (the reference indexes ``gen[name]`` for every target name, reduced.py:190-196).
+
+Two paths compute the same thing.  The torch path (``fused = False``, any device) is the reference's formulas in torch ops on the
+window and on ``normalize`` of the window.  The fused path (CUDA fp32 windows) makes one ``ace_diag_paired_window`` call per window
+(csrc/diag.hip: every quantity above from one pass over each plane, a band's halo rows re-read through the cache; fp64, fixed
+order, no atomics, no host synchronisation) and per
+spectrum chunk one SHT and one ``ace_diag_spectrum`` for each side.  It never normalises a field: ``normalize`` is (x - mu) / sigma
+per name (fme/core/normalizer.py:213-227), every per-sample quantity is linear in it (rmse / sigma, bias / sigma, (mean - mu) /
+sigma, std / sigma, and the time-mean RMSE / sigma), so the ``_norm`` outputs are formed from the denormalised fp64 accumulators at
+``get_*`` time.  Names without statistics are dropped from the ``_norm`` outputs, as ``normalize`` drops them
+(normalizer.py:159).  A normaliser that fills NaNs (not linear) or exposes no statistics takes the torch path.
+
+The one deliberate difference from the reference: the zonal mean adds each step at its coarsened slot ``(t - t_first) // factor``
+scaled by 1 / factor, which equals the reference's buffer-carry form (zonal_mean.py:192-266) whenever every window has at least
+``factor`` steps; a shorter window raises ``ValueError`` where the reference silently drops it (zonal_mean.py:181-190).  Zonal
+accumulator memory: names x 2 x slots x H x 8 bytes (40 names, 4096 slots, 180 latitudes: 472 MB; the default
+``zonal_mean_max_size`` only coarsens past 4096 steps)."""
+import dataclasses
+import logging
+import math
+import os
+from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence
+
+import torch
+
+from .aggregator import InferenceAggregator, TensorMapping, _check, _is_healpix, _upload
+
+SERIES = ("weighted_mean_gen", "weighted_std_gen", "weighted_mean_target", "weighted_bias", "weighted_rmse",
+          "weighted_grad_mag_percent_diff")                               # the rows of the fused series accumulator
+NORM_SERIES = SERIES[:5]                                                  # reduced.py:248-255: the percent diff is denorm-only
+_SHIFTED = ("weighted_mean_gen", "weighted_mean_target")                  # (v - mu) / sigma; the others v / sigma
+
+
+@dataclasses.dataclass
+class MetricConfig:
+    """The fields every metric configuration of the reference shares (e.g. reduced.py:506-512)."""
+    enabled: bool = True
+    strict: bool = False
+    variables: Optional[List[str]] = None
+    name: Optional[str] = None
+
+
+@dataclasses.dataclass
+class ZonalMeanMetricConfig(MetricConfig):
+    zonal_mean_max_size: int = 4096                                       # zonal_mean.py:357-363
+
+
+@dataclasses.dataclass
+class PowerSpectrumMetricConfig(MetricConfig):
+    report_directional_bias: bool = True                                  # spectrum.py:317-322
+
+
+def _off() -> MetricConfig:
+    return MetricConfig(enabled=False, strict=True)
+
+
+@dataclasses.dataclass
+class InferenceSummary:
+    logs: Dict[str, Any]
+    loss: Optional[float]
+
+
+@dataclasses.dataclass
+class InferenceEvaluatorAggregatorConfig:
+    """main.py:186-361 (same field names and defaults; each metric carries ``enabled`` and ``strict``)."""
+    mean_denorm: MetricConfig = dataclasses.field(default_factory=MetricConfig)
+    mean_norm: MetricConfig = dataclasses.field(default_factory=MetricConfig)
+    step_means: List[MetricConfig] = dataclasses.field(default_factory=lambda: [MetricConfig(), MetricConfig()])
+    ensembles: List[MetricConfig] = dataclasses.field(default_factory=lambda: [MetricConfig()])
+    power_spectrum: PowerSpectrumMetricConfig = dataclasses.field(default_factory=PowerSpectrumMetricConfig)
+    zonal_mean: ZonalMeanMetricConfig = dataclasses.field(default_factory=ZonalMeanMetricConfig)
+    time_mean_denorm: MetricConfig = dataclasses.field(default_factory=MetricConfig)
+    time_mean_norm: MetricConfig = dataclasses.field(default_factory=MetricConfig)
+    video: MetricConfig = dataclasses.field(default_factory=_off)
+    histogram: MetricConfig = dataclasses.field(default_factory=_off)
+    seasonal: MetricConfig = dataclasses.field(default_factory=_off)
+    annual: MetricConfig = dataclasses.field(default_factory=MetricConfig)
+    enso_index: MetricConfig = dataclasses.field(default_factory=MetricConfig)
+    enso_coefficient: MetricConfig = dataclasses.field(default_factory=MetricConfig)
+    ipo_index: MetricConfig = dataclasses.field(default_factory=MetricConfig)
+    trend: MetricConfig = dataclasses.field(default_factory=lambda: MetricConfig(enabled=False))
+    near_zero_fraction: MetricConfig = dataclasses.field(default_factory=_off)
+    monthly_reference_data: Optional[str] = None
+    time_mean_reference_data: Optional[str] = None
+    step_diagnostics: Optional[Any] = None
+
+    BUILT = {"mean_denorm": "mean", "mean_norm": "mean_norm", "time_mean_denorm": "time_mean", "time_mean_norm": "time_mean_norm",
+             "power_spectrum": "power_spectrum", "zonal_mean": "zonal_mean"}
+    SKIPPED = ("step_means", "ensembles", "annual", "enso_index", "enso_coefficient", "ipo_index")
+    REFUSED = ("video", "histogram", "seasonal", "trend", "near_zero_fraction")
+
+    def build(self, dataset_info, n_ic_steps: int, n_forward_steps: int, normalize, output_dir: Optional[str] = None,
+              channel_mean_names: Optional[Sequence[str]] = None, save_diagnostics: bool = False,
+              sht_factory: Optional[Callable[[int, int], Callable]] = None) -> "InferenceEvaluatorAggregator":
+        """``normalize``: a ``StandardNormalizer``, its bound ``normalize``, or anything exposing per-name ``means`` and ``stds``
+        (the fused path reads the statistics, the torch path calls it); a bare callable serves the torch path only."""
+        if self.monthly_reference_data is not None or self.time_mean_reference_data is not None:
+            raise NotImplementedError("monthly_reference_data / time_mean_reference_data are netCDF files and there is no netCDF "
+                                      "reader here; compare the maps of get_dataset() offline")
+        if self.step_diagnostics not in (None, {}):
+            raise NotImplementedError("step_diagnostics: only the default configuration is supported (no step-diagnostics "
+                                      "aggregator is built)")
+        for field in self.REFUSED:
+            if getattr(self, field).enabled:
+                raise NotImplementedError(f"the {field} metric is not built")
+        skipped = []
+        for field in self.SKIPPED:
+            v = getattr(self, field)
+            for m in (v if isinstance(v, list) else [v]):
+                if not m.enabled:
+                    continue
+                if m.strict:
+                    raise NotImplementedError(f"the {field} metric is not built (strict=True)")
+                if field not in skipped:
+                    skipped.append(field)
+        if skipped:
+            logging.warning("metrics not supported for this configuration, omitting: " + ", ".join(skipped))
+        labels = {}
+        for field, default in self.BUILT.items():
+            m = getattr(self, field)
+            if m.variables is not None:
+                raise NotImplementedError(f"{field}.variables: a per-metric variable filter is not built")
+            if m.enabled:
+                labels[default] = m.name or default
+        if _is_healpix(dataset_info):
+            raise NotImplementedError("the inference evaluator aggregator is built for lat-lon grids only, not HEALPix")
+        if getattr(dataset_info, "area_weights", None) is None:
+            raise ValueError("the inference evaluator aggregator needs the dataset's area weights: build the DatasetInfo with lat "
+                             "(and lon) or area_weights")
+        return InferenceEvaluatorAggregator(
+            dataset_info, int(n_ic_steps), int(n_forward_steps), normalize, labels=labels, skipped=skipped,
+            zonal_mean_max_size=getattr(self.zonal_mean, "zonal_mean_max_size", 4096), channel_mean_names=channel_mean_names,
+            report_directional_bias=getattr(self.power_spectrum, "report_directional_bias", True), output_dir=output_dir,
+            save_diagnostics=save_diagnostics, sht_factory=sht_factory)
+
+
+# ---- the reference's formulas in torch ops (the torch path) ---------------------------------------------------------------------
+def _wmean(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """metrics.py:63-90 over the last two dimensions"""
+    w = w.expand(x.shape)
+    return (x.where(w != 0.0, 0.0) * w).sum(dim=(-2, -1)) / w.sum(dim=(-2, -1))
+
+
+def _wstd(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """metrics.py:118-143"""
+    return _wmean((x - _wmean(x, w)[..., None, None]) ** 2, w).sqrt()
+
+
+def _grad_mag_mean(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """metrics.py:200-210 with weighted_nanmean (metrics.py:93-115)"""
+    gy, gx = torch.gradient(x, dim=(-2, -1))
+    g = torch.sqrt(gy ** 2 + gx ** 2)
+    denom = torch.where(torch.isnan(g), torch.zeros((), dtype=w.dtype, device=w.device), w.expand(g.shape)).sum(dim=(-2, -1))
+    return (g * w).nansum(dim=(-2, -1)) / denom
+
+
+def zonal_coarsening(n_timesteps: int, max_size: int):
+    """zonal_mean.py:89-127: (coarsening factor, number of slots)"""
+    max_size = min(int(max_size), 2 ** 15, n_timesteps)
+    if n_timesteps > max_size:
+        factor = int(math.ceil(n_timesteps / max_size))
+        return factor, n_timesteps // factor
+    return 1, n_timesteps
+
+
+def spectrum_bias_scores(gen: torch.Tensor, target: torch.Tensor, directional: bool = True) -> Dict[str, float]:
+    """spectrum.py:218-276 for one name"""
+    ratio = gen / target - 1
+    pos = float(ratio[ratio > 0].sum() / target.shape[0])
+    neg = float(ratio[ratio < 0].sum() / target.shape[0])
+    out = {"smallest_scale_norm_bias": float(ratio[-1])}
+    if directional:
+        out["positive_norm_bias"], out["negative_norm_bias"] = pos, neg
+    out["mean_abs_norm_bias"] = abs(pos) + abs(neg)
+    return out
+
+
+class InferenceEvaluatorAggregator(InferenceAggregator):
+    """main.py:526-732 for the sub-aggregators of the module docstring.  Weights, masks, routing and the SHT are the parent's."""
+
+    def __init__(self, dataset_info, n_ic_steps: int, n_forward_steps: int, normalize, labels: Optional[Mapping[str, str]] = None,
+                 skipped: Sequence[str] = (), zonal_mean_max_size: int = 4096, channel_mean_names: Optional[Sequence[str]] = None,
+                 report_directional_bias: bool = True, output_dir: Optional[str] = None, save_diagnostics: bool = False,
+                 sht_factory=None, spectrum_chunk_bytes: int = 256 << 20):
+        super().__init__(dataset_info, n_ic_steps + n_forward_steps, True, output_dir, save_diagnostics, sht_factory,
+                         spectrum_chunk_bytes)
+        self.n_ic_steps = int(n_ic_steps)
+        self.skipped = list(skipped)
+        default = InferenceEvaluatorAggregatorConfig.BUILT.values()
+        self._labels = dict(labels) if labels is not None else {k: k for k in default}
+        self._log_series = "mean" in self._labels or "mean_norm" in self._labels
+        self._channel_mean_names = None if channel_mean_names is None else list(channel_mean_names)
+        self._directional = bool(report_directional_bias)
+        owner = getattr(normalize, "__self__", normalize)
+        self._normalize_fn = normalize if callable(normalize) else getattr(normalize, "normalize", None)
+        self._stats = None
+        if hasattr(owner, "means") and hasattr(owner, "stds") and not getattr(owner, "fill_nans_on_normalize", False):
+            self._stats = {n: (float(owner.means[n]), float(owner.stds[n])) for n in owner.means if n in owner.stds}
+        self._factor, self._n_slots = zonal_coarsening(self._n_time, zonal_mean_max_size)
+        self._zon_first: Optional[int] = None
+        self._zon_steps = 0
+        self._pair_names: List[str] = []
+        self._present: Dict[str, Dict[str, List[int]]] = {"gen": {}, "target": {}}     # name -> records per time index
+        self._spec_side_counts: List[Dict[str, int]] = [{}, {}]
+        self._need_norm = "mean_norm" in self._labels or "time_mean_norm" in self._labels
+        # torch path state
+        self._t_series: Dict[str, Dict[str, Dict[str, torch.Tensor]]] = {"denorm": {}, "norm": {}}
+        self._t_tsum: Dict[str, List[Dict[str, torch.Tensor]]] = {"denorm": [{}, {}], "norm": [{}, {}]}
+        self._t_spec2: List[Dict[str, torch.Tensor]] = [{}, {}]
+        self._t_zon: List[Dict[str, torch.Tensor]] = [{}, {}]
+        # fused path state: _series (6, rows, n_time), _tsum (2, rows, H W), _spec (2, rows, lmax), _zon (2, rows, slots, H)
+        self._zon = None
+
+    # ---- routing ------------------------------------------------------------------------------------------------------
+    def route(self, prediction: TensorMapping, target: Optional[TensorMapping] = None) -> str:
+        """"fused" when recording this pair runs the HIP kernels, "torch" when it runs the torch ops."""
+        if self._need_norm and self._stats is None:
+            return "torch"
+        return super().route({**{f"p:{k}": v for k, v in prediction.items()}, **{f"t:{k}": v for k, v in (target or {}).items()}})
+
+    def launches(self) -> int:
+        """Native launches made so far: one ``ace_diag_paired_window`` per window, and per spectrum chunk of either side one
+        forward SHT and one ``ace_diag_spectrum``."""
+        return self._launches
+
+    def _pick_pair(self, prediction, target) -> str:
+        path = self.route(prediction, target)
+        if self._path is None:
+            self._path = path
+        elif path != self._path:
+            raise ValueError(f"this aggregator reduces on the {self._path} path, but a window only the {path} path takes came in "
+                             "(device, dtype or shape changed between windows)")
+        return path
+
+    # ---- recording ----------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def record_initial_condition(self, initial_condition: TensorMapping, target: Optional[TensorMapping] = None):
+        """main.py:629-666: the initial condition (name -> (B, H, W) or (B, n_ic_steps, H, W)) feeds the series only; without
+        ``target`` it is its own target (main.py:638-646).  Returns no per-step logs (reading them back would synchronise)."""
+        if self._n_seen != 0:
+            raise RuntimeError("record_initial_condition may only be called once, before recording any batches")
+        fix = lambda d: {k: (v if v.dim() == 4 else v.unsqueeze(1)) for k, v in d.items()}      # noqa: E731
+        gen = fix(initial_condition)
+        if not gen:
+            raise ValueError("data is empty")
+        tgt = gen if target is None else fix(target)
+        n = next(iter(gen.values())).shape[1]
+        if n != self.n_ic_steps:
+            raise ValueError(f"Expected {self.n_ic_steps} initial condition steps, but got {n}")
+        if self._log_series:
+            self._record_pair(gen, tgt, 0, with_maps=False)
+        self._n_seen = n
+        return []
+
+    @torch.no_grad()
+    def record_batch(self, prediction: TensorMapping, target: TensorMapping):
+        """main.py:579-627: a paired window, each name -> (B, T, H, W), at time index ``i_time_start`` = the steps seen so far.
+        Returns no per-step logs and does not synchronise."""
+        if len(prediction) == 0:
+            raise ValueError("No prediction values in data")
+        if len(target) == 0:
+            raise ValueError("No target values in data")
+        n = next(iter(prediction.values())).shape[1]
+        self._record_pair(dict(prediction), dict(target), self._n_seen, with_maps=True)
+        self._n_seen += n
+        return []
+
+    def _record_pair(self, gen: Dict[str, torch.Tensor], tgt: Dict[str, torch.Tensor], i_time_start: int, with_maps: bool):
+        first = next(iter(gen.values()))
+        B, T = first.shape[:2]
+        if i_time_start + T > self._n_time:
+            raise ValueError(f"steps {i_time_start}..{i_time_start + T - 1} are past the aggregator's n_timesteps {self._n_time}")
+        if tuple(first.shape[-2:]) != self._shape:
+            raise ValueError(f"fields of shape {tuple(first.shape[-2:])} on an aggregator of {self._shape}")
+        for n, y in tgt.items():
+            if n not in gen:
+                raise ValueError(f"target name '{n}' has no prediction")
+            if y.shape != gen[n].shape:
+                raise RuntimeError(f"Tensors in target and gen must have the same shape, but got {tuple(y.shape)} and "
+                                   f"{tuple(gen[n].shape)} for the tensor '{n}'.")
+        zonal = with_maps and "zonal_mean" in self._labels
+        if zonal and T < self._factor:
+            raise ValueError(f"a window of {T} steps is shorter than the zonal mean's time coarsening factor {self._factor}")
+        path = self._pick_pair(gen, tgt)
+        ignore_initial = i_time_start == 0
+        if zonal and self._zon_first is None:
+            self._zon_first = i_time_start
+        if path == "fused":
+            self._record_fused_pair(gen, tgt, i_time_start, with_maps, ignore_initial)
+        else:
+            self._record_torch_pair(gen, tgt, i_time_start, with_maps, ignore_initial)
+        for n in gen:
+            if n not in self._series_names:
+                self._series_names.append(n)
+        if self._log_series:
+            for side, d in (("gen", gen), ("target", tgt)):
+                for n in d:
+                    seen = self._present[side].setdefault(n, [0] * self._n_time)
+                    for i in range(i_time_start, i_time_start + T):
+                        seen[i] += 1
+            for i in range(i_time_start, i_time_start + T):
+                self._n_batches[i] += 1
+        if with_maps:
+            if self._tm_samples is None:                                              # time_mean.py:127-146
+                self._tm_samples = B
+            self._tm_steps = T - 1 if ignore_initial else self._tm_steps + T
+            for n in gen:
+                if n not in self._tm_names:
+                    self._tm_names.append(n)
+            for n in tgt:                   # the maps' pairs: an initial condition that is its own target feeds the series only
+                if n not in self._pair_names:
+                    self._pair_names.append(n)
+            if zonal:
+                self._zon_steps += T
+            for side, d in enumerate((gen, tgt)):
+                for n in d:
+                    if not self._omitted(n):
+                        self._spec_side_counts[side][n] = self._spec_side_counts[side].get(n, 0) + B * T
+
+    # ---- the torch path -------------------------------------------------------------------------------------------------------
+    def _record_torch_pair(self, gen, tgt, i_time_start, with_maps, ignore_initial):
+        T = next(iter(gen.values())).shape[1]
+        sl = slice(i_time_start, i_time_start + T)
+        kinds = {"denorm": (gen, tgt)}
+        if self._need_norm:
+            kinds["norm"] = (self._normalize_fn(gen), self._normalize_fn(tgt))            # main.py:594-598
+        for kind, (g, t) in kinds.items():
+            if ("mean" if kind == "denorm" else "mean_norm") in self._labels:
+                vals: Dict[str, Dict[str, torch.Tensor]] = {m: {} for m in (SERIES if kind == "denorm" else NORM_SERIES)}
+                for n, x in g.items():
+                    w = self.weights_for(n, x.device).to(x.dtype)
+                    vals["weighted_mean_gen"][n] = _wmean(x, w)
+                    vals["weighted_std_gen"][n] = _wstd(x, w)
+                for n, y in t.items():
+                    x, w = g[n], self.weights_for(n, y.device).to(y.dtype)
+                    vals["weighted_mean_target"][n] = _wmean(y, w)
+                    vals["weighted_bias"][n] = _wmean(x - y, w)                            # metrics.py:146-168
+                    vals["weighted_rmse"][n] = _wmean(torch.square(x - y), w).sqrt()      # metrics.py:171-197
+                    if kind == "denorm":                                                  # metrics.py:213-224
+                        gt, gg = _grad_mag_mean(y, w), _grad_mag_mean(x, w)
+                        vals["weighted_grad_mag_percent_diff"][n] = 100 * (gg - gt) / gt
+                for metric, d in vals.items():
+                    tot = self._t_series[kind].setdefault(metric, {})
+                    for n, v in d.items():
+                        if n not in tot:
+                            tot[n] = torch.zeros(self._n_time, dtype=v.dtype, device=v.device)
+                        tot[n][sl] += v.mean(dim=0)                                       # reduced.py:201-211
+            if with_maps and ("time_mean" if kind == "denorm" else "time_mean_norm") in self._labels:
+                part = slice(1, None) if ignore_initial else slice(0, None)
+                for side, d in enumerate((g, t)):
+                    acc = self._t_tsum[kind][side]
+                    for n, x in d.items():
+                        s = x[:, part].sum(dim=1).sum(dim=0)
+                        acc[n] = s if n not in acc else acc[n] + s
+        if not with_maps:
+            return
+        if "power_spectrum" in self._labels:
+            for side, d in enumerate((gen, tgt)):
+                for n, x in d.items():
+                    if self._omitted(n):
+                        continue
+                    ps = torch.sum(abs(self._get_sht()(x)) ** 2, dim=-1)                  # metrics.py:388-408
+                    mean_ps = torch.mean(ps, dim=(0, 1))
+                    new, old = x.shape[0] * x.shape[1], self._spec_side_counts[side].get(n, 0)
+                    acc = self._t_spec2[side]
+                    acc[n] = mean_ps if n not in acc else (new * mean_ps + old * acc[n]) / (new + old)
+        if "zonal_mean" in self._labels:
+            z0 = i_time_start - self._zon_first
+            slots = torch.arange(z0, z0 + T, device=next(iter(gen.values())).device) // self._factor
+            keep = slots < self._n_slots
+            for side, d in enumerate((gen, tgt)):
+                for n, x in d.items():
+                    zm = x.nanmean(dim=-1)                                                # non_distributed.py:136-137
+                    acc = self._t_zon[side]
+                    if n not in acc:
+                        acc[n] = torch.zeros(x.shape[0], self._n_slots, x.shape[2], dtype=x.dtype, device=x.device)
+                    acc[n].index_add_(1, slots[keep], zm[:, keep] / self._factor)
+
+    # ---- the fused path -------------------------------------------------------------------------------------------------------
+    def _ensure_rows(self, names: Sequence[str], dev):
+        new = [n for n in names if n not in self._rows]
+        if not new and self._series is not None:
+            return
+        for n in new:
+            self._rows[n] = len(self._rows)
+        R, (H, W) = len(self._rows), self._shape
+        lmax = self._get_sht().lmax if "power_spectrum" in self._labels else 1
+
+        def grow(buf, shape):
+            fresh = torch.zeros(shape, dtype=torch.float64, device=dev)
+            if buf is not None:
+                fresh[tuple(slice(0, s) for s in buf.shape)] = buf
+            return fresh
+        self._series = grow(self._series, (len(SERIES), R, self._n_time))
+        self._tsum = grow(self._tsum, (2, R, H * W))
+        self._spec = grow(self._spec, (2, R, lmax))
+        self._zon = grow(self._zon, (2, R, self._n_slots if "zonal_mean" in self._labels else 1, H))
+        self._tables.clear()
+
+    def _record_fused_pair(self, gen, tgt, i_time_start, with_maps, ignore_initial):
+        from . import _lib
+        first = next(iter(gen.values()))
+        dev = first.device
+        B, T, H, W = first.shape
+        # the planes of a field must be contiguous for the pointer tables; anything else is made so
+        flat = lambda x: x if x.stride(-1) == 1 and x.stride(-2) == W else x.contiguous()      # noqa: E731
+        given = gen
+        gen = {n: flat(x) for n, x in given.items()}
+        tgt = {n: (gen[n] if y is given[n] else flat(y)) for n, y in tgt.items()}
+        names = list(gen)
+        n = len(names)
+        self._ensure_rows(names, dev)
+        wrows = self._weight_rows(names, dev)
+        rows = self._row_table(names, dev)
+        table = [x.data_ptr() for x in gen.values()]
+        for x in gen.values():
+            table += [x.stride(0), x.stride(1)]
+        table += [tgt[nm].data_ptr() if nm in tgt else 0 for nm in names]
+        for nm in names:
+            table += [tgt[nm].stride(0), tgt[nm].stride(1)] if nm in tgt else [0, 0]
+        table = _upload(table, torch.int64, dev)
+        lib = _lib.lib()
+        partial = torch.empty(int(lib.ace_diag_paired_partial_doubles(n, B, T, H, W)), dtype=torch.float64, device=dev)
+        base = table.data_ptr()
+        series, n_time, t0 = self._series, self._n_time, i_time_start
+        if not self._log_series:
+            series, n_time, t0 = torch.empty(len(SERIES), len(self._rows), T, dtype=torch.float64, device=dev), T, 0
+        zonal = with_maps and "zonal_mean" in self._labels
+        zt0 = i_time_start - self._zon_first if zonal else 0
+        with torch.cuda.device(dev):
+            _check(lib.ace_diag_paired_window(
+                base, base + 8 * n, base + 24 * n, base + 32 * n, rows.data_ptr(), wrows.data_ptr(), self._wplanes.data_ptr(),
+                self._wplanes.shape[0], partial.data_ptr(), self._tsum.data_ptr(), self._zon.data_ptr(), series.data_ptr(),
+                len(self._rows), n_time, t0, 1 if ignore_initial else 0, 1 if with_maps else 0, zt0,
+                self._factor if zonal else 1, self._zon.shape[2], n, B, T, H, W, _lib.current_stream()))
+            self._launches += 1
+            if not with_maps or "power_spectrum" not in self._labels:
+                return
+            sht = self._get_sht()
+            L, M = sht.lmax, sht.mmax
+            k = max(1, self.spectrum_chunk_bytes // (B * T * (H * W * 4 + L * M * 8)))
+            for side, d in enumerate((gen, tgt)):
+                spec_names = [nm for nm in d if not self._omitted(nm)]
+                acc = self._spec.data_ptr() + side * self._spec.shape[1] * L * 8
+                for c0 in range(0, len(spec_names), k):
+                    chunk = spec_names[c0:c0 + k]
+                    coeffs = sht(torch.stack([d[nm] for nm in chunk]))            # (k, B, T, L, M) complex64
+                    _check(lib.ace_diag_spectrum(coeffs.data_ptr(), self._row_table(chunk, dev).data_ptr(), acc,
+                                                 self._spec.shape[1], len(chunk), B * T, L, M, _lib.current_stream()))
+                    self._launches += 2
+
+    # ---- results --------------------------------------------------------------------------------------------------------
+    def _has_stats(self, name: str) -> bool:
+        return self._stats is not None and name in self._stats
+
+    def _series_data(self, kind: str = "denorm") -> Dict[str, Dict[str, torch.Tensor]]:
+        """reduced.py:34-55, 213-218: metric -> name -> (n_timesteps,) series (sorted names), total / per-index count."""
+        if not any(self._n_batches):
+            raise ValueError("No batches have been recorded.")
+        metrics = SERIES if kind == "denorm" else NORM_SERIES
+        out: Dict[str, Dict[str, torch.Tensor]] = {m: {} for m in sorted(metrics)}
+        if self._path != "fused":
+            for metric in out:
+                tot = self._t_series[kind].get(metric, {})
+                for n in sorted(tot):
+                    counts = torch.tensor(self._n_batches, dtype=torch.int32, device=tot[n].device)
+                    out[metric][n] = self._reduce_mean(tot[n] / counts)
+            return out
+        dev = self._series.device
+        counts = torch.tensor(self._n_batches, dtype=torch.float64, device=dev)
+        for i, metric in enumerate(SERIES):
+            if metric not in out:
+                continue
+            side = "gen" if metric in ("weighted_mean_gen", "weighted_std_gen") else "target"
+            for n in sorted(self._present[side]):
+                if kind == "norm" and not self._has_stats(n):
+                    continue
+                tot = self._series[i, self._rows[n]]
+                if kind == "norm":
+                    mu, sigma = self._stats[n]
+                    if metric in _SHIFTED:                    # a record without the name adds 0 to the normalised total as well
+                        tot = tot - mu * torch.tensor(self._present[side][n], dtype=torch.float64, device=dev)
+                    tot = tot / sigma
+                out[metric][n] = self._reduce_mean((tot / counts).float())
+        return out
+
+    def _time_means(self):
+        """time_mean.py:151-162 for both sides: name -> (gen, target or None) fp64-or-input-dtype (H, W) maps, denormalised
+        (fused) or per kind (torch)."""
+        if self._tm_steps == 0 or not self._tm_names:
+            raise ValueError("No data recorded.")
+        div = self._tm_steps * self._tm_samples
+        out: Dict[str, Dict[str, Any]] = {"denorm": {}, "norm": {}}
+        for n in sorted(self._tm_names):
+            if self._path == "fused":
+                g = self._reduce_mean((self._tsum[0, self._rows[n]] / div).reshape(self._shape))
+                t = self._reduce_mean((self._tsum[1, self._rows[n]] / div).reshape(self._shape)) if n in self._pair_names else None
+                out["denorm"][n] = (g, t)
+                if self._has_stats(n):
+                    mu, sigma = self._stats[n]
+                    out["norm"][n] = ((g - mu) / sigma, None if t is None else (t - mu) / sigma)
+            else:
+                for kind in out:
+                    gs, ts = self._t_tsum[kind]
+                    if n in gs:
+                        out[kind][n] = (self._reduce_mean(gs[n] / self._tm_steps / self._tm_samples),
+                                        self._reduce_mean(ts[n] / self._tm_steps / self._tm_samples) if n in ts else None)
+        return out
+
+    def _time_mean_logs(self, kind: str, maps) -> Dict[str, Any]:
+        """time_mean.py:339-401 without the label"""
+        logs: Dict[str, Any] = {}
+        rmse_all, all_nan = {}, set()
+        for n, (g, t) in maps.items():
+            logs[f"gen_map/{n}"] = g.float().cpu()
+            if t is None:
+                continue
+            w = self.weights_for(n, g.device).to(g.dtype)
+            rmse_all[n] = float(_wmean(torch.square(g - t), w).sqrt())
+            if bool(torch.isnan(t).all()):
+                all_nan.add(n)
+            logs[f"rmse/{n}"] = rmse_all[n]
+            if kind == "denorm":
+                logs[f"bias_map/{n}"] = (g - t).float().cpu()
+                logs[f"bias/{n}"] = float(_wmean(g - t, w))
+        if kind == "norm":
+            if self._channel_mean_names is None:
+                names = list(rmse_all)
+            else:
+                missing = [n for n in self._channel_mean_names if n not in rmse_all]
+                if missing:
+                    raise KeyError(f"channel_mean_names contains entries not present in the recorded data: {missing}. "
+                                   f"Available: {sorted(rmse_all)}.")
+                names = list(self._channel_mean_names)
+            names = [n for n in names if n not in all_nan]
+            if not names:
+                raise ValueError("All target variables are NaN; cannot compute channel mean.")
+            logs["rmse/channel_mean"] = sum(rmse_all[n] for n in names) / len(names)
+        return logs
+
+    def _spectra(self) -> Dict[str, torch.Tensor]:
+        """spectrum.py:67-77, 207-215: name -> (2, lmax) [prediction, target] mean spectra; the target row of a name without a
+        target is NaN."""
+        out = {}
+        for n in sorted(self._spec_side_counts[0]):
+            sides = []
+            for side in (0, 1):
+                cnt = self._spec_side_counts[side].get(n)
+                if cnt is None:
+                    sides.append(None)
+                elif self._path == "fused":
+                    sides.append(self._reduce_mean((self._spec[side, self._rows[n]] / cnt).float()))
+                else:
+                    sides.append(self._reduce_mean(self._t_spec2[side][n].clone()))
+            if sides[1] is None:
+                sides[1] = torch.full_like(sides[0], float("nan"))
+            out[n] = torch.stack(sides)
+        return out
+
+    def _zonal(self) -> Dict[str, torch.Tensor]:
+        """zonal_mean.py:268-306: name -> (2, n_slots, H) [generated, target]; a slot that no window completed is NaN (the
+        reference's 0 / 0)."""
+        if self._zon_first is None:
+            raise RuntimeError("No data recorded")
+        done = self._zon_steps // self._factor
+        out = {}
+        for n in sorted(self._pair_names):
+            if self._path == "fused":
+                if n not in self._rows:
+                    continue
+                z = self._zon[:, self._rows[n]].float()
+            elif n in self._t_zon[0] and n in self._t_zon[1]:
+                z = torch.stack([self._t_zon[0][n].mean(dim=0), self._t_zon[1][n].mean(dim=0)])
+            else:
+                continue
+            z = z.clone()
+            z[:, done:] = float("nan")
+            out[n] = torch.stack([self._reduce_mean(z[0]), self._reduce_mean(z[1])])
+        return out
+
+    @torch.no_grad()
+    def get_dataset(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        """get_reduced_diagnostics with the reference's variable keys (CPU tensors): ``mean`` / ``mean_norm``:
+        ``<metric>-<name>`` (T,); ``time_mean`` / ``time_mean_norm``: ``bias_map-<name>``, ``gen_map-<name>`` (H, W);
+        ``power_spectrum``: ``<name>`` (2, lmax) with the leading source axis [prediction, target]; ``zonal_mean``:
+        ``gen-<name>``, ``error-<name>`` (n_slots, H)."""
+        ds: Dict[str, Dict[str, torch.Tensor]] = {}
+        L = self._labels
+        for kind, key in (("denorm", "mean"), ("norm", "mean_norm")):
+            if key in L:
+                ds[L[key]] = {f"{m}-{n}": v.cpu() for m, d in self._series_data(kind).items() for n, v in d.items()}
+        if "time_mean" in L or "time_mean_norm" in L:
+            maps = self._time_means()
+            for kind, key in (("denorm", "time_mean"), ("norm", "time_mean_norm")):
+                if key in L:
+                    d = ds[L[key]] = {}
+                    for n, (g, t) in maps[kind].items():
+                        if t is not None:
+                            d[f"bias_map-{n}"] = (g - t).float().cpu() if self._path == "fused" else (g - t).cpu()
+                            d[f"gen_map-{n}"] = g.float().cpu() if self._path == "fused" else g.cpu()
+        if "power_spectrum" in L:
+            ds[L["power_spectrum"]] = {n: v.cpu() for n, v in self._spectra().items()}
+        if "zonal_mean" in L:
+            d = ds[L["zonal_mean"]] = {}
+            for n, z in self._zonal().items():
+                d[f"gen-{n}"] = z[0].cpu()
+                d[f"error-{n}"] = (z[0] - z[1]).cpu()
+        return ds
+
+    @torch.no_grad()
+    def get_summary(self) -> InferenceSummary:
+        """main.py:668-676: the logs of the sub-aggregators that are not time series, and ``loss`` =
+        ``time_mean_norm/rmse/channel_mean``."""
+        logs: Dict[str, Any] = {}
+        L = self._labels
+        if "time_mean" in L or "time_mean_norm" in L:
+            maps = self._time_means()
+            for kind, key in (("denorm", "time_mean"), ("norm", "time_mean_norm")):
+                if key in L:
+                    logs.update({f"{L[key]}/{k}": v for k, v in self._time_mean_logs(kind, maps[kind]).items()})
+        if "power_spectrum" in L:
+            label = L["power_spectrum"]
+            for n, s in self._spectra().items():
+                logs[f"{label}/{n}"] = s.cpu()
+                if not bool(torch.isnan(s[1]).all()):
+                    for k, v in spectrum_bias_scores(s[0].double().cpu(), s[1].double().cpu(), self._directional).items():
+                        logs[f"{label}/{k}/{n}"] = v
+        if "zonal_mean" in L:
+            for n, z in self._zonal().items():
+                logs[f"{L['zonal_mean']}/gen/{n}"] = z.cpu()
+                logs[f"{L['zonal_mean']}/error/{n}"] = (z[0] - z[1]).cpu()
+        key = L.get("time_mean_norm")
+        return InferenceSummary(logs=logs, loss=logs.get(f"{key}/rmse/channel_mean") if key else None)
+
+    def get_summary_logs(self) -> Dict[str, Any]:
+        return self.get_summary().logs
+
+    @torch.no_grad()
+    def get_inference_logs(self) -> List[Dict[str, Any]]:
+        """to_inference_logs (main.py:751-772): one dict per time index with ``<label>/forecast_step`` and
+        ``<label>/<metric>/<name>`` floats for both ``mean`` labels; the summary logs go in the last dict."""
+        rows: List[Dict[str, Any]] = [{} for _ in range(self._n_time if self._log_series else 1)]
+        for kind, key in (("denorm", "mean"), ("norm", "mean_norm")):
+            if key not in self._labels:
+                continue
+            label = self._labels[key]
+            series = {f"{m}/{n}": v.cpu().tolist() for m, d in self._series_data(kind).items() for n, v in d.items()}
+            for i, row in enumerate(rows):
+                row[f"{label}/forecast_step"] = i
+                for k in sorted(series):
+                    row[f"{label}/{k}"] = series[k][i]
+        rows[-1].update(self.get_summary_logs())
+        return rows
+
+    @torch.no_grad()
+    def flush_diagnostics(self, subdir: Optional[str] = None):
+        """main.py:713-731: one ``<sub-aggregator>_diagnostics.pt`` per non-empty sub-aggregator (root rank only)."""
+        if not self._save:
+            return
+        if self._output_dir is None:
+            raise ValueError("Output directory is not set.")
+        from .distributed import Distributed
+        out = self._output_dir if subdir is None else os.path.join(self._output_dir, subdir)
+        ds = self.get_dataset()
+        if Distributed.get_instance().is_root():
+            os.makedirs(out, exist_ok=True)
+            for name, d in ds.items():
+                if d:
+                    torch.save(d, os.path.join(out, f"{name}_diagnostics.pt"))

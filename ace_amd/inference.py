@@ -203,6 +203,39 @@ def run_inference(predict: Callable, data: InferenceData, aggregator=None, write
     return state
 
 
+def run_evaluator(predict: Callable, data: InferenceData, aggregator, writer=None,
+                  record_logs: Optional[Callable[[Any], None]] = None, compute_derived_variables: bool = False):
+    """The paired counterpart of ``run_inference`` (the reference's ``predict_paired`` under fme/core/generics/inference.py:117-166):
+    the window the loader yields carries the target variables beside the forcings, the target of a window is ``win[name][:, 1:]``
+    for every output name it holds, the writer gets the prediction and ``aggregator`` (ace_amd/evaluator.py) the pair.  With
+    ``compute_derived_variables`` the target gets the derived variables whose inputs the window holds, from ``predict``'s own
+    ``derive_target`` (``EnginePredict`` has one).  Returns the final prognostic state."""
+    if writer is None:
+        writer = NullDataWriter()
+    state = data.initial_condition
+    logs = aggregator.record_initial_condition(initial_condition=state)
+    if record_logs is not None:
+        record_logs(logs)
+    writer.write(state, "initial_condition.nc")
+    derive_target = getattr(predict, "derive_target", None) if compute_derived_variables else None
+    for win in data.loader:
+        if compute_derived_variables:
+            out, state = predict(state, win, compute_derived_variables=True)
+        else:
+            out, state = predict(state, win)
+        target = {k: win[k][:, 1:] for k in out if k in win}
+        if derive_target is not None:
+            target.update({k: v[:, 1:] for k, v in derive_target(win, list(target)).items() if k in out})
+        writer.append_batch(batch=out)
+        logs = aggregator.record_batch(prediction=out, target=target)
+        if record_logs is not None:
+            record_logs(logs)
+    writer.write(state, "restart.nc")
+    if hasattr(writer, "flush"):
+        writer.flush()
+    return state
+
+
 class EnginePredict:
     """``PredictFunction`` on the static-buffer ``RolloutEngine`` (``OceanRolloutEngine`` for a Samudra stepper): one engine per window length (the last window of a
     rollout may be shorter), built on first use.  Outputs are copied out of the engine's buffers (the next window reuses them)."""
@@ -221,6 +254,14 @@ class EnginePredict:
         self._labels = labels
         for eng in self._engines.values():
             eng.set_labels(labels)
+
+    def derive_target(self, window: TensorDict, names: Sequence[str]) -> TensorDict:
+        """The derived variables of the target fields ``names`` of a window (every time level), for ``run_evaluator``: the
+        stepper's derive function on them against the rest of the window; a variable whose inputs are missing is left out."""
+        window = self._stepper.forcing_deriver(window)
+        fields = {k: window[k] for k in names}
+        derived = self._stepper.derive_func(fields, {k: v for k, v in window.items() if k not in fields})
+        return {k: v for k, v in derived.items() if k not in window}
 
     def __call__(self, initial_condition: TensorDict, forcing: TensorDict,
                  compute_derived_variables: bool = False) -> Tuple[TensorDict, TensorDict]:

@@ -264,6 +264,28 @@ int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, c
  *                  4-byte boundary.
  *   diag_spectrum: coeffs: DEVICE complex64 [nnames][planes][lmax][mmax] (the forward SHT of each plane);
  *                  spec (DEVICE fp64 [nrows][lmax]) [rows[j]][l] += sum over planes and m of |c|^2.
+ *   diag_paired_window: the inference evaluator's paired metrics (fme/ace/aggregator/inference/main.py:526-732: reduced.py:221-316,
+ *                  time_mean.py:246-337, zonal_mean.py:153-266 on fme/core/metrics.py:63-224) from one read of the generated and
+ *                  the target planes of a window, in place of the reference's separate torch reductions per name and metric on
+ *                  the fields and on their normalised copies (main.py:594-598).  gen / target: DEVICE arrays of nplanes pointers to
+ *                  (batch, steps, nlat, nlon) fp32 fields with contiguous planes, and their DEVICE long [nplanes][2] sample and step
+ *                  strides in floats; target[j] may be NULL: then only name j's generated-side quantities are produced.  rows,
+ *                  wrows, weights (DEVICE fp32 [nw][nlat * nlon]): as diag_window; a pixel of weight 0 is skipped (NaN included),
+ *                  a NaN at a non-zero weight propagates.  partial: DEVICE fp64 scratch of ace_diag_paired_partial_doubles(...)
+ *                  values.  series: DEVICE fp64 [6][nrows][n_time] += at t0 + t the batch mean (samples in order) of the per-sample
+ *                    0 weighted mean of gen            1 weighted std of gen sqrt(wmean((x - wmean x)^2))
+ *                    2 weighted mean of target         3 weighted bias wmean(d), d = gen - target widened to fp64 first
+ *                    4 weighted rmse sqrt(wmean(d^2))   5 100 (G(gen) - G(target)) / G(target), G = the weighted nan-mean of the
+ *                  gradient magnitude sqrt(gy^2 + gx^2): torch.gradient with unit spacing (central differences inside, one-sided
+ *                  at the first / last row and at the first / last longitude, no periodic wrap), a pixel whose gradient is NaN
+ *                  leaving numerator and denominator; 2..5 only for a name with a target.  do_maps: tsum (DEVICE fp64
+ *                  [2][nrows][nlat * nlon], generated then target) += the per-pixel sums over samples (outer) and steps
+ *                  t >= t_begin (inner) as diag_window's, and zonal (DEVICE fp64 [2][nrows][nslots][nlat]) [side][row][slot][lat]
+ *                  += (the unweighted nan-mean over longitude of row lat, NaN for an all-NaN row) / (batch * factor), for b (outer)
+ *                  and t (inner) in order, at slot = (zt0 + t) / factor; slots >= nslots are dropped.  zt0: this window's first
+ *                  step counted from the first step of the zonal record.  tsum and zonal may be NULL when do_maps is 0.  A plane
+ *                  whose rows[j] or wrows[j] is out of range contributes to nothing.  2 <= nlat, 2 <= nlon <= 2730.  Planes and the
+ *                  weight table may start at any 4-byte boundary.
  * ------------------------------------------------------------------------------------------ */
 const char* ace_diag_last_error(void);
 long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
@@ -272,6 +294,11 @@ int ace_diag_window(const float* const* srcs, const long* strides, const int* ro
                     int nplanes, int batch, int steps, long hw, void* stream);
 int ace_diag_spectrum(const void* coeffs, const int* rows, double* spec, int nrows, int nnames, long planes, int lmax, int mmax,
                       void* stream);
+long ace_diag_paired_partial_doubles(int nplanes, int batch, int steps, int nlat, int nlon);
+int ace_diag_paired_window(const float* const* gen, const long* gen_strides, const float* const* target, const long* target_strides,
+                           const int* rows, const int* wrows, const float* weights, int nw, double* partial, double* tsum,
+                           double* zonal, double* series, int nrows, int n_time, int t0, int t_begin, int do_maps, int zt0, int factor,
+                           int nslots, int nplanes, int batch, int steps, int nlat, int nlon, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
