@@ -185,6 +185,10 @@ SIGNATURES = {
     # gen, gen_strides, target, target_strides, rows, wrows, weights, nw, partial, tsum, zonal, series, nrows, n_time, t0, t_begin,
     # do_maps, zt0, factor, nslots, nplanes, batch, steps, nlat, nlon, stream
     "ace_diag_paired_window": (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 4 + [c_int] * 13 + [c_void_p]),
+    "ace_diag_hist_scratch_bytes": (c_long, [c_int, c_int, c_int, c_long]),
+    # gen, gen_strides, target, target_strides, rows, masks, scratch, range, counts, dropped, nrows, n_bins, nplanes, batch, steps,
+    # hw, stream
+    "ace_diag_hist_window": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_long, c_void_p]),
 }
 
 _lib = None

@@ -23,6 +23,7 @@
 static thread_local std::string g_derr;
 static int dfail(int code, const std::string& m) { g_derr = m; return code; }
 extern "C" const char* ace_diag_last_error(void) { return g_derr.c_str(); }
+int ace_diag_fail_(int code, const std::string& m) { return dfail(code, m); }      // csrc/hist.hip reports through the same string
 #define DIAG_TRY(expr)                                                                                      \
     do {                                                                                                    \
         hipError_t e__ = (expr);                                                                            \

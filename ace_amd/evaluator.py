@@ -6,12 +6,16 @@ compared against a target record, for ``ace_amd.inference.run_evaluator``.  Buil
   * ``time_mean`` / ``time_mean_norm`` (time_mean.py:246-444): the time-mean maps of both sides, their bias map, RMSE and bias, and
     ``time_mean_norm/rmse/channel_mean``, which ``get_summary`` returns as the inference ``loss`` (main.py:668-676);
   * ``power_spectrum`` (spectrum.py:112-276): the mean spectra of prediction and target and their bias scores;
-  * ``zonal_mean`` (zonal_mean.py:50-355): time-latitude maps of both sides and of their difference, coarsened in time.
+  * ``zonal_mean`` (zonal_mean.py:50-355): time-latitude maps of both sides and of their difference, coarsened in time;
+  * ``histogram`` (histogram.py:12-82 on fme/core/histogram.py:121-509), off by default and built from a ``HistogramMetricConfig``
+    only: a 200-bin dynamic histogram of every paired name for prediction and target over the windows of ``record_batch``, the
+    99.9999th percentiles of both, and the trimmed densities as tensors where the reference logs a figure (``_Histograms``).
 
 Not built, skipped at build time with one warning and listed in ``skipped`` as the reference's non-strict path does
 (main.py:143-153): ``step_means``, ``ensembles``, ``annual``, ``enso_index``, ``enso_coefficient``, ``ipo_index``.  ``video``,
-``histogram``, ``seasonal``, ``trend``, ``near_zero_fraction``, the reference-data paths, a ``variables`` filter, HEALPix grids and
-``strict=True`` on a skipped metric raise ``NotImplementedError``.  As in ace_amd/aggregator.py, tensors and floats stand where the
+``seasonal``, ``trend``, ``near_zero_fraction``, a ``histogram`` enabled through a bare ``MetricConfig``, the reference-data paths, a
+``variables`` filter on any metric but the histogram, HEALPix grids and ``strict=True`` on a skipped metric raise
+``NotImplementedError``.  As in ace_amd/aggregator.py, tensors and floats stand where the
 reference logs images and figures, and a name whose mask has zeros is left out of the spectrum and listed in ``omitted``.
 
 Paired metrics cover the names present in both mappings, ``weighted_mean_gen`` / ``weighted_std_gen`` every generated name; a target
@@ -21,7 +25,9 @@ Two paths compute the same thing.  The torch path (``fused = False``, any device
 window and on ``normalize`` of the window.  The fused path (CUDA fp32 windows) makes one ``ace_diag_paired_window`` call per window
 (csrc/diag.hip: every quantity above from one pass over each plane, a band's halo rows re-read through the cache; fp64, fixed
 order, no atomics, no host synchronisation) and per
-spectrum chunk one SHT and one ``ace_diag_spectrum`` for each side.  It never normalises a field: ``normalize`` is (x - mu) / sigma
+spectrum chunk one SHT and one ``ace_diag_spectrum`` for each side, and with the histogram on one ``ace_diag_hist_window`` per window
+(csrc/hist.hip: range, update and binning passes on device-resident state, integer counts bitwise equal to the torch path's, nothing
+read back before ``get_*``).  It never normalises a field: ``normalize`` is (x - mu) / sigma
 per name (fme/core/normalizer.py:213-227), every per-sample quantity is linear in it (rmse / sigma, bias / sigma, (mean - mu) /
 sigma, std / sigma, and the time-mean RMSE / sigma), so the ``_norm`` outputs are formed from the denormalised fp64 accumulators at
 ``get_*`` time.  Names without statistics are dropped from the ``_norm`` outputs, as ``normalize`` drops them
@@ -67,6 +73,22 @@ class PowerSpectrumMetricConfig(MetricConfig):
     report_directional_bias: bool = True                                  # spectrum.py:317-322
 
 
+@dataclasses.dataclass
+class HistogramMetricConfig(MetricConfig):
+    """histogram.py:12-45.  ``variables``: record these names only; ``percentile_variables``: emit the percentile scalars for these
+    names only (the densities are still logged for every recorded name)."""
+    enabled: bool = False
+    strict: bool = True
+    name: Optional[str] = "histogram"
+    percentile_variables: Optional[List[str]] = None
+
+    def __post_init__(self):
+        if self.variables is not None and self.percentile_variables is not None:
+            extra = set(self.percentile_variables) - set(self.variables)
+            if extra:
+                raise ValueError(f"percentile_variables contains names not in variables: {sorted(extra)}")
+
+
 def _off() -> MetricConfig:
     return MetricConfig(enabled=False, strict=True)
 
@@ -89,7 +111,7 @@ class InferenceEvaluatorAggregatorConfig:
     time_mean_denorm: MetricConfig = dataclasses.field(default_factory=MetricConfig)
     time_mean_norm: MetricConfig = dataclasses.field(default_factory=MetricConfig)
     video: MetricConfig = dataclasses.field(default_factory=_off)
-    histogram: MetricConfig = dataclasses.field(default_factory=_off)
+    histogram: MetricConfig = dataclasses.field(default_factory=HistogramMetricConfig)
     seasonal: MetricConfig = dataclasses.field(default_factory=_off)
     annual: MetricConfig = dataclasses.field(default_factory=MetricConfig)
     enso_index: MetricConfig = dataclasses.field(default_factory=MetricConfig)
@@ -119,6 +141,11 @@ class InferenceEvaluatorAggregatorConfig:
                                       "aggregator is built)")
         for field in self.REFUSED:
             if getattr(self, field).enabled:
+                if field == "histogram":
+                    if isinstance(self.histogram, HistogramMetricConfig):
+                        continue
+                    raise NotImplementedError("the histogram metric is built from its typed configuration only: pass a "
+                                              "HistogramMetricConfig, not a bare MetricConfig")
                 raise NotImplementedError(f"the {field} metric is not built")
         skipped = []
         for field in self.SKIPPED:
@@ -148,7 +175,8 @@ class InferenceEvaluatorAggregatorConfig:
             dataset_info, int(n_ic_steps), int(n_forward_steps), normalize, labels=labels, skipped=skipped,
             zonal_mean_max_size=getattr(self.zonal_mean, "zonal_mean_max_size", 4096), channel_mean_names=channel_mean_names,
             report_directional_bias=getattr(self.power_spectrum, "report_directional_bias", True), output_dir=output_dir,
-            save_diagnostics=save_diagnostics, sht_factory=sht_factory)
+            save_diagnostics=save_diagnostics, sht_factory=sht_factory,
+            histogram=self.histogram if self.histogram.enabled else None)
 
 
 # ---- the reference's formulas in torch ops (the torch path) ---------------------------------------------------------------------
@@ -192,15 +220,198 @@ def spectrum_bias_scores(gen: torch.Tensor, target: torch.Tensor, directional: b
     return out
 
 
+HIST_BINS = 200                                                           # histogram.py:59
+HIST_PERCENTILES = (99.9999,)
+
+
+def trim_zero_bins(counts, edges):
+    """fme/core/histogram.py:52-71: the empty bins at both ends removed"""
+    import numpy as np
+    mask = counts > 0
+    first, last = int(np.argmax(mask)), len(mask) - int(np.argmax(mask[::-1]))
+    return counts[first:last], edges[first:last + 1]
+
+
+def histogram_quantile(edges, counts, probability: float) -> float:
+    """fme/core/metrics.py:355-385: the inverse CDF, linear inside a bin"""
+    import numpy as np
+    cdf = np.cumsum(counts)
+    cdf = np.insert(cdf / cdf[-1], 0, 0)
+    i = int(np.argmax(cdf > probability)) - 1
+    return float(edges[i] + (edges[i + 1] - edges[i]) * (probability - cdf[i]) / (cdf[i + 1] - cdf[i]))
+
+
+class _Histograms:
+    """ComparedDynamicHistograms(n_bins=200, percentiles=[99.9999]) (fme/core/histogram.py:336-509) behind the reference's
+    HistogramAggregator and its ``variables`` filter (histogram.py:50-82, build_context.py:19-46): per paired name and side one
+    dynamic histogram of every unmasked value of every window of ``record_batch``.  The statement both paths follow is the header
+    contract of ``ace_diag_hist_window`` (include/ace_sfno.h): the range starts at (min - 1e-6, max + 1e-6) of the first window,
+    doubles towards whichever side a later window overflows, pairs of bins merging, and a value goes to bin
+    int((x - float(lo)) / float(bin)) with the division in fp32 - by a 0-dim tensor on the torch path, because torch on a GPU turns
+    a division by a Python scalar into a multiplication by its reciprocal, which moves values across bin edges.
+
+    The NaN mask of a name is the NaN pattern of the target's first sample and step at the first window, for both sides
+    (fme/core/histogram.py:241-264); it is kept as a device plane and never reduced to a flag.  One difference from the reference:
+    a window whose unmasked values hold a non-finite value, or whose range is degenerate in fp32, is skipped and counted
+    (``dropped_windows``) at every window; the reference skips it once it has edges (fme/core/histogram.py:181-183) but on a first
+    window keeps the poisoned edges.  The torch path reads minima, maxima and counts back per name, as the reference does; the
+    fused path reads nothing back before ``dataset`` / ``logs``."""
+
+    def __init__(self, config: HistogramMetricConfig):
+        self.label = config.name or "histogram"
+        self._only = None if config.variables is None else frozenset(config.variables)
+        self._pct_only = None if config.percentile_variables is None else set(config.percentile_variables)
+        self._names: Optional[List[str]] = None
+        self._masks: Dict[str, torch.Tensor] = {}                         # name -> bool (1, 1, H, W), True where removed
+        self._host: Dict[str, List[Dict[str, Any]]] = {}                   # torch path: name -> [generated, target] states
+        self._range = self._counts = self._dropped = self._mask_planes = self._table = None     # fused path
+
+    @property
+    def recorded(self) -> bool:
+        return self._names is not None
+
+    def _select(self, gen, tgt):
+        """_check_overlapping_keys (fme/core/histogram.py:357-372) after the variable filter"""
+        keep = lambda d: {k: v for k, v in d.items() if self._only is None or k in self._only}      # noqa: E731
+        gen, tgt = keep(gen), keep(tgt)
+        current = set(tgt).intersection(gen)
+        if self._names is None:
+            if not current:
+                raise ValueError("No overlapping keys between target and prediction variables. "
+                                 f"target: {tgt.keys()}, prediction: {gen.keys()}")
+            self._names = sorted(current)
+            for n in self._names:
+                self._masks[n] = tgt[n][:1, :1].isnan()
+        elif current != set(self._names):
+            raise ValueError("Available comparison variables provided to record_batch differ from initial call to record_batch.  "
+                             f"initial: {set(self._names)}, current: {current}")
+        return gen, tgt
+
+    # ---- the torch path -----------------------------------------------------------------------------------------------
+    def record_torch(self, gen, tgt):
+        import numpy as np
+        gen, tgt = self._select(gen, tgt)
+        for n in self._names:
+            states = self._host.setdefault(n, [{"lo": math.nan, "hi": math.nan, "counts": np.zeros(HIST_BINS, np.int64),
+                                               "dropped": 0} for _ in range(2)])
+            for st, x in zip(states, (gen[n], tgt[n])):
+                v = torch.masked_select(x, ~self._masks[n].to(x.device).expand(x.shape))
+                if v.numel() == 0 or not bool(torch.isfinite(v).all()):
+                    st["dropped"] += 1
+                    continue
+                vmin, vmax = float(v.min() - 1.0e-6), float(v.max() + 1.0e-6)     # the epsilon in the tensor's precision
+                lo, hi, nleft, nright = st["lo"], st["hi"], 0, 0
+                if math.isnan(lo):
+                    lo, hi = vmin, vmax
+                else:
+                    while vmin < lo:
+                        lo, nleft = hi - 2 * (hi - lo), nleft + 1
+                    while vmax > hi:
+                        hi, nright = lo + 2 * (hi - lo), nright + 1
+                with np.errstate(all="ignore"):
+                    edges = np.linspace(lo, hi, HIST_BINS + 1)
+                flo = torch.tensor(float(edges[0]), dtype=v.dtype, device=v.device)
+                fbin = torch.tensor(float(edges[1] - edges[0]), dtype=v.dtype, device=v.device)
+                if not (float(fbin) > 0 and math.isfinite(float(fbin)) and math.isfinite(float(flo))):
+                    st["dropped"] += 1
+                    continue
+                c = st["counts"]
+                for i in range(nleft + nright):
+                    merged, c = c[0::2] + c[1::2], np.zeros(HIST_BINS, np.int64)
+                    c[HIST_BINS // 2 if i < nleft else 0:][:HIST_BINS // 2] = merged
+                idx = ((v - flo) / fbin).clamp(0, HIST_BINS - 1).int()            # past the last edge: the last bin
+                st.update(lo=lo, hi=hi, counts=c + torch.bincount(idx, minlength=HIST_BINS).cpu().numpy())
+
+    # ---- the fused path -----------------------------------------------------------------------------------------------
+    def record_fused(self, gen, tgt) -> int:
+        """one ``ace_diag_hist_window`` for both sides and all names of fields with contiguous planes; returns the launches made"""
+        from . import _lib
+        gen, tgt = self._select(gen, tgt)
+        names = self._names
+        n, first = len(names), gen[names[0]]
+        dev, (B, T, H, W) = first.device, first.shape
+        if self._range is None:
+            self._range = torch.full((2, n, 2), math.nan, dtype=torch.float64, device=dev)
+            self._counts = torch.zeros(2, n, HIST_BINS, dtype=torch.int64, device=dev)
+            self._dropped = torch.zeros(2, n, dtype=torch.int32, device=dev)
+            self._mask_planes = torch.stack([self._masks[nm].reshape(H * W) for nm in names]).to(torch.uint8).contiguous()
+            self._rows = _upload(list(range(n)), torch.int32, dev)
+        table = []
+        for d in (gen, tgt):
+            table += [d[nm].data_ptr() for nm in names]
+            for nm in names:
+                table += [d[nm].stride(0), d[nm].stride(1)]
+        table += [self._mask_planes.data_ptr() + i * H * W for i in range(n)]
+        table = _upload(table, torch.int64, dev)
+        lib = _lib.lib()
+        scratch = torch.empty(int(lib.ace_diag_hist_scratch_bytes(n, B, T, H * W)), dtype=torch.uint8, device=dev)
+        base = table.data_ptr()
+        _check(lib.ace_diag_hist_window(base, base + 8 * n, base + 24 * n, base + 32 * n, self._rows.data_ptr(), base + 48 * n,
+                                        scratch.data_ptr(), self._range.data_ptr(), self._counts.data_ptr(),
+                                        self._dropped.data_ptr(), n, HIST_BINS, n, B, T, H * W, _lib.current_stream()))
+        return 1
+
+    # ---- results ------------------------------------------------------------------------------------------------------
+    def _state(self):
+        """name -> ([target, prediction] int64 counts (2, n_bins), fp64 edges (2, n_bins + 1), dropped windows)"""
+        import numpy as np
+        out = {}
+        if self._range is not None:
+            rng, cnt, drop = self._range.cpu().numpy(), self._counts.cpu().numpy(), self._dropped.cpu().numpy()
+        for i, n in enumerate(self._names):
+            if self._range is not None:
+                sides = [(rng[s, i, 0], rng[s, i, 1], cnt[s, i], int(drop[s, i])) for s in (1, 0)]
+            else:
+                sides = [(st["lo"], st["hi"], st["counts"], st["dropped"]) for st in reversed(self._host[n])]
+            with np.errstate(all="ignore"):
+                edges = np.stack([np.linspace(lo, hi, HIST_BINS + 1) for lo, hi, _, _ in sides])
+            out[n] = (np.stack([c for _, _, c, _ in sides]), edges, sum(d for _, _, _, d in sides))
+        return out
+
+    def dataset(self) -> Dict[str, torch.Tensor]:
+        """fme/core/histogram.py:480-509: ``<name>`` (2, n_bins) int64 and ``<name>_bin_edges`` (2, n_bins + 1) fp64, the leading
+        axis source = [target, prediction]"""
+        ds = {}
+        for n, (counts, edges, _) in self._state().items():
+            ds[n] = torch.from_numpy(counts.copy())
+            ds[f"{n}_bin_edges"] = torch.from_numpy(edges.copy())
+        return ds
+
+    def logs(self) -> Dict[str, Any]:
+        """fme/core/histogram.py:446-478 without the label: ``<source>/<p>th-percentile/<name>`` floats, ``<name>`` the trimmed
+        densities and edges of both sources (the reference's figure), ``dropped_windows/<name>`` when any window was skipped.  A
+        source without a recorded value has no percentile and an empty density."""
+        import numpy as np
+        logs: Dict[str, Any] = {}
+        for n, (counts, edges, dropped) in self._state().items():
+            fig = {}
+            for s, source in enumerate(("target", "prediction")):
+                if counts[s].sum() == 0:
+                    fig[f"{source}_density"], fig[f"{source}_bin_edges"] = torch.zeros(0, dtype=torch.float64), \
+                        torch.zeros(0, dtype=torch.float64)
+                    continue
+                c, e = trim_zero_bins(counts[s], edges[s])
+                fig[f"{source}_density"] = torch.from_numpy(c / np.sum(c * np.diff(e)))       # _normalize_histogram
+                fig[f"{source}_bin_edges"] = torch.from_numpy(e.copy())
+                if self._pct_only is None or n in self._pct_only:
+                    for p in HIST_PERCENTILES:
+                        logs[f"{source}/{p}th-percentile/{n}"] = histogram_quantile(e, c, p / 100.0)
+            logs[n] = fig
+            if dropped:
+                logs[f"dropped_windows/{n}"] = dropped
+        return logs
+
+
 class InferenceEvaluatorAggregator(InferenceAggregator):
     """main.py:526-732 for the sub-aggregators of the module docstring.  Weights, masks, routing and the SHT are the parent's."""
 
     def __init__(self, dataset_info, n_ic_steps: int, n_forward_steps: int, normalize, labels: Optional[Mapping[str, str]] = None,
                  skipped: Sequence[str] = (), zonal_mean_max_size: int = 4096, channel_mean_names: Optional[Sequence[str]] = None,
                  report_directional_bias: bool = True, output_dir: Optional[str] = None, save_diagnostics: bool = False,
-                 sht_factory=None, spectrum_chunk_bytes: int = 256 << 20):
+                 sht_factory=None, spectrum_chunk_bytes: int = 256 << 20, histogram: Optional[HistogramMetricConfig] = None):
         super().__init__(dataset_info, n_ic_steps + n_forward_steps, True, output_dir, save_diagnostics, sht_factory,
                          spectrum_chunk_bytes)
+        self._hist = None if histogram is None or not histogram.enabled else _Histograms(histogram)
         self.n_ic_steps = int(n_ic_steps)
         self.skipped = list(skipped)
         default = InferenceEvaluatorAggregatorConfig.BUILT.values()
@@ -236,8 +447,9 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         return super().route({**{f"p:{k}": v for k, v in prediction.items()}, **{f"t:{k}": v for k, v in (target or {}).items()}})
 
     def launches(self) -> int:
-        """Native launches made so far: one ``ace_diag_paired_window`` per window, and per spectrum chunk of either side one
-        forward SHT and one ``ace_diag_spectrum``."""
+        """Native launches made so far: one ``ace_diag_paired_window`` per window, one ``ace_diag_hist_window`` per window of
+        ``record_batch`` when the histogram is on, and per spectrum chunk of either side one forward SHT and one
+        ``ace_diag_spectrum``."""
         return self._launches
 
     def _pick_pair(self, prediction, target) -> str:
@@ -338,6 +550,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
     def _record_torch_pair(self, gen, tgt, i_time_start, with_maps, ignore_initial):
         T = next(iter(gen.values())).shape[1]
         sl = slice(i_time_start, i_time_start + T)
+        if with_maps and self._hist is not None:
+            self._hist.record_torch(gen, tgt)
         kinds = {"denorm": (gen, tgt)}
         if self._need_norm:
             kinds["norm"] = (self._normalize_fn(gen), self._normalize_fn(tgt))            # main.py:594-598
@@ -451,6 +665,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
                 len(self._rows), n_time, t0, 1 if ignore_initial else 0, 1 if with_maps else 0, zt0,
                 self._factor if zonal else 1, self._zon.shape[2], n, B, T, H, W, _lib.current_stream()))
             self._launches += 1
+            if with_maps and self._hist is not None:
+                self._launches += self._hist.record_fused(gen, tgt)
             if not with_maps or "power_spectrum" not in self._labels:
                 return
             sht = self._get_sht()
@@ -622,6 +838,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
             for n, z in self._zonal().items():
                 d[f"gen-{n}"] = z[0].cpu()
                 d[f"error-{n}"] = (z[0] - z[1]).cpu()
+        if self._hist is not None and self._hist.recorded:
+            ds[self._hist.label] = self._hist.dataset()
         return ds
 
     @torch.no_grad()
@@ -646,6 +864,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
             for n, z in self._zonal().items():
                 logs[f"{L['zonal_mean']}/gen/{n}"] = z.cpu()
                 logs[f"{L['zonal_mean']}/error/{n}"] = (z[0] - z[1]).cpu()
+        if self._hist is not None and self._hist.recorded:
+            logs.update({f"{self._hist.label}/{k}": v for k, v in self._hist.logs().items()})
         key = L.get("time_mean_norm")
         return InferenceSummary(logs=logs, loss=logs.get(f"{key}/rmse/channel_mean") if key else None)
 

@@ -286,6 +286,32 @@ int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, c
  *                  step counted from the first step of the zonal record.  tsum and zonal may be NULL when do_maps is 0.  A plane
  *                  whose rows[j] or wrows[j] is out of range contributes to nothing.  2 <= nlat, 2 <= nlon <= 2730.  Planes and the
  *                  weight table may start at any 4-byte boundary.
+ *   diag_hist_window: the evaluator's histogram metric (fme/ace/aggregator/inference/histogram.py:57-82 on
+ *                  fme/core/histogram.py:74-225, n_times = 1): one dynamic histogram per (side, row), side 0 = generated, 1 =
+ *                  target, both sides and all names of a window in one call.  gen / target / strides / rows: as
+ *                  diag_paired_window, planes of hw contiguous fp32; target[j] may be NULL: then only the generated side of name
+ *                  j is recorded.  masks: NULL, or a DEVICE array of nplanes pointers to uint8 [hw] (a NULL entry: no mask); a
+ *                  pixel whose byte is non-zero is removed from both sides of plane j.  State, all DEVICE and persistent across
+ *                  calls: range fp64 [2][nrows][2] = (lo, hi), a NaN lo meaning "no window yet"; counts int64
+ *                  [2][nrows][n_bins]; dropped int32 [2][nrows].  scratch: 16-byte aligned DEVICE memory of the bytes
+ *                  ace_diag_hist_scratch_bytes(...) returns (-1 for arguments this call would refuse).
+ *                  Per (side, plane j) with v = the unmasked values of all samples and steps:
+ *                    1. vmin = (double)(min v - 1e-6f), vmax = (double)(max v + 1e-6f), the epsilon added in fp32.
+ *                    2. lo is NaN: lo, hi = vmin, vmax.  Otherwise, while vmin < lo: lo = hi - 2 (hi - lo), and then while
+ *                       vmax > hi: hi = lo + 2 (hi - lo); each doubling replaces counts by c[i] = counts[2i] + counts[2i+1] in the
+ *                       upper half (left doubling) or the lower half (right doubling) and zeros in the other half.
+ *                    3. step = (hi - lo) / n_bins and bin = (lo + step) - lo in fp64 (numpy's linspace(lo, hi, n_bins + 1)[1] -
+ *                       [0]).
+ *                    4. every value x adds 1 to counts[idx], q = (x - (float)lo) / (float)bin in fp32 with a correctly rounded
+ *                       division and no contraction, idx = n_bins - 1 where q >= n_bins, 0 where q < 0, else q truncated.
+ *                  The window of a (side, plane) is dropped - lo, hi and counts unchanged, dropped[side][row] += 1 - when v holds
+ *                  a non-finite value, when v is empty, or when after step 2 (float)bin is 0 or not finite or (float)lo is not
+ *                  finite (a constant field whose epsilon vanishes in fp32).  The reference drops such a window too once it has
+ *                  edges; on a first window it keeps the poisoned edges instead, here the next good window starts the range.
+ *                  A plane whose rows[j] is out of range contributes to nothing.  rows must not name one row twice; this is not
+ *                  checked.  n_bins even, 2 <= n_bins <= 1024; batch * steps <= 2^21; nplanes == 0 is a no-op.  Counts are
+ *                  integers added with integer atomics: bitwise repeatable.  Three launches, no allocation, no host
+ *                  synchronisation.  Planes may start at any 4-byte boundary.
  * ------------------------------------------------------------------------------------------ */
 const char* ace_diag_last_error(void);
 long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
@@ -299,6 +325,10 @@ int ace_diag_paired_window(const float* const* gen, const long* gen_strides, con
                            const int* rows, const int* wrows, const float* weights, int nw, double* partial, double* tsum,
                            double* zonal, double* series, int nrows, int n_time, int t0, int t_begin, int do_maps, int zt0, int factor,
                            int nslots, int nplanes, int batch, int steps, int nlat, int nlon, void* stream);
+long ace_diag_hist_scratch_bytes(int nplanes, int batch, int steps, long hw);
+int ace_diag_hist_window(const float* const* gen, const long* gen_strides, const float* const* target, const long* target_strides,
+                         const int* rows, const unsigned char* const* masks, void* scratch, double* range, long long* counts,
+                         int* dropped, int nrows, int n_bins, int nplanes, int batch, int steps, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
