@@ -9,12 +9,26 @@ compared against a target record, for ``ace_amd.inference.run_evaluator``.  Buil
   * ``zonal_mean`` (zonal_mean.py:50-355): time-latitude maps of both sides and of their difference, coarsened in time;
   * ``histogram`` (histogram.py:12-82 on fme/core/histogram.py:121-509), off by default and built from a ``HistogramMetricConfig``
     only: a 200-bin dynamic histogram of every paired name for prediction and target over the windows of ``record_batch``, the
-    99.9999th percentiles of both, and the trimmed densities as tensors where the reference logs a figure (``_Histograms``).
+    99.9999th percentiles of both, and the trimmed densities as tensors where the reference logs a figure (``_Histograms``);
+  * ``trend`` (trend.py:46-314), off by default and built from a ``TrendMetricConfig`` only: the per-pixel least-squares slope of
+    every name against time in years since 2000-01-01 (a fixed 365.25-day year) for target and prediction, in fp64, and the
+    area-weighted RMSE between the two maps.  It needs the time axis of each window: ``record_batch(..., time=)``, which
+    ``inference.run_evaluator`` hands to an aggregator whose ``needs_time`` is set;
+  * ``enso_coefficient`` (enso/enso_coefficient.py:61-500), built from an ``EnsoCoefficientMetricConfig`` that carries an
+    ``index``: per pixel the regression coefficient of every name on a zero-mean index series, per sample, averaged over the
+    samples, for target and prediction, and the area-weighted RMSE of the two maps.  The one stated difference: the reference looks
+    the index up in its own monthly Nino 3.4 table, which is not shipped here; the caller supplies the index values at every time
+    level of every sample, a row with a non-finite value standing for the reference's sample without a series.  Without an index
+    the metric is skipped, as it always was;
+  * ``near_zero_fraction`` (near_zero_fraction.py:20-300), off by default and built from a ``NearZeroFractionMetricConfig`` only:
+    the area-weighted fraction of cells ``<= eps`` of the named variables for the prediction and its difference from the target's,
+    and with ``include_maps`` the per-cell fractions (``_Regress`` holds these three).
 
 Not built, skipped at build time with one warning and listed in ``skipped`` as the reference's non-strict path does
-(main.py:143-153): ``step_means``, ``ensembles``, ``annual``, ``enso_index``, ``enso_coefficient``, ``ipo_index``.  ``video``,
-``seasonal``, ``trend``, ``near_zero_fraction``, a ``histogram`` enabled through a bare ``MetricConfig``, the reference-data paths, a
-``variables`` filter on any metric but the histogram, HEALPix grids and ``strict=True`` on a skipped metric raise
+(main.py:143-153): ``step_means``, ``ensembles``, ``annual``, ``enso_index``, ``ipo_index``, an ``enso_coefficient`` without an index
+or over a record of 1800 days or less, a ``trend`` over fewer than two forward steps.  ``video``, ``seasonal``, a ``histogram``,
+``trend`` or ``near_zero_fraction`` enabled through a bare ``MetricConfig``, the reference-data paths, a ``variables`` filter on any
+metric but the histogram, the trend and the near-zero fraction, HEALPix grids and ``strict=True`` on a skipped metric raise
 ``NotImplementedError``.  As in ace_amd/aggregator.py, tensors and floats stand where the
 reference logs images and figures, and a name whose mask has zeros is left out of the spectrum and listed in ``omitted``.
 
@@ -27,7 +41,9 @@ window and on ``normalize`` of the window.  The fused path (CUDA fp32 windows) m
 order, no atomics, no host synchronisation) and per
 spectrum chunk one SHT and one ``ace_diag_spectrum`` for each side, and with the histogram on one ``ace_diag_hist_window`` per window
 (csrc/hist.hip: range, update and binning passes on device-resident state, integer counts bitwise equal to the torch path's, nothing
-read back before ``get_*``).  It never normalises a field: ``normalize`` is (x - mu) / sigma
+read back before ``get_*``), and with any of trend, enso_coefficient and near_zero_fraction on one ``ace_diag_regress_window`` per
+window for the three together (csrc/regress.hip: every plane read once, the fp64 sums of a pixel kept in registers).  It never
+normalises a field: ``normalize`` is (x - mu) / sigma
 per name (fme/core/normalizer.py:213-227), every per-sample quantity is linear in it (rmse / sigma, bias / sigma, (mean - mu) /
 sigma, std / sigma, and the time-mean RMSE / sigma), so the ``_norm`` outputs are formed from the denormalised fp64 accumulators at
 ``get_*`` time.  Names without statistics are dropped from the ``_norm`` outputs, as ``normalize`` drops them
@@ -39,6 +55,7 @@ scaled by 1 / factor, which equals the reference's buffer-carry form (zonal_mean
 accumulator memory: names x 2 x slots x H x 8 bytes (40 names, 4096 slots, 180 latitudes: 472 MB; the default
 ``zonal_mean_max_size`` only coarsens past 4096 steps)."""
 import dataclasses
+import datetime
 import logging
 import math
 import os
@@ -89,6 +106,50 @@ class HistogramMetricConfig(MetricConfig):
                 raise ValueError(f"percentile_variables contains names not in variables: {sorted(extra)}")
 
 
+@dataclasses.dataclass
+class TrendMetricConfig(MetricConfig):
+    """trend.py:279-314.  ``variables``: compute trends for these names only."""
+    enabled: bool = False
+    strict: bool = False
+    name: Optional[str] = "trend"
+
+
+@dataclasses.dataclass
+class NearZeroFractionMetricConfig(MetricConfig):
+    """near_zero_fraction.py:20-94: the area-weighted fraction of cells ``<= eps`` of ``variables`` (``per_variable_eps``
+    overriding ``eps`` per name); ``include_maps``: also the per-cell fraction maps."""
+    enabled: bool = False
+    strict: bool = True
+    variables: List[str] = dataclasses.field(default_factory=list)
+    name: Optional[str] = "near_zero_fraction"
+    eps: float = 0.0
+    per_variable_eps: Dict[str, float] = dataclasses.field(default_factory=dict)
+    include_maps: bool = False
+
+    def __post_init__(self):                                              # near_zero_fraction.py:61-80
+        if not self.enabled:
+            return
+        if not self.variables:
+            raise ValueError("NearZeroFractionMetricConfig is enabled but no variables were given; specify the variables to "
+                             "compute the metric for.")
+        if self.eps < 0:
+            raise ValueError(f"NearZeroFractionMetricConfig.eps must be >= 0, got {self.eps}.")
+        negative = {var: value for var, value in self.per_variable_eps.items() if value < 0}
+        if negative:
+            raise ValueError(f"NearZeroFractionMetricConfig.per_variable_eps values must be >= 0, got {negative}.")
+
+
+@dataclasses.dataclass
+class EnsoCoefficientMetricConfig(MetricConfig):
+    """enso_coefficient.py:440-500 with the index supplied by the caller: ``index`` is a (B, n_ic_steps + n_forward_steps) tensor of
+    index values at every time level of every sample (the reference looks them up in its own monthly Nino 3.4 table, which is not
+    shipped here); ``None`` leaves the metric skipped."""
+    enabled: bool = True
+    strict: bool = False
+    name: Optional[str] = "enso_coefficient"
+    index: Optional[Any] = None
+
+
 def _off() -> MetricConfig:
     return MetricConfig(enabled=False, strict=True)
 
@@ -115,10 +176,10 @@ class InferenceEvaluatorAggregatorConfig:
     seasonal: MetricConfig = dataclasses.field(default_factory=_off)
     annual: MetricConfig = dataclasses.field(default_factory=MetricConfig)
     enso_index: MetricConfig = dataclasses.field(default_factory=MetricConfig)
-    enso_coefficient: MetricConfig = dataclasses.field(default_factory=MetricConfig)
+    enso_coefficient: MetricConfig = dataclasses.field(default_factory=EnsoCoefficientMetricConfig)
     ipo_index: MetricConfig = dataclasses.field(default_factory=MetricConfig)
-    trend: MetricConfig = dataclasses.field(default_factory=lambda: MetricConfig(enabled=False))
-    near_zero_fraction: MetricConfig = dataclasses.field(default_factory=_off)
+    trend: MetricConfig = dataclasses.field(default_factory=TrendMetricConfig)
+    near_zero_fraction: MetricConfig = dataclasses.field(default_factory=NearZeroFractionMetricConfig)
     monthly_reference_data: Optional[str] = None
     time_mean_reference_data: Optional[str] = None
     step_diagnostics: Optional[Any] = None
@@ -146,12 +207,26 @@ class InferenceEvaluatorAggregatorConfig:
                         continue
                     raise NotImplementedError("the histogram metric is built from its typed configuration only: pass a "
                                               "HistogramMetricConfig, not a bare MetricConfig")
+                if isinstance(getattr(self, field), (TrendMetricConfig, NearZeroFractionMetricConfig)):
+                    continue
                 raise NotImplementedError(f"the {field} metric is not built")
         skipped = []
+        trend = self.trend if self.trend.enabled else None
+        if trend is not None and n_forward_steps < 2:                     # trend.py:300-308, through the skipped-metric path
+            if trend.strict:
+                raise NotImplementedError(f"trend metric requires at least 2 forward steps, got {n_forward_steps} (strict=True)")
+            skipped.append("trend")
+            trend = None
+        enso = self.enso_coefficient
+        if not (enso.enabled and isinstance(enso, EnsoCoefficientMetricConfig) and enso.index is not None):
+            enso = None
+        elif getattr(dataset_info, "timestep", None) is not None and \
+                (n_ic_steps + n_forward_steps) * dataset_info.timestep <= datetime.timedelta(days=1800):
+            enso = None                                                   # enso_coefficient.py:478-483; skipped or raised below
         for field in self.SKIPPED:
             v = getattr(self, field)
             for m in (v if isinstance(v, list) else [v]):
-                if not m.enabled:
+                if not m.enabled or m is enso:
                     continue
                 if m.strict:
                     raise NotImplementedError(f"the {field} metric is not built (strict=True)")
@@ -176,7 +251,8 @@ class InferenceEvaluatorAggregatorConfig:
             zonal_mean_max_size=getattr(self.zonal_mean, "zonal_mean_max_size", 4096), channel_mean_names=channel_mean_names,
             report_directional_bias=getattr(self.power_spectrum, "report_directional_bias", True), output_dir=output_dir,
             save_diagnostics=save_diagnostics, sht_factory=sht_factory,
-            histogram=self.histogram if self.histogram.enabled else None)
+            histogram=self.histogram if self.histogram.enabled else None, trend=trend, enso_coefficient=enso,
+            near_zero_fraction=self.near_zero_fraction if self.near_zero_fraction.enabled else None)
 
 
 # ---- the reference's formulas in torch ops (the torch path) ---------------------------------------------------------------------
@@ -402,16 +478,362 @@ class _Histograms:
         return logs
 
 
+SECONDS_PER_YEAR = 365.25 * 24 * 60 * 60                                 # trend.py:21-25: a fixed Julian year
+TREND_EPOCH = (2000, 1, 1)                                                # trend.py:26-32
+MAX_REGRESS_MAPS = 8                                                      # ACE_DIAG_REGRESS_MAX_MAPS (include/ace_sfno.h)
+
+
+class _Regress:
+    """The three metrics that are per-pixel sums over time: ``trend`` (TrendEvaluatorAggregator, trend.py:46-194),
+    ``enso_coefficient`` (EnsoCoefficientEvaluatorAggregator, enso_coefficient.py:61-244) and ``near_zero_fraction``
+    (NearZeroFractionAggregator, near_zero_fraction.py:97-216).  The torch path states the reference's formulas in the reference's
+    dtypes (trend fp64, the ENSO covariance fp32, the indicator in the field's dtype); the fused path feeds all that are on from one
+    ``ace_diag_regress_window`` per window (csrc/regress.hip; the header contract in include/ace_sfno.h): term 0 = 1 -> map 0 (sum y),
+    term 1 = t in years -> map 1 (sum t y), term 2 = the index -> map 2 + b (sample b's covariance), eps per plane for the indicator
+    (NaN for a plane outside the near-zero variables: nothing is below NaN).  n, sum t, sum t^2, the per-sample sum of index^2 and
+    the record counts stay on the host in fp64.
+
+    The ENSO index is the caller's (B, n_ic_steps + n_forward_steps) table; each row is made zero-mean over its time levels in fp64
+    (enso_coefficient.py:408-410) and rounded to fp32, as the reference rounds each window's values (enso_coefficient.py:141-145);
+    both paths regress on those fp32 numbers.  A row with a non-finite value is left out, the reference's ``None`` series.  The
+    reference records the ENSO sums at every step of a window but drops, as the time mean does, the first step of a window at time
+    index 0 from the trend and the near-zero fraction; the fused path then makes a second call for the ENSO term alone."""
+
+    def __init__(self, agg, trend, enso, nzf):
+        self._agg = agg
+        self.trend, self.enso, self.nzf = trend, enso, nzf
+        self._n = self._sum_t = self._sum_tt = 0.0
+        self._index = self._valid = None
+        if enso is not None:
+            idx = torch.as_tensor(enso.index).detach().to("cpu", torch.float64)
+            if idx.dim() != 2 or idx.shape[1] != agg._n_time:
+                raise ValueError(f"enso_coefficient.index must be (samples, {agg._n_time} time levels), got {tuple(idx.shape)}")
+            self._valid = [bool(torch.isfinite(row).all()) for row in idx]
+            self._index = (idx - idx.mean(dim=1, keepdim=True)).float()
+            self._ivar64 = [0.0] * idx.shape[0]
+        self._recorded = False
+        self._tnames: List[List[str]] = [[], []]                              # per side, the names of each metric seen so far
+        self._enames: List[List[str]] = [[], []]
+        self._znames: List[List[str]] = [[], []]
+        self._zcount = 0                                                  # (sample, step) entries behind the fractions and maps
+        # torch path
+        self._t_sum_y: List[Dict[str, torch.Tensor]] = [{}, {}]
+        self._t_sum_ty: List[Dict[str, torch.Tensor]] = [{}, {}]
+        self._t_cov: List[Dict[int, Dict[str, torch.Tensor]]] = [{}, {}]
+        self._t_ivar: Dict[int, torch.Tensor] = {}
+        self._t_frac: List[Dict[str, torch.Tensor]] = [{}, {}]
+        self._t_cells: List[Dict[str, torch.Tensor]] = [{}, {}]
+        # fused path: _maps (2, rows, nmaps, H W) fp64, _count (2, rows, H W) int64, _frac (2, rows) fp64
+        self._rows: Dict[str, int] = {}
+        self._maps = self._count = self._frac = None
+        self._nmaps = 0
+
+    @property
+    def needs_time(self) -> bool:
+        return self.trend is not None
+
+    def labels(self) -> List[str]:
+        return [m.name or d for m, d in ((self.trend, "trend"), (self.enso, "enso_coefficient"), (self.nzf, "near_zero_fraction"))
+                if m is not None]
+
+    def _eps_for(self, name: str) -> float:
+        return self.nzf.per_variable_eps.get(name, self.nzf.eps)
+
+    def _prepare(self, gen, tgt, i_time_start, time):
+        """the host side of a window: the name lists of each metric, the years and the index values of its steps"""
+        B, T = next(iter(gen.values())).shape[:2]
+        begin = 1 if i_time_start == 0 else 0
+        only = lambda d, v: [n for n in d if v is None or n in v]           # noqa: E731  (maybe_filter, build_context.py:19-46)
+        years = None
+        if self.trend is not None:
+            if time is None:
+                raise ValueError("the trend metric needs the window's time axis: record_batch(prediction, target, time=...)")
+            if tuple(time.shape) != (B, T):
+                raise ValueError(f"time must be (samples, steps) = {(B, T)}, got {tuple(time.shape)}")
+            years = time.microseconds_since(TREND_EPOCH).astype("float64") / 1.0e6 / SECONDS_PER_YEAR
+            part = years[:, begin:]
+            self._n += part.size
+            self._sum_t += float(part.sum())
+            self._sum_tt += float((part * part).sum())
+        index = None
+        if self.enso is not None:
+            if B != self._index.shape[0]:
+                raise ValueError("number of index series must match number of samples")
+            index = self._index[:, i_time_start:i_time_start + T]
+            for b in range(B):
+                if self._valid[b]:
+                    self._ivar64[b] += float((index[b].double() ** 2).sum())
+        names = {"trend": [only(d, self.trend.variables) if self.trend is not None and T > begin else [] for d in (gen, tgt)],
+                 "enso": [list(d) if self.enso is not None else [] for d in (gen, tgt)],
+                 "nzf": [only(d, self.nzf.variables) if self.nzf is not None and T > begin else [] for d in (gen, tgt)]}
+        for key, seen in (("trend", self._tnames), ("enso", self._enames), ("nzf", self._znames)):
+            for side in (0, 1):
+                seen[side] += [n for n in names[key][side] if n not in seen[side]]
+        if self.nzf is not None:
+            self._zcount += B * (T - begin)
+        self._recorded = True
+        return B, T, begin, years, index, names
+
+    # ---- the torch path -----------------------------------------------------------------------------------------------
+    def record_torch(self, gen, tgt, i_time_start, time=None):
+        B, T, begin, years, index, names = self._prepare(gen, tgt, i_time_start, time)
+        for side, d in enumerate((gen, tgt)):
+            if names["trend"][side]:                                          # trend.py:104-147
+                dev = d[names["trend"][side][0]].device
+                t = torch.tensor(years[:, begin:], dtype=torch.float64, device=dev)[:, :, None, None]
+                for n in names["trend"][side]:
+                    y = d[n][:, begin:].to(torch.float64)
+                    cy, cty = y.sum(dim=(0, 1)), (t * y).sum(dim=(0, 1))
+                    sy, sty = self._t_sum_y[side], self._t_sum_ty[side]
+                    sy[n], sty[n] = (sy[n] + cy, sty[n] + cty) if n in sy else (cy, cty)
+            for b in range(B if names["enso"][side] else 0):                  # enso_coefficient.py:136-168
+                if not self._valid[b]:
+                    continue
+                first = d[names["enso"][side][0]]
+                w = index[b].to(device=first.device, dtype=torch.float32)
+                if side == 0:
+                    self._t_ivar[b] = self._t_ivar.get(b, torch.tensor(0.0, dtype=torch.float32, device=first.device)) + (w ** 2).sum()
+                cov = self._t_cov[side].setdefault(b, {})
+                for n in names["enso"][side]:
+                    c = (d[n][b] * w.view(T, 1, 1)).sum(dim=0)                # data_index_covariance, enso_coefficient.py:418-437
+                    cov[n] = cov[n] + c if n in cov else c
+            for n in names["nzf"][side]:                                      # near_zero_fraction.py:147-186
+                x = d[n][:, begin:]
+                below = (x <= torch.tensor(self._eps_for(n), dtype=torch.float32, device=x.device)).to(x.dtype)
+                frac = _wmean(below, self._agg.weights_for(n, x.device).to(x.dtype))
+                acc = self._t_frac[side]
+                acc[n] = acc.get(n, frac.new_zeros(())) + frac.sum()
+                if self.nzf.include_maps:
+                    cells = below.sum(dim=1).sum(dim=0)
+                    self._t_cells[side][n] = self._t_cells[side][n] + cells if n in self._t_cells[side] else cells
+
+    # ---- the fused path -----------------------------------------------------------------------------------------------
+    def record_fused(self, gen, tgt, i_time_start, time=None) -> int:
+        """one ``ace_diag_regress_window`` for all the metrics that are on, both sides and all names (fields with contiguous
+        planes); returns the launches made"""
+        import numpy as np
+        from . import _lib
+        B, T, begin, years, index, names = self._prepare(gen, tgt, i_time_start, time)
+        agg = self._agg
+        first = next(iter(gen.values()))
+        dev, (H, W) = first.device, first.shape[-2:]
+        HW = H * W
+        base_e = 2 if self.trend is not None else 0
+        nmaps = base_e + (B if self.enso is not None else 0)
+        if nmaps > MAX_REGRESS_MAPS:
+            raise ValueError(f"the fused trend / enso_coefficient pass keeps 2 + samples maps per pixel in registers, at most "
+                             f"{MAX_REGRESS_MAPS}: {B} samples with the ENSO coefficient on need {nmaps}; record fewer samples per "
+                             "window or take the torch path (fused = False)")
+        if self._maps is not None and nmaps != self._nmaps:
+            raise ValueError("the number of samples changed between windows")
+        planes = [n for n in gen if any(n in names[k][s] for k in names for s in (0, 1))]
+        new = [n for n in planes if n not in self._rows]
+        if new or self._maps is None:
+            for n in new:
+                self._rows[n] = len(self._rows)
+            R = max(1, len(self._rows))
+
+            def grow(buf, shape, dtype):
+                fresh = torch.zeros(shape, dtype=dtype, device=dev)
+                if buf is not None:
+                    fresh[tuple(slice(0, k) for k in buf.shape)] = buf
+                return fresh
+            self._nmaps = nmaps
+            self._maps = grow(self._maps, (2, R, max(1, nmaps), HW), torch.float64)
+            self._count = grow(self._count, (2, R, HW), torch.int64)
+            self._frac = grow(self._frac, (2, R), torch.float64)
+        if not planes:
+            return 0
+        n = len(planes)
+        wrows = agg._weight_rows(planes, dev)
+        ptrs = [gen[nm].data_ptr() for nm in planes]
+        for nm in planes:
+            ptrs += [gen[nm].stride(0), gen[nm].stride(1)]
+        ptrs += [tgt[nm].data_ptr() if nm in tgt else 0 for nm in planes]
+        for nm in planes:
+            ptrs += [tgt[nm].stride(0), tgt[nm].stride(1)] if nm in tgt else [0, 0]
+        # a plane takes part in every term of the call; what a metric's variable filter excludes is left out at get_* time
+        calls = []
+        if self.trend is not None or self.nzf is not None or (self.enso is not None and begin == 0):
+            calls.append((begin, self.trend is not None, self.enso is not None and begin == 0, self.nzf is not None))
+        if self.enso is not None and begin == 1:
+            calls.append((0, False, True, False))
+        lib = _lib.lib()
+        made = 0
+        for t_begin, do_trend, do_enso, do_nzf in calls:
+            coef, slot = [], []
+            if do_trend:
+                coef += [np.ones((B, T)), years]
+                slot += [[0] * B, [1] * B]
+            if do_enso:
+                coef.append(index.double().numpy())
+                slot.append([base_e + b if self._valid[b] else -1 for b in range(B)])
+            nterms = len(coef)
+            eps = [self._eps_for(nm) if nm in self.nzf.variables else math.nan for nm in planes] if do_nzf else []
+            blob = np.concatenate([np.asarray(ptrs, np.int64).view(np.uint8),
+                                   np.asarray(coef, np.float64).reshape(-1).view(np.uint8),
+                                   np.asarray([self._rows[nm] for nm in planes], np.int32).view(np.uint8),
+                                   np.asarray(slot, np.int32).reshape(-1).view(np.uint8),
+                                   np.asarray(eps, np.float32).view(np.uint8)])
+            table = torch.from_numpy(blob).pin_memory().to(dev, non_blocking=True)
+            base = table.data_ptr()
+            p_coef = base + 48 * n
+            p_rows = p_coef + 8 * nterms * B * T
+            p_slot = p_rows + 4 * n
+            p_eps = p_slot + 4 * nterms * B
+            partial = None
+            if do_nzf:
+                partial = torch.empty(int(lib.ace_diag_regress_partial_doubles(n, B, T, HW)), dtype=torch.float64, device=dev)
+            with torch.cuda.device(dev):
+                _check(lib.ace_diag_regress_window(
+                    base, base + 8 * n, base + 24 * n, base + 32 * n, p_rows, p_coef if nterms else None,
+                    p_slot if nterms else None, self._maps.data_ptr() if nterms else None, p_eps if do_nzf else None,
+                    wrows.data_ptr(), agg._wplanes.data_ptr(), agg._wplanes.shape[0], partial.data_ptr() if do_nzf else None,
+                    self._count.data_ptr(), self._frac.data_ptr(), self._maps.shape[1], nterms, nmaps if nterms else 0, t_begin, n,
+                    B, T, HW, _lib.current_stream()))
+            made += 1
+        return made
+
+    # ---- results ------------------------------------------------------------------------------------------------------
+    def _fused(self) -> bool:
+        return self._maps is not None
+
+    def _trends(self) -> Dict[str, List[Optional[torch.Tensor]]]:
+        """trend.py:163-194: name -> [target, prediction] fp64 (H, W) slopes (None for a side the name was not recorded on)"""
+        n, st, stt = self._n, self._sum_t, self._sum_tt
+        denom = n * stt - st * st
+        out: Dict[str, List[Optional[torch.Tensor]]] = {}
+        for side, slot in ((1, 0), (0, 1)):
+            for name in sorted(self._tnames[side]):
+                if self._fused():
+                    sy, sty = self._maps[side, self._rows[name], 0], self._maps[side, self._rows[name], 1]
+                else:
+                    sy, sty = self._t_sum_y[side][name], self._t_sum_ty[side][name]
+                slope = self._agg._reduce_mean(((n * sty - st * sy) / denom).reshape(self._agg._shape))
+                out.setdefault(name, [None, None])[slot] = slope
+        return {k: v for k, v in out.items() if v[1] is not None}
+
+    def _coefficients(self) -> Dict[str, List[Optional[torch.Tensor]]]:
+        """enso_coefficient.py:170-244: name -> [target, prediction] (H, W) coefficients, the mean over the samples that have a
+        series of covariance / sum of index^2; fp32 on the torch path, fp64 on the fused path"""
+        out: Dict[str, List[Optional[torch.Tensor]]] = {}
+        samples = [b for b, ok in enumerate(self._valid) if ok]
+        base_e = 2 if self.trend is not None else 0
+        for side, slot in ((1, 0), (0, 1)):
+            for name in sorted(self._enames[side]):
+                if self._fused():
+                    per = [self._maps[side, self._rows[name], base_e + b] / self._ivar64[b] for b in samples]
+                else:
+                    per = [self._t_cov[side][b][name] / self._t_ivar[b] for b in samples if name in self._t_cov[side].get(b, {})]
+                if per:
+                    c = torch.stack(per, dim=0).mean(dim=0).reshape(self._agg._shape)
+                    out.setdefault(name, [None, None])[slot] = self._agg._reduce_mean(c)
+        return {k: v for k, v in out.items() if v[1] is not None}
+
+    def _fractions(self):
+        """near_zero_fraction.py:209-225: name -> [gen, target] scalar fractions and, with include_maps, per-cell fraction maps"""
+        fr: Dict[str, List[Optional[float]]] = {}
+        maps: Dict[str, List[Optional[torch.Tensor]]] = {}
+        for side in (0, 1):
+            for name in sorted(self._znames[side]):
+                if self._fused():
+                    f = self._frac[side, self._rows[name]] / self._zcount
+                    cells = self._count[side, self._rows[name]].to(torch.float32)
+                else:
+                    f = self._t_frac[side][name] / self._zcount
+                    cells = self._t_cells[side].get(name)
+                fr.setdefault(name, [None, None])[side] = float(self._agg._reduce_mean(f))
+                if self.nzf.include_maps:
+                    maps.setdefault(name, [None, None])[side] = self._agg._reduce_mean((cells / self._zcount).reshape(self._agg._shape))
+        return fr, maps
+
+    def _rmse(self, name, gen_map, target_map) -> float:
+        w = self._agg.weights_for(name, gen_map.device).to(gen_map.dtype)
+        return float(_wmean(torch.square(gen_map - target_map), w).sqrt())
+
+    def dataset(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        """label -> variables.  trend (trend.py:252-276) and enso_coefficient (enso_coefficient.py:308-329): ``<name>`` (2, H, W), the
+        leading axis source = [target, prediction], NaN where a name has no target; near_zero_fraction with include_maps
+        (near_zero_fraction.py:284-300): ``gen_map-<name>``, ``target_map-<name>``, ``error_map-<name>``."""
+        ds: Dict[str, Dict[str, torch.Tensor]] = {}
+        if not self._recorded:
+            return ds
+        pair = lambda t, g: torch.stack([torch.full_like(g, math.nan) if t is None else t, g]).cpu()      # noqa: E731
+        if self.trend is not None and self._n > 0:
+            ds[self.trend.name or "trend"] = {n: pair(t, g) for n, (t, g) in self._trends().items()}
+        if self.enso is not None:
+            ds[self.enso.name or "enso_coefficient"] = {n: pair(t, g) for n, (t, g) in self._coefficients().items()}
+        if self.nzf is not None and self._zcount > 0:
+            d = ds[self.nzf.name or "near_zero_fraction"] = {}
+            for n, (g, t) in self._fractions()[1].items():
+                if g is None:
+                    continue
+                d[f"gen_map-{n}"] = g.cpu()
+                if t is not None:
+                    d[f"target_map-{n}"] = t.cpu()
+                    d[f"error_map-{n}"] = (g - t).cpu()
+        return ds
+
+    def logs(self) -> Dict[str, Any]:
+        """trend.py:204-239, enso_coefficient.py:246-306 and near_zero_fraction.py:269-282 with tensors where the reference logs
+        images: ``<label>/maps/<name>`` (2, H, W) [target, generated] and ``<label>/difference_map/<name>``,
+        ``<label>/weighted_rmse/<name>`` from the fp32 casts; ``<label>/coefficient_maps/<name>``,
+        ``<label>/coefficient_difference_map/<name>``, ``<label>/rmse/<name>``; ``<label>/gen/<name>``,
+        ``<label>/gen_minus_target/<name>`` and with include_maps ``<label>/gen_target_map/<name>`` (2, H, W) [generated, target],
+        ``<label>/error_map/<name>`` (``<label>/gen_map/<name>`` for a name without a target)."""
+        logs: Dict[str, Any] = {}
+        if not self._recorded:
+            return logs
+        if self.trend is not None and self._n > 0:
+            label = self.trend.name or "trend"
+            for n, (t, g) in self._trends().items():
+                if t is None:
+                    continue
+                logs[f"{label}/maps/{n}"] = torch.stack([t, g]).cpu()
+                logs[f"{label}/difference_map/{n}"] = (g - t).cpu()
+                logs[f"{label}/weighted_rmse/{n}"] = self._rmse(n, g.to(torch.float32), t.to(torch.float32))
+        if self.enso is not None:
+            label = self.enso.name or "enso_coefficient"
+            for n, (t, g) in self._coefficients().items():
+                if t is None:
+                    continue
+                logs[f"{label}/coefficient_maps/{n}"] = torch.stack([t, g]).cpu()
+                logs[f"{label}/coefficient_difference_map/{n}"] = (g - t).cpu()
+                logs[f"{label}/rmse/{n}"] = self._rmse(n, g, t)
+        if self.nzf is not None and self._zcount > 0:
+            label = self.nzf.name or "near_zero_fraction"
+            fr, maps = self._fractions()
+            for n, (g, t) in fr.items():
+                if g is None:
+                    continue
+                logs[f"{label}/gen/{n}"] = g
+                if t is not None:
+                    logs[f"{label}/gen_minus_target/{n}"] = g - t
+            for n, (g, t) in maps.items():
+                if g is None:
+                    continue
+                if t is None:
+                    logs[f"{label}/gen_map/{n}"] = g.cpu()
+                else:
+                    logs[f"{label}/gen_target_map/{n}"] = torch.stack([g, t]).cpu()
+                    logs[f"{label}/error_map/{n}"] = (g - t).cpu()
+        return logs
+
+
 class InferenceEvaluatorAggregator(InferenceAggregator):
     """main.py:526-732 for the sub-aggregators of the module docstring.  Weights, masks, routing and the SHT are the parent's."""
 
     def __init__(self, dataset_info, n_ic_steps: int, n_forward_steps: int, normalize, labels: Optional[Mapping[str, str]] = None,
                  skipped: Sequence[str] = (), zonal_mean_max_size: int = 4096, channel_mean_names: Optional[Sequence[str]] = None,
                  report_directional_bias: bool = True, output_dir: Optional[str] = None, save_diagnostics: bool = False,
-                 sht_factory=None, spectrum_chunk_bytes: int = 256 << 20, histogram: Optional[HistogramMetricConfig] = None):
+                 sht_factory=None, spectrum_chunk_bytes: int = 256 << 20, histogram: Optional[HistogramMetricConfig] = None,
+                 trend: Optional[TrendMetricConfig] = None, enso_coefficient: Optional[EnsoCoefficientMetricConfig] = None,
+                 near_zero_fraction: Optional[NearZeroFractionMetricConfig] = None):
         super().__init__(dataset_info, n_ic_steps + n_forward_steps, True, output_dir, save_diagnostics, sht_factory,
                          spectrum_chunk_bytes)
         self._hist = None if histogram is None or not histogram.enabled else _Histograms(histogram)
+        on = [None if m is None or not m.enabled else m for m in (trend, enso_coefficient, near_zero_fraction)]
+        self._regress = _Regress(self, *on) if any(m is not None for m in on) else None
         self.n_ic_steps = int(n_ic_steps)
         self.skipped = list(skipped)
         default = InferenceEvaluatorAggregatorConfig.BUILT.values()
@@ -448,9 +870,15 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
 
     def launches(self) -> int:
         """Native launches made so far: one ``ace_diag_paired_window`` per window, one ``ace_diag_hist_window`` per window of
-        ``record_batch`` when the histogram is on, and per spectrum chunk of either side one forward SHT and one
-        ``ace_diag_spectrum``."""
+        ``record_batch`` when the histogram is on, one ``ace_diag_regress_window`` per window of ``record_batch`` when any of
+        trend, enso_coefficient and near_zero_fraction is on (a second one for the ENSO term of a window at time index 0), and
+        per spectrum chunk of either side one forward SHT and one ``ace_diag_spectrum``."""
         return self._launches
+
+    @property
+    def needs_time(self) -> bool:
+        """True when ``record_batch`` needs the window's time axis (the trend metric regresses against it)."""
+        return self._regress is not None and self._regress.needs_time
 
     def _pick_pair(self, prediction, target) -> str:
         path = self.route(prediction, target)
@@ -482,19 +910,26 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         return []
 
     @torch.no_grad()
-    def record_batch(self, prediction: TensorMapping, target: TensorMapping):
-        """main.py:579-627: a paired window, each name -> (B, T, H, W), at time index ``i_time_start`` = the steps seen so far.
-        Returns no per-step logs and does not synchronise."""
+    def record_batch(self, prediction: TensorMapping, target: TensorMapping, time=None):
+        """main.py:579-627: a paired window, each name -> (B, T, H, W), at time index ``i_time_start`` = the steps seen so far;
+        ``time``: the ``TimeAxis`` (B, T) of the window's steps, needed when ``needs_time``.  Returns no per-step logs and does not
+        synchronise."""
         if len(prediction) == 0:
             raise ValueError("No prediction values in data")
         if len(target) == 0:
             raise ValueError("No target values in data")
         n = next(iter(prediction.values())).shape[1]
-        self._record_pair(dict(prediction), dict(target), self._n_seen, with_maps=True)
+        if self.needs_time:
+            if time is None:
+                raise ValueError("the trend metric needs the window's time axis: record_batch(prediction, target, time=...)")
+            from .timeaxis import as_time_axis
+            time = as_time_axis(time)
+        self._record_pair(dict(prediction), dict(target), self._n_seen, with_maps=True, time=time)
         self._n_seen += n
         return []
 
-    def _record_pair(self, gen: Dict[str, torch.Tensor], tgt: Dict[str, torch.Tensor], i_time_start: int, with_maps: bool):
+    def _record_pair(self, gen: Dict[str, torch.Tensor], tgt: Dict[str, torch.Tensor], i_time_start: int, with_maps: bool,
+                     time=None):
         first = next(iter(gen.values()))
         B, T = first.shape[:2]
         if i_time_start + T > self._n_time:
@@ -515,9 +950,9 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         if zonal and self._zon_first is None:
             self._zon_first = i_time_start
         if path == "fused":
-            self._record_fused_pair(gen, tgt, i_time_start, with_maps, ignore_initial)
+            self._record_fused_pair(gen, tgt, i_time_start, with_maps, ignore_initial, time)
         else:
-            self._record_torch_pair(gen, tgt, i_time_start, with_maps, ignore_initial)
+            self._record_torch_pair(gen, tgt, i_time_start, with_maps, ignore_initial, time)
         for n in gen:
             if n not in self._series_names:
                 self._series_names.append(n)
@@ -547,11 +982,13 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
                         self._spec_side_counts[side][n] = self._spec_side_counts[side].get(n, 0) + B * T
 
     # ---- the torch path -------------------------------------------------------------------------------------------------------
-    def _record_torch_pair(self, gen, tgt, i_time_start, with_maps, ignore_initial):
+    def _record_torch_pair(self, gen, tgt, i_time_start, with_maps, ignore_initial, time=None):
         T = next(iter(gen.values())).shape[1]
         sl = slice(i_time_start, i_time_start + T)
         if with_maps and self._hist is not None:
             self._hist.record_torch(gen, tgt)
+        if with_maps and self._regress is not None:
+            self._regress.record_torch(gen, tgt, i_time_start, time)
         kinds = {"denorm": (gen, tgt)}
         if self._need_norm:
             kinds["norm"] = (self._normalize_fn(gen), self._normalize_fn(tgt))            # main.py:594-598
@@ -628,7 +1065,7 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         self._zon = grow(self._zon, (2, R, self._n_slots if "zonal_mean" in self._labels else 1, H))
         self._tables.clear()
 
-    def _record_fused_pair(self, gen, tgt, i_time_start, with_maps, ignore_initial):
+    def _record_fused_pair(self, gen, tgt, i_time_start, with_maps, ignore_initial, time=None):
         from . import _lib
         first = next(iter(gen.values()))
         dev = first.device
@@ -667,6 +1104,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
             self._launches += 1
             if with_maps and self._hist is not None:
                 self._launches += self._hist.record_fused(gen, tgt)
+            if with_maps and self._regress is not None:
+                self._launches += self._regress.record_fused(gen, tgt, i_time_start, time)
             if not with_maps or "power_spectrum" not in self._labels:
                 return
             sht = self._get_sht()
@@ -840,6 +1279,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
                 d[f"error-{n}"] = (z[0] - z[1]).cpu()
         if self._hist is not None and self._hist.recorded:
             ds[self._hist.label] = self._hist.dataset()
+        if self._regress is not None:
+            ds.update(self._regress.dataset())
         return ds
 
     @torch.no_grad()
@@ -866,6 +1307,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
                 logs[f"{L['zonal_mean']}/error/{n}"] = (z[0] - z[1]).cpu()
         if self._hist is not None and self._hist.recorded:
             logs.update({f"{self._hist.label}/{k}": v for k, v in self._hist.logs().items()})
+        if self._regress is not None:
+            logs.update(self._regress.logs())
         key = L.get("time_mean_norm")
         return InferenceSummary(logs=logs, loss=logs.get(f"{key}/rmse/channel_mean") if key else None)
 

@@ -227,7 +227,12 @@ def run_evaluator(predict: Callable, data: InferenceData, aggregator, writer=Non
         if derive_target is not None:
             target.update({k: v[:, 1:] for k, v in derive_target(win, list(target)).items() if k in out})
         writer.append_batch(batch=out)
-        logs = aggregator.record_batch(prediction=out, target=target)
+        if getattr(aggregator, "needs_time", False):      # the trend metric regresses against the times of the window's steps
+            if getattr(win, "time", None) is None:
+                raise ValueError("this aggregator needs the windows' time axis: build the ForcingWindows with time=")
+            logs = aggregator.record_batch(prediction=out, target=target, time=win.time[:, 1:])
+        else:
+            logs = aggregator.record_batch(prediction=out, target=target)
         if record_logs is not None:
             record_logs(logs)
     writer.write(state, "restart.nc")

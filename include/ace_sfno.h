@@ -312,6 +312,39 @@ int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, c
  *                  checked.  n_bins even, 2 <= n_bins <= 1024; batch * steps <= 2^21; nplanes == 0 is a no-op.  Counts are
  *                  integers added with integer atomics: bitwise repeatable.  Three launches, no allocation, no host
  *                  synchronisation.  Planes may start at any 4-byte boundary.
+ *   diag_regress_window: the evaluator's per-pixel sums over time - the regression sums of the trend and ENSO-coefficient metrics
+ *                  and the near-zero counts (fme/ace/aggregator/inference/trend.py:104-147, enso/enso_coefficient.py:118-168 and
+ *                  418-437, near_zero_fraction.py:147-186) - for both sides and all names of a window from one read of every
+ *                  plane, in place of the reference's torch reductions per name (and, for the ENSO covariance, per sample).
+ *                  gen / target / strides / rows: as diag_paired_window, planes of hw contiguous fp32 starting at any 4-byte
+ *                  boundary; side 0 = generated, 1 = target; target[j] may be NULL: then only the generated side of plane j is
+ *                  produced.  A plane whose rows[j] is out of range contributes to nothing.  rows must not name one row twice
+ *                  (the += below are not atomic); this is not checked.  Only steps t >= t_begin enter anything (t_begin >= steps:
+ *                  nothing changes); nplanes == 0 is a no-op.
+ *                  Linear terms.  coef: DEVICE fp64 [nterms][batch][steps]; slot: DEVICE int [nterms][batch], the output map of
+ *                  (term k, sample b) in [0, nmaps), any other value (-1) for none; maps: DEVICE fp64 [2][nrows][nmaps][hw].
+ *                  For each side, plane j, map m and pixel p:  acc = 0;  for k ascending, for b ascending over the samples with
+ *                  slot[k][b] == m, for t ascending from t_begin:  acc += coef[k][b][t] * (double)x[b][t][p];  then
+ *                  maps[side][rows[j]][m][p] += acc.  The multiply-add is NOT contracted: the fp64 product is rounded, then
+ *                  added (no fma), so a host statement in plain fp64 arithmetic reproduces it.  NaN and infinity propagate
+ *                  (0 * NaN is NaN).  Every plane is read once, in (b, t) order, so the stated order holds when each map is fed
+ *                  by one term; maps fed by several terms are not supported (two terms on one map interleave per (b, t); not
+ *                  checked).  0 <= nmaps <= ACE_DIAG_REGRESS_MAX_MAPS = 8: a thread holds the accumulators of its pixels in
+ *                  registers; more maps are refused and belong in several calls over map subsets.  nterms == 0 is allowed (maps,
+ *                  coef and slot may then be NULL and no map changes); nterms <= 64.
+ *                  Indicator part, on when eps is not NULL.  eps: DEVICE fp32 [nplanes]; below = x[b][t][p] <= eps[j], compared in
+ *                  fp32, NaN counting as not below.  below_count: DEVICE int64 [2][nrows][hw], [side][rows[j]][p] += the number of
+ *                  (b, t >= t_begin) with below, every pixel whatever its weight.  below_frac: DEVICE fp64 [2][nrows],
+ *                  [side][rows[j]] += f, where f = 0, then for b ascending, t ascending from t_begin:
+ *                  f += (sum over p of w[p] below) / (sum over p of w[p]), w = row wrows[j] of weights (DEVICE fp32 [nw][hw], as
+ *                  diag_window); a pixel of weight 0 enters neither sum (all weights 0: NaN, the reference's 0 / 0).  Both sums
+ *                  over pixels are fp64, taken per wave of 256 pixels (4 consecutive pixels per lane, then an xor butterfly), the
+ *                  per-wave partials through scratch to a second stage that adds them in a fixed order: no float atomics.  A
+ *                  plane whose wrows[j] is out of range takes no part in the indicator outputs (its linear terms are still
+ *                  produced).  partial: DEVICE fp64 scratch of ace_diag_regress_partial_doubles(nplanes, batch, steps, hw) values
+ *                  (-1 for arguments this call would refuse); needed with the indicator only.  The counts are integers, each
+ *                  pixel owned by one thread: bitwise repeatable, as are the maps and fractions.  batch * steps < 2^31.
+ *                  One launch, two with the indicator, however many planes; no allocation, no host synchronisation.
  * ------------------------------------------------------------------------------------------ */
 const char* ace_diag_last_error(void);
 long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
@@ -329,6 +362,12 @@ long ace_diag_hist_scratch_bytes(int nplanes, int batch, int steps, long hw);
 int ace_diag_hist_window(const float* const* gen, const long* gen_strides, const float* const* target, const long* target_strides,
                          const int* rows, const unsigned char* const* masks, void* scratch, double* range, long long* counts,
                          int* dropped, int nrows, int n_bins, int nplanes, int batch, int steps, long hw, void* stream);
+#define ACE_DIAG_REGRESS_MAX_MAPS 8
+long ace_diag_regress_partial_doubles(int nplanes, int batch, int steps, long hw);
+int ace_diag_regress_window(const float* const* gen, const long* gen_strides, const float* const* target, const long* target_strides,
+                            const int* rows, const double* coef, const int* slot, double* maps, const float* eps, const int* wrows,
+                            const float* weights, int nw, double* partial, long long* below_count, double* below_frac, int nrows,
+                            int nterms, int nmaps, int t_begin, int nplanes, int batch, int steps, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
