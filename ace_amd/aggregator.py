@@ -286,15 +286,9 @@ class InferenceAggregator:
             self._rows[n] = len(self._rows)
         R, HW = len(self._rows), self._shape[0] * self._shape[1]
         lmax = self._get_sht().lmax
-
-        def grow(buf, shape):
-            fresh = torch.zeros(shape, dtype=torch.float64, device=dev)
-            if buf is not None:
-                fresh[tuple(slice(0, s) for s in buf.shape)] = buf
-            return fresh
-        self._series = grow(self._series, (2, R, self._n_time))
-        self._tsum = grow(self._tsum, (R, HW))
-        self._spec = grow(self._spec, (R, lmax))
+        self._series = _grow(self._series, (2, R, self._n_time), torch.float64, dev)
+        self._tsum = _grow(self._tsum, (R, HW), torch.float64, dev)
+        self._spec = _grow(self._spec, (R, lmax), torch.float64, dev)
         self._tables.clear()
 
     def _weight_rows(self, names, dev) -> torch.Tensor:
@@ -325,27 +319,24 @@ class InferenceAggregator:
         dev = first.device
         B, T, H, W = first.shape
         HW = H * W
-        # rows of a plane must be contiguous for the pointer table; anything else is made so
-        data = {n: (x if x.stride(-1) == 1 and x.stride(-2) == W else x.contiguous()) for n, x in data.items()}
+        data = {n: _flat(x, W) for n, x in data.items()}
         names = list(data)
         self._ensure_rows(names, dev)
         wrows = self._weight_rows(names, dev)
         rows = self._row_table(names, dev)
-        table = [x.data_ptr() for x in data.values()]
-        for x in data.values():
-            table += [x.stride(0), x.stride(1)]
-        table = _upload(table, torch.int64, dev)
+        values, off = _plane_table(names, data)
+        table = _upload(values, torch.int64, dev)
         n = len(names)
-        partial = torch.empty(int(_lib.lib().ace_diag_partial_doubles(n, B, T, HW)), dtype=torch.float64, device=dev)
-        base = table.data_ptr()
         lib = _lib.lib()
+        partial = torch.empty(int(lib.ace_diag_partial_doubles(n, B, T, HW)), dtype=torch.float64, device=dev)
+        at = {k: table.data_ptr() + o for k, o in off.items()}
         # without the time series the window's series go to scratch (the kernel computes them with the same loads)
         series, n_time, t0 = self._series, self._n_time, i_time_start
         if not self._log_series:
             series, n_time, t0 = torch.empty(2, len(self._rows), T, dtype=torch.float64, device=dev), T, 0
         with torch.cuda.device(dev):
             stream = _lib.current_stream()
-            _check(lib.ace_diag_window(base, base + 8 * n, rows.data_ptr(), wrows.data_ptr(), self._wplanes.data_ptr(),
+            _check(lib.ace_diag_window(at["gen"], at["gen_strides"], rows.data_ptr(), wrows.data_ptr(), self._wplanes.data_ptr(),
                                        self._wplanes.shape[0], partial.data_ptr(), self._tsum.data_ptr(), series.data_ptr(),
                                        len(self._rows), n_time, t0, 1 if ignore_initial else 0, 1 if with_maps else 0, n, B, T,
                                        HW, stream))
@@ -477,6 +468,37 @@ def _upload(values: List[int], dtype, dev) -> torch.Tensor:
     """A small host table to ``dev`` from pinned memory without synchronising the host."""
     host = torch.tensor(values, dtype=dtype).pin_memory()
     return host.to(dev, non_blocking=True)
+
+
+def _flat(x: torch.Tensor, W: int) -> torch.Tensor:
+    """The planes of a field must be contiguous for the pointer table; anything else is made so."""
+    return x if x.stride(-1) == 1 and x.stride(-2) == W else x.contiguous()
+
+
+def _grow(buf: Optional[torch.Tensor], shape, dtype, dev) -> torch.Tensor:
+    """A zeroed accumulator of ``shape`` with the old one (``None``: none yet) in its leading corner."""
+    fresh = torch.zeros(shape, dtype=dtype, device=dev)
+    if buf is not None:
+        fresh[tuple(slice(0, s) for s in buf.shape)] = buf
+    return fresh
+
+
+def _plane_table(names: Sequence[str], gen: TensorMapping, target: Optional[TensorMapping] = None):
+    """The int64 table through which the diag kernels read a window's (B, T, H, W) fields in place, and the byte offsets of its
+    sections.  Per side (``gen``, then ``target`` when given) one pointer per name, then one (stride(0), stride(1)) pair per name; a
+    name ``target`` lacks has pointer 0 and strides 0, 0.  Offsets: ``gen``, ``gen_strides``, with a target ``target`` and
+    ``target_strides``, and ``end``, where a caller appends sections of its own.  Uploading is the caller's (``_upload``)."""
+    values: List[int] = []
+    off: Dict[str, int] = {}
+    for side, d in (("gen", gen),) if target is None else (("gen", gen), ("target", target)):
+        fields = [d[n] if side == "gen" else d.get(n) for n in names]
+        off[side] = 8 * len(values)
+        values += [0 if x is None else x.data_ptr() for x in fields]
+        off[side + "_strides"] = 8 * len(values)
+        for x in fields:
+            values += (0, 0) if x is None else x.stride()[:2]
+    off["end"] = 8 * len(values)
+    return values, off
 
 
 def _check(rc: int) -> None:

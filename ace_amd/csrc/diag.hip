@@ -15,34 +15,18 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
 #include <string>
 
-#include "../../include/ace_sfno.h"
+#include "diag_common.h"
 
 static thread_local std::string g_derr;
 static int dfail(int code, const std::string& m) { g_derr = m; return code; }
 extern "C" const char* ace_diag_last_error(void) { return g_derr.c_str(); }
-int ace_diag_fail_(int code, const std::string& m) { return dfail(code, m); }      // csrc/hist.hip reports through the same string
-#define DIAG_TRY(expr)                                                                                      \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess) return dfail(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
+int ace_diag_fail_(int code, const std::string& m) { return dfail(code, m); }      // hist.hip, regress.hip and DIAG_TRY report here
 
 namespace {
 
-constexpr int NT = 256;              // four wave64s
-constexpr int WAVES = NT / 64;
-constexpr int PIX = 4;               // pixels per thread
-constexpr int CHUNK = NT * PIX;      // pixels per workgroup
 constexpr int NMOM = 3;              // sum of weights, weighted mean, second central moment
-
-__device__ __forceinline__ double wave_sum(double v) {
-    // xor butterfly: every lane ends with the same sum (fp add is commutative)
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // Chan et al.'s parallel update of (weight, mean, M2) with the partial (wb, mb, Mb); empty partials are skipped
 __device__ __forceinline__ void chan(double& w, double& m, double& M, double wb, double mb, double Mb) {
@@ -52,16 +36,6 @@ __device__ __forceinline__ void chan(double& w, double& m, double& M, double wb,
     m += d * (wb / n);
     M += Mb + d * d * (w * wb / n);
     w = n;
-}
-
-__device__ __forceinline__ float4 load4(const float* s, long p, long HW, bool vec) {
-    if (vec && p + 3 < HW) return *reinterpret_cast<const float4*>(s + p);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p < HW) v.x = s[p];
-    if (p + 1 < HW) v.y = s[p + 1];
-    if (p + 2 < HW) v.z = s[p + 2];
-    if (p + 3 < HW) v.w = s[p + 3];
-    return v;
 }
 
 __global__ __launch_bounds__(NT) void diag_window_kernel(const float* const* srcs, const long* __restrict__ strides,
@@ -76,9 +50,9 @@ __global__ __launch_bounds__(NT) void diag_window_kernel(const float* const* src
     const long p = (long)chunk * CHUNK + (long)threadIdx.x * PIX;
     const float* base = srcs[j];
     const long sb = strides[2 * j], st = strides[2 * j + 1];
-    const bool vec = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0 && (sb & 3) == 0 && (st & 3) == 0;
+    const bool vec = DIAG_VEC4_OK(base, HW, sb, st);
     const float* wrow = weights + (long)wr * HW;
-    const float4 w4 = load4(wrow, p, HW, (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(wrow) & 15u) == 0);
+    const float4 w4 = load4(wrow, p, HW, DIAG_VEC4_ROW_OK(wrow, HW));
     const float wv[PIX] = {w4.x, w4.y, w4.z, w4.w};
     double acc[PIX] = {0.0, 0.0, 0.0, 0.0};
     const long nparts = (long)nchunk * WAVES;
@@ -173,8 +147,6 @@ __global__ __launch_bounds__(NT) void diag_spectrum_kernel(const float2* __restr
         spec[(long)r * L + l] += tot;
     }
 }
-
-long nchunk_for(long hw) { return (hw + CHUNK - 1) / CHUNK; }
 
 // ---- the paired pass (inference evaluator) -------------------------------------------------------------------------------------
 //   diag_paired    one pass over the generated and the target (plane j, sample b, step t) fields of a window.  Workgroup (band, j)

@@ -18,41 +18,18 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
 #include <string>
 
-#include "../../include/ace_sfno.h"
-
-int ace_diag_fail_(int code, const std::string& m);      // csrc/diag.hip: the string behind ace_diag_last_error
+#include "diag_common.h"
 
 namespace {
 
-constexpr int NT = 256;              // four wave64s
-constexpr int WAVES = NT / 64;
-constexpr int PIX = 4;               // pixels per thread
-constexpr int CHUNK = NT * PIX;      // pixels per workgroup
 constexpr int MAX_BINS = 1024;
 constexpr int MAX_PLANES_PER_CALL = 1 << 21;    // batch * steps: 1024 pixels of each fit a 32-bit LDS counter
 constexpr int PEEL = 2;              // rounds of wave-level combining before the LDS atomics
 
 struct Partial { float mn, mx; int bad, pad; };       // one per (side, plane, chunk)
 struct BinParam { float lo, bin; int skip, pad; };    // one per (side, plane), after the partials
-
-#define HIST_TRY(expr)                                                                                               \
-    do {                                                                                                             \
-        hipError_t e__ = (expr);                                                                                     \
-        if (e__ != hipSuccess) return ace_diag_fail_(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
-__device__ __forceinline__ float4 load4(const float* s, long p, long HW, bool vec) {
-    if (vec && p + 3 < HW) return *reinterpret_cast<const float4*>(s + p);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p < HW) v.x = s[p];
-    if (p + 1 < HW) v.y = s[p + 1];
-    if (p + 2 < HW) v.z = s[p + 2];
-    if (p + 3 < HW) v.w = s[p + 3];
-    return v;
-}
 
 // which of this thread's four pixels are inside the plane and not masked out
 __device__ __forceinline__ void live_pixels(const unsigned char* mask, long p, long HW, bool live[PIX]) {
@@ -83,7 +60,7 @@ __global__ __launch_bounds__(NT) void hist_range_kernel(HistArgs a) {
     if (base == nullptr || r < 0 || r >= a.nrows) return;
     const long HW = a.HW, p = (long)chunk * CHUNK + (long)threadIdx.x * PIX;
     const long sb = a.strides[side][2 * j], st = a.strides[side][2 * j + 1];
-    const bool vec = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0 && (sb & 3) == 0 && (st & 3) == 0;
+    const bool vec = DIAG_VEC4_OK(base, HW, sb, st);
     bool live[PIX];
     live_pixels(a.masks ? a.masks[j] : nullptr, p, HW, live);
     float mn = INFINITY, mx = -INFINITY;
@@ -204,7 +181,7 @@ __global__ __launch_bounds__(NT) void hist_bin_kernel(HistArgs a) {
     const float* base = a.src[side][j];
     const long HW = a.HW, p = (long)chunk * CHUNK + (long)threadIdx.x * PIX;
     const long sb = a.strides[side][2 * j], st = a.strides[side][2 * j + 1];
-    const bool vec = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0 && (sb & 3) == 0 && (st & 3) == 0;
+    const bool vec = DIAG_VEC4_OK(base, HW, sb, st);
     bool live[PIX];
     live_pixels(a.masks ? a.masks[j] : nullptr, p, HW, live);
     const float flo = prm.lo, fbin = prm.bin, top = (float)nb;
@@ -247,8 +224,6 @@ __global__ __launch_bounds__(NT) void hist_bin_kernel(HistArgs a) {
     }
 }
 
-long nchunk_for(long hw) { return (hw + CHUNK - 1) / CHUNK; }
-
 }  // namespace
 
 extern "C" long ace_diag_hist_scratch_bytes(int nplanes, int batch, int steps, long hw) {
@@ -287,10 +262,10 @@ extern "C" int ace_diag_hist_window(const float* const* gen, const long* gen_str
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)a.nchunk, nplanes, 2);
     hipLaunchKernelGGL(hist_range_kernel, grid, dim3(NT), 0, s, a);
-    HIST_TRY(hipGetLastError());
+    DIAG_TRY(hipGetLastError());
     hipLaunchKernelGGL(hist_update_kernel, dim3(nplanes, 2), dim3(64), 0, s, a);
-    HIST_TRY(hipGetLastError());
+    DIAG_TRY(hipGetLastError());
     hipLaunchKernelGGL(hist_bin_kernel, grid, dim3(NT), (size_t)WAVES * n_bins * sizeof(unsigned int), s, a);
-    HIST_TRY(hipGetLastError());
+    DIAG_TRY(hipGetLastError());
     return ACE_OK;
 }

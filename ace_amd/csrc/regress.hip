@@ -16,43 +16,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
 #include <string>
 
-#include "../../include/ace_sfno.h"
-
-int ace_diag_fail_(int code, const std::string& m);      // csrc/diag.hip: the string behind ace_diag_last_error
+#include "diag_common.h"
 
 namespace {
 
-constexpr int NT = 256;              // four wave64s
-constexpr int WAVES = NT / 64;
-constexpr int PIX = 4;               // pixels per thread
-constexpr int CHUNK = NT * PIX;      // pixels per workgroup
 constexpr int MAX_MAPS = ACE_DIAG_REGRESS_MAX_MAPS;     // 8 maps x 4 pixels x fp64 = 64 VGPRs of accumulators: no spill
 constexpr int MAX_TERMS = 64;
-
-#define REG_TRY(expr)                                                                                                \
-    do {                                                                                                             \
-        hipError_t e__ = (expr);                                                                                     \
-        if (e__ != hipSuccess) return ace_diag_fail_(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
-__device__ __forceinline__ double wave_sum(double v) {
-    // xor butterfly: every lane ends with the same sum (fp add is commutative)
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float4 load4(const float* s, long p, long HW, bool vec) {
-    if (vec && p + 3 < HW) return *reinterpret_cast<const float4*>(s + p);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p < HW) v.x = s[p];
-    if (p + 1 < HW) v.y = s[p + 1];
-    if (p + 2 < HW) v.z = s[p + 2];
-    if (p + 3 < HW) v.w = s[p + 3];
-    return v;
-}
 
 struct RegArgs {
     const float* const* src[2];
@@ -82,7 +53,7 @@ __global__ __launch_bounds__(NT) void regress_window_kernel(RegArgs a) {
     if (base == nullptr || r < 0 || r >= a.nrows) return;
     const long HW = a.HW, p = (long)chunk * CHUNK + (long)threadIdx.x * PIX;
     const long sb = a.strides[side][2 * j], st = a.strides[side][2 * j + 1];
-    const bool vec = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0 && (sb & 3) == 0 && (st & 3) == 0;
+    const bool vec = DIAG_VEC4_OK(base, HW, sb, st);
     const int B = a.B, T = a.T, t_begin = a.t_begin, span = T - t_begin, n = B * span;
     const long nparts = (long)a.nchunk * WAVES, part = (long)chunk * WAVES + wave;
     double acc[NM > 0 ? NM : 1][PIX];
@@ -100,7 +71,7 @@ __global__ __launch_bounds__(NT) void regress_window_kernel(RegArgs a) {
         ind = wr >= 0 && wr < a.nw;
         if (ind) {
             const float* wrow = a.weights + (long)wr * HW;
-            const float4 w4 = load4(wrow, p, HW, (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(wrow) & 15u) == 0);
+            const float4 w4 = load4(wrow, p, HW, DIAG_VEC4_ROW_OK(wrow, HW));
             wv[0] = w4.x; wv[1] = w4.y; wv[2] = w4.z; wv[3] = w4.w;
             eps = a.eps[j];
             q = a.partial + ((long)side * a.nplanes + j) * B * T * nparts + part;
@@ -190,8 +161,6 @@ __global__ __launch_bounds__(64) void regress_frac_kernel(RegArgs a) {
     if (lane == 0) a.below_frac[(long)side * a.nrows + r] += frac;
 }
 
-long nchunk_for(long hw) { return (hw + CHUNK - 1) / CHUNK; }
-
 bool shape_ok(int nplanes, int batch, int steps, long hw) {
     return nplanes >= 0 && nplanes <= 65535 && batch >= 1 && steps >= 1 && (long)batch * steps <= 2147483647L && hw >= 1 &&
            nchunk_for(hw) <= 2147483647L;
@@ -250,10 +219,10 @@ extern "C" int ace_diag_regress_window(const float* const* gen, const long* gen_
     if (a.nmaps == 0) launch<0>(a, ind, grid, s);
     else if (a.nmaps <= 4) launch<4>(a, ind, grid, s);
     else launch<MAX_MAPS>(a, ind, grid, s);
-    REG_TRY(hipGetLastError());
+    DIAG_TRY(hipGetLastError());
     if (ind) {
         hipLaunchKernelGGL(regress_frac_kernel, dim3(nplanes, 2), dim3(64), 0, s, a);
-        REG_TRY(hipGetLastError());
+        DIAG_TRY(hipGetLastError());
     }
     return ACE_OK;
 }

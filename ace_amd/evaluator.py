@@ -56,6 +56,7 @@ accumulator memory: names x 2 x slots x H x 8 bytes (40 names, 4096 slots, 180 l
 ``zonal_mean_max_size`` only coarsens past 4096 steps)."""
 import dataclasses
 import datetime
+import itertools
 import logging
 import math
 import os
@@ -63,7 +64,7 @@ from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence
 
 import torch
 
-from .aggregator import InferenceAggregator, TensorMapping, _check, _is_healpix, _upload
+from .aggregator import InferenceAggregator, TensorMapping, _check, _flat, _grow, _is_healpix, _plane_table, _upload
 
 SERIES = ("weighted_mean_gen", "weighted_std_gen", "weighted_mean_target", "weighted_bias", "weighted_rmse",
           "weighted_grad_mag_percent_diff")                               # the rows of the fused series accumulator
@@ -186,8 +187,9 @@ class InferenceEvaluatorAggregatorConfig:
 
     BUILT = {"mean_denorm": "mean", "mean_norm": "mean_norm", "time_mean_denorm": "time_mean", "time_mean_norm": "time_mean_norm",
              "power_spectrum": "power_spectrum", "zonal_mean": "zonal_mean"}
-    SKIPPED = ("step_means", "ensembles", "annual", "enso_index", "enso_coefficient", "ipo_index")
-    REFUSED = ("video", "histogram", "seasonal", "trend", "near_zero_fraction")
+    NEVER_BUILT = ("video", "seasonal")
+    TYPED = {"histogram": HistogramMetricConfig, "trend": TrendMetricConfig, "near_zero_fraction": NearZeroFractionMetricConfig}
+    SKIPPED = ("step_means", "ensembles", "annual", "enso_index", "ipo_index")      # main.py:143-153, the non-strict path
 
     def build(self, dataset_info, n_ic_steps: int, n_forward_steps: int, normalize, output_dir: Optional[str] = None,
               channel_mean_names: Optional[Sequence[str]] = None, save_diagnostics: bool = False,
@@ -200,15 +202,14 @@ class InferenceEvaluatorAggregatorConfig:
         if self.step_diagnostics not in (None, {}):
             raise NotImplementedError("step_diagnostics: only the default configuration is supported (no step-diagnostics "
                                       "aggregator is built)")
-        for field in self.REFUSED:
+        for field in self.NEVER_BUILT:
             if getattr(self, field).enabled:
+                raise NotImplementedError(f"the {field} metric is not built")
+        for field, typed in self.TYPED.items():
+            if getattr(self, field).enabled and not isinstance(getattr(self, field), typed):
                 if field == "histogram":
-                    if isinstance(self.histogram, HistogramMetricConfig):
-                        continue
                     raise NotImplementedError("the histogram metric is built from its typed configuration only: pass a "
                                               "HistogramMetricConfig, not a bare MetricConfig")
-                if isinstance(getattr(self, field), (TrendMetricConfig, NearZeroFractionMetricConfig)):
-                    continue
                 raise NotImplementedError(f"the {field} metric is not built")
         skipped = []
         trend = self.trend if self.trend.enabled else None
@@ -223,10 +224,13 @@ class InferenceEvaluatorAggregatorConfig:
         elif getattr(dataset_info, "timestep", None) is not None and \
                 (n_ic_steps + n_forward_steps) * dataset_info.timestep <= datetime.timedelta(days=1800):
             enso = None                                                   # enso_coefficient.py:478-483; skipped or raised below
-        for field in self.SKIPPED:
+        unbuilt = list(self.SKIPPED)
+        if enso is None:
+            unbuilt.insert(unbuilt.index("ipo_index"), "enso_coefficient")      # its place in the reference's list
+        for field in unbuilt:
             v = getattr(self, field)
             for m in (v if isinstance(v, list) else [v]):
-                if not m.enabled or m is enso:
+                if not m.enabled:
                     continue
                 if m.strict:
                     raise NotImplementedError(f"the {field} metric is not built (strict=True)")
@@ -412,18 +416,14 @@ class _Histograms:
             self._dropped = torch.zeros(2, n, dtype=torch.int32, device=dev)
             self._mask_planes = torch.stack([self._masks[nm].reshape(H * W) for nm in names]).to(torch.uint8).contiguous()
             self._rows = _upload(list(range(n)), torch.int32, dev)
-        table = []
-        for d in (gen, tgt):
-            table += [d[nm].data_ptr() for nm in names]
-            for nm in names:
-                table += [d[nm].stride(0), d[nm].stride(1)]
-        table += [self._mask_planes.data_ptr() + i * H * W for i in range(n)]
-        table = _upload(table, torch.int64, dev)
+        values, off = _plane_table(names, gen, tgt)
+        values += [self._mask_planes.data_ptr() + i * H * W for i in range(n)]      # the mask pointers, from off["end"]
+        table = _upload(values, torch.int64, dev)
         lib = _lib.lib()
         scratch = torch.empty(int(lib.ace_diag_hist_scratch_bytes(n, B, T, H * W)), dtype=torch.uint8, device=dev)
-        base = table.data_ptr()
-        _check(lib.ace_diag_hist_window(base, base + 8 * n, base + 24 * n, base + 32 * n, self._rows.data_ptr(), base + 48 * n,
-                                        scratch.data_ptr(), self._range.data_ptr(), self._counts.data_ptr(),
+        at = {k: table.data_ptr() + o for k, o in off.items()}
+        _check(lib.ace_diag_hist_window(at["gen"], at["gen_strides"], at["target"], at["target_strides"], self._rows.data_ptr(),
+                                        at["end"], scratch.data_ptr(), self._range.data_ptr(), self._counts.data_ptr(),
                                         self._dropped.data_ptr(), n, HIST_BINS, n, B, T, H * W, _lib.current_stream()))
         return 1
 
@@ -632,26 +632,15 @@ class _Regress:
             for n in new:
                 self._rows[n] = len(self._rows)
             R = max(1, len(self._rows))
-
-            def grow(buf, shape, dtype):
-                fresh = torch.zeros(shape, dtype=dtype, device=dev)
-                if buf is not None:
-                    fresh[tuple(slice(0, k) for k in buf.shape)] = buf
-                return fresh
             self._nmaps = nmaps
-            self._maps = grow(self._maps, (2, R, max(1, nmaps), HW), torch.float64)
-            self._count = grow(self._count, (2, R, HW), torch.int64)
-            self._frac = grow(self._frac, (2, R), torch.float64)
+            self._maps = _grow(self._maps, (2, R, max(1, nmaps), HW), torch.float64, dev)
+            self._count = _grow(self._count, (2, R, HW), torch.int64, dev)
+            self._frac = _grow(self._frac, (2, R), torch.float64, dev)
         if not planes:
             return 0
         n = len(planes)
         wrows = agg._weight_rows(planes, dev)
-        ptrs = [gen[nm].data_ptr() for nm in planes]
-        for nm in planes:
-            ptrs += [gen[nm].stride(0), gen[nm].stride(1)]
-        ptrs += [tgt[nm].data_ptr() if nm in tgt else 0 for nm in planes]
-        for nm in planes:
-            ptrs += [tgt[nm].stride(0), tgt[nm].stride(1)] if nm in tgt else [0, 0]
+        values, off = _plane_table(planes, gen, tgt)
         # a plane takes part in every term of the call; what a metric's variable filter excludes is left out at get_* time
         calls = []
         if self.trend is not None or self.nzf is not None or (self.enso is not None and begin == 0):
@@ -670,23 +659,19 @@ class _Regress:
                 slot.append([base_e + b if self._valid[b] else -1 for b in range(B)])
             nterms = len(coef)
             eps = [self._eps_for(nm) if nm in self.nzf.variables else math.nan for nm in planes] if do_nzf else []
-            blob = np.concatenate([np.asarray(ptrs, np.int64).view(np.uint8),
-                                   np.asarray(coef, np.float64).reshape(-1).view(np.uint8),
-                                   np.asarray([self._rows[nm] for nm in planes], np.int32).view(np.uint8),
-                                   np.asarray(slot, np.int32).reshape(-1).view(np.uint8),
-                                   np.asarray(eps, np.float32).view(np.uint8)])
-            table = torch.from_numpy(blob).pin_memory().to(dev, non_blocking=True)
-            base = table.data_ptr()
-            p_coef = base + 48 * n
-            p_rows = p_coef + 8 * nterms * B * T
-            p_slot = p_rows + 4 * n
-            p_eps = p_slot + 4 * nterms * B
+            # one pinned blob: the plane table, then from off["end"] the coefficients, the rows, the slots and the eps
+            sections = [np.asarray(values, np.int64), np.asarray(coef, np.float64).reshape(-1),
+                        np.asarray([self._rows[nm] for nm in planes], np.int32), np.asarray(slot, np.int32).reshape(-1),
+                        np.asarray(eps, np.float32)]
+            table = torch.from_numpy(np.concatenate([s.view(np.uint8) for s in sections])).pin_memory().to(dev, non_blocking=True)
+            at = {k: table.data_ptr() + o for k, o in off.items()}
+            p_coef, p_rows, p_slot, p_eps, _ = itertools.accumulate([s.nbytes for s in sections[1:]], initial=at["end"])
             partial = None
             if do_nzf:
                 partial = torch.empty(int(lib.ace_diag_regress_partial_doubles(n, B, T, HW)), dtype=torch.float64, device=dev)
             with torch.cuda.device(dev):
                 _check(lib.ace_diag_regress_window(
-                    base, base + 8 * n, base + 24 * n, base + 32 * n, p_rows, p_coef if nterms else None,
+                    at["gen"], at["gen_strides"], at["target"], at["target_strides"], p_rows, p_coef if nterms else None,
                     p_slot if nterms else None, self._maps.data_ptr() if nterms else None, p_eps if do_nzf else None,
                     wrows.data_ptr(), agg._wplanes.data_ptr(), agg._wplanes.shape[0], partial.data_ptr() if do_nzf else None,
                     self._count.data_ptr(), self._frac.data_ptr(), self._maps.shape[1], nterms, nmaps if nterms else 0, t_begin, n,
@@ -1053,16 +1038,10 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
             self._rows[n] = len(self._rows)
         R, (H, W) = len(self._rows), self._shape
         lmax = self._get_sht().lmax if "power_spectrum" in self._labels else 1
-
-        def grow(buf, shape):
-            fresh = torch.zeros(shape, dtype=torch.float64, device=dev)
-            if buf is not None:
-                fresh[tuple(slice(0, s) for s in buf.shape)] = buf
-            return fresh
-        self._series = grow(self._series, (len(SERIES), R, self._n_time))
-        self._tsum = grow(self._tsum, (2, R, H * W))
-        self._spec = grow(self._spec, (2, R, lmax))
-        self._zon = grow(self._zon, (2, R, self._n_slots if "zonal_mean" in self._labels else 1, H))
+        self._series = _grow(self._series, (len(SERIES), R, self._n_time), torch.float64, dev)
+        self._tsum = _grow(self._tsum, (2, R, H * W), torch.float64, dev)
+        self._spec = _grow(self._spec, (2, R, lmax), torch.float64, dev)
+        self._zon = _grow(self._zon, (2, R, self._n_slots if "zonal_mean" in self._labels else 1, H), torch.float64, dev)
         self._tables.clear()
 
     def _record_fused_pair(self, gen, tgt, i_time_start, with_maps, ignore_initial, time=None):
@@ -1070,26 +1049,19 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         first = next(iter(gen.values()))
         dev = first.device
         B, T, H, W = first.shape
-        # the planes of a field must be contiguous for the pointer tables; anything else is made so
-        flat = lambda x: x if x.stride(-1) == 1 and x.stride(-2) == W else x.contiguous()      # noqa: E731
         given = gen
-        gen = {n: flat(x) for n, x in given.items()}
-        tgt = {n: (gen[n] if y is given[n] else flat(y)) for n, y in tgt.items()}
+        gen = {n: _flat(x, W) for n, x in given.items()}
+        tgt = {n: (gen[n] if y is given[n] else _flat(y, W)) for n, y in tgt.items()}
         names = list(gen)
         n = len(names)
         self._ensure_rows(names, dev)
         wrows = self._weight_rows(names, dev)
         rows = self._row_table(names, dev)
-        table = [x.data_ptr() for x in gen.values()]
-        for x in gen.values():
-            table += [x.stride(0), x.stride(1)]
-        table += [tgt[nm].data_ptr() if nm in tgt else 0 for nm in names]
-        for nm in names:
-            table += [tgt[nm].stride(0), tgt[nm].stride(1)] if nm in tgt else [0, 0]
-        table = _upload(table, torch.int64, dev)
+        values, off = _plane_table(names, gen, tgt)
+        table = _upload(values, torch.int64, dev)
         lib = _lib.lib()
         partial = torch.empty(int(lib.ace_diag_paired_partial_doubles(n, B, T, H, W)), dtype=torch.float64, device=dev)
-        base = table.data_ptr()
+        at = {k: table.data_ptr() + o for k, o in off.items()}
         series, n_time, t0 = self._series, self._n_time, i_time_start
         if not self._log_series:
             series, n_time, t0 = torch.empty(len(SERIES), len(self._rows), T, dtype=torch.float64, device=dev), T, 0
@@ -1097,8 +1069,9 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         zt0 = i_time_start - self._zon_first if zonal else 0
         with torch.cuda.device(dev):
             _check(lib.ace_diag_paired_window(
-                base, base + 8 * n, base + 24 * n, base + 32 * n, rows.data_ptr(), wrows.data_ptr(), self._wplanes.data_ptr(),
-                self._wplanes.shape[0], partial.data_ptr(), self._tsum.data_ptr(), self._zon.data_ptr(), series.data_ptr(),
+                at["gen"], at["gen_strides"], at["target"], at["target_strides"], rows.data_ptr(), wrows.data_ptr(),
+                self._wplanes.data_ptr(), self._wplanes.shape[0], partial.data_ptr(), self._tsum.data_ptr(), self._zon.data_ptr(),
+                series.data_ptr(),
                 len(self._rows), n_time, t0, 1 if ignore_initial else 0, 1 if with_maps else 0, zt0,
                 self._factor if zonal else 1, self._zon.shape[2], n, B, T, H, W, _lib.current_stream()))
             self._launches += 1
