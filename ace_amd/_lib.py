@@ -193,6 +193,10 @@ SIGNATURES = {
     # gen, gen_strides, target, target_strides, rows, coef, slot, maps, eps, wrows, weights, nw, partial, below_count, below_frac,
     # nrows, nterms, nmaps, t_begin, nplanes, batch, steps, hw, stream
     "ace_diag_regress_window": (c_int, [c_void_p] * 11 + [c_int] + [c_void_p] * 3 + [c_int] * 7 + [c_long, c_void_p]),
+    "ace_diag_calendar_partial_doubles": (c_long, [c_int, c_int, c_int, c_int, c_long]),
+    # gen, gen_strides, target, target_strides, rows, bin, bins, regions, srow, mode, wrows, weights, nw, partial, series, nrows,
+    # nbins, nreg, nsrows, n_time, t0, t_begin, nplanes, batch, steps, hw, stream
+    "ace_diag_calendar_window": (c_int, [c_void_p] * 12 + [c_int] + [c_void_p] * 2 + [c_int] * 10 + [c_long, c_void_p]),
 }
 
 _lib = None

@@ -227,9 +227,10 @@ def run_evaluator(predict: Callable, data: InferenceData, aggregator, writer=Non
         if derive_target is not None:
             target.update({k: v[:, 1:] for k, v in derive_target(win, list(target)).items() if k in out})
         writer.append_batch(batch=out)
-        if getattr(aggregator, "needs_time", False):      # the trend metric regresses against the times of the window's steps
-            if getattr(win, "time", None) is None:
-                raise ValueError("this aggregator needs the windows' time axis: build the ForcingWindows with time=")
+        needs, has = getattr(aggregator, "needs_time", False), getattr(win, "time", None) is not None
+        if needs and not has:                             # the trend metric regresses against the times of the window's steps
+            raise ValueError("this aggregator needs the windows' time axis: build the ForcingWindows with time=")
+        if needs or (has and getattr(aggregator, "uses_time", False)):      # the calendar metrics take it when there is one
             logs = aggregator.record_batch(prediction=out, target=target, time=win.time[:, 1:])
         else:
             logs = aggregator.record_batch(prediction=out, target=target)

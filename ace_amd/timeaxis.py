@@ -80,6 +80,35 @@ def days_since_base(calendar: str, year, month, day) -> np.ndarray:
     return np.where(after, greg + 2, jul)
 
 
+def date_from_days(calendar: str, days):
+    """The inverse of ``days_since_base``: (year, month, day) int64 arrays of the date `days` whole days after 0001-01-01 of
+    `calendar`."""
+    calendar = canonical_calendar(calendar)
+    n = np.asarray(days, dtype=np.int64)
+    if np.any(n < 0):
+        raise ValueError("years before 1 are not supported")
+    if calendar == "360_day":
+        return n // 360 + 1, (n % 360) // 30 + 1, n % 30 + 1
+    if calendar in ("noleap", "all_leap"):
+        length = 365 if calendar == "noleap" else 366
+        y, in_year = n // length + 1, n % length
+    else:
+        start = lambda year: days_since_base(calendar, year, 1, 1)         # noqa: E731  (1 January exists in every year)
+        y = n // 366 + 1                                                    # never past the year: steps up from below
+        while True:
+            late = start(y + 1) <= n
+            if not late.any():
+                break
+            y = np.where(late, y + np.maximum((n - start(y + 1)) // 366, 0) + 1, y)
+        in_year = n - start(y)
+        if calendar == "standard":                                          # 1582 has no 5 ... 14 October: day 277 is the 15th
+            in_year = in_year + 10 * ((y == 1582) & (in_year > 276))
+    leap = _is_leap(calendar, y, y > 1582)
+    cum = _CUM + (np.arange(12) >= 2) * leap[..., None]                     # days before each month of that year
+    m = (in_year[..., None] >= cum).sum(axis=-1)
+    return y, m, in_year - np.take_along_axis(cum, (m - 1)[..., None], axis=-1)[..., 0] + 1
+
+
 class TimeAxis:
     """calendar + microseconds since that calendar's 0001-01-01T00:00 (int64 array)."""
 
@@ -158,6 +187,11 @@ class TimeAxis:
 
     def microseconds_of_day(self) -> np.ndarray:
         return self.us % US_PER_DAY
+
+    def year_month(self):
+        """(year, month) int64 arrays of the axis' shape: cftime's ``.dt.year`` / ``.dt.month`` in the axis' own calendar."""
+        y, m, _ = date_from_days(self.calendar, self.us // US_PER_DAY)
+        return y, m
 
 
 def _timedelta_us(delta: datetime.timedelta) -> int:

@@ -345,6 +345,47 @@ int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, c
  *                  (-1 for arguments this call would refuse); needed with the indicator only.  The counts are integers, each
  *                  pixel owned by one thread: bitwise repeatable, as are the maps and fractions.  batch * steps < 2^31.
  *                  One launch, two with the indicator, however many planes; no allocation, no host synchronisation.
+ *   diag_calendar_window: the evaluator's calendar metrics - the seasonal sums and the regional series behind the annual means, the
+ *                  Nino 3.4 index and the tripole index (fme/ace/aggregator/inference/seasonal.py:40-69, annual.py:181-208,
+ *                  enso/dynamic_index.py:65-92, ipo/ipo_index.py:43-58 and 109-131) - for both sides and all names of a window from
+ *                  one read of every plane, in place of the reference's copy of every field to the host (seasonal) and its torch
+ *                  reduction and .cpu() per name and region (the others).  gen / target / strides / rows: as diag_regress_window,
+ *                  planes of hw contiguous fp32 starting at any 4-byte boundary; side 0 = generated, 1 = target; target[j] may be
+ *                  NULL: then only the generated side of plane j is produced.  A plane whose rows[j] is out of range [0, nrows)
+ *                  contributes to nothing, binned sums and series alike.  rows must not name one row twice, and no two valid
+ *                  srow entries may be equal (the += and the assignments below are not atomic); this is not checked.  Only steps
+ *                  t >= t_begin enter anything (t_begin >= steps: nothing changes); nplanes == 0 is a no-op.
+ *                  Binned sums, on when bins is not NULL.  bin: DEVICE int [batch][steps], the bin of step (b, t) in [0, nbins),
+ *                  any other value (-1) for none; bins: DEVICE fp64 [2][nrows][nbins][hw].  For each side, plane j, bin m and
+ *                  pixel p:  acc = 0;  for b ascending, for t ascending from t_begin, taking only the steps with bin[b][t] == m:
+ *                  acc += (double)x[b][t][p];  then bins[side][rows[j]][m][p] += acc.  A step is ADDED to its own bin and to no
+ *                  other; nothing is multiplied, so a NaN or an infinity stays in the bin of its step.  (That is why the linear
+ *                  terms of diag_regress_window with 0 / 1 coefficients do not serve: 0 * NaN is NaN, and one NaN step would
+ *                  poison every bin, where the reference's groupby(...).sum(skipna=False) keeps it inside its season.)  A bin no
+ *                  step names adds +0.  0 <= nbins <= ACE_DIAG_CALENDAR_MAX_BINS = 8: a thread holds the sums of its pixels in
+ *                  registers; more bins are refused.  Each pixel is owned by one thread: bitwise repeatable.
+ *                  Regional series, on when series is not NULL.  regions: DEVICE fp32 [nreg][hw]; srow: DEVICE int
+ *                  [nplanes][nreg], the output row of (plane j, region r) in [0, nsrows), any other value (-1) for none; mode:
+ *                  DEVICE int [nreg]; series: DEVICE fp64 [2][nsrows][batch][n_time]; weights / wrows / nw: as diag_window.  For
+ *                  each (side, j, r) with a valid srow and each (b, t >= t_begin):
+ *                  series[side][srow[j][r]][b][t0 + t] = num / den, an assignment, not a +=, with num = sum over p of
+ *                  (double)w[p] * (double)x[b][t][p] (the product of two fp32 values is exact in fp64) and den = sum over p of
+ *                  (double)w[p], over the pixels that take part:
+ *                    mode 0  metrics.weighted_mean as regional_area_weighted_mean uses it (fme/core/gridded_ops.py:361-371):
+ *                            w[p] = regions[r][p] * weights[wrows[j]][p], the product formed in fp32 as the reference multiplies two
+ *                            fp32 tensors (gridded_ops.py:336); a pixel with w == 0 enters neither sum (NaN included), a NaN at a
+ *                            pixel of non-zero weight propagates; all weights zero: NaN, the reference's 0 / 0.
+ *                    mode 1  _nan_aware_regional_mean (ipo/ipo_index.py:43-58), which takes the regional weights alone:
+ *                            w[p] = regions[r][p]; a pixel whose x is NaN leaves both sums, as does a pixel with w == 0; no pixel
+ *                            left: NaN.
+ *                  Both sums are fp64, taken per wave of 256 pixels (4 consecutive pixels per lane added in order, then an xor
+ *                  butterfly), the per-wave partials through scratch to a second stage that adds them in a fixed order: no float
+ *                  atomics, bitwise repeatable.  A plane whose wrows[j] is out of range takes no part in the series, in either
+ *                  mode (its binned sums are still produced).  partial: DEVICE fp64 scratch of
+ *                  ace_diag_calendar_partial_doubles(nplanes, nreg, batch, steps, hw) values (-1 for arguments this call would
+ *                  refuse); needed with the series only.  0 <= nreg <= ACE_DIAG_CALENDAR_MAX_REGIONS = 8; t0 >= 0 and
+ *                  t0 + steps <= n_time, or the call is refused.  batch * steps < 2^31.
+ *                  One launch, two with the series, however many planes; no allocation, no host synchronisation.
  * ------------------------------------------------------------------------------------------ */
 const char* ace_diag_last_error(void);
 long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
@@ -368,6 +409,14 @@ int ace_diag_regress_window(const float* const* gen, const long* gen_strides, co
                             const int* rows, const double* coef, const int* slot, double* maps, const float* eps, const int* wrows,
                             const float* weights, int nw, double* partial, long long* below_count, double* below_frac, int nrows,
                             int nterms, int nmaps, int t_begin, int nplanes, int batch, int steps, long hw, void* stream);
+#define ACE_DIAG_CALENDAR_MAX_BINS 8
+#define ACE_DIAG_CALENDAR_MAX_REGIONS 8
+long ace_diag_calendar_partial_doubles(int nplanes, int nreg, int batch, int steps, long hw);
+int ace_diag_calendar_window(const float* const* gen, const long* gen_strides, const float* const* target, const long* target_strides,
+                             const int* rows, const int* bin, double* bins, const float* regions, const int* srow, const int* mode,
+                             const int* wrows, const float* weights, int nw, double* partial, double* series, int nrows, int nbins,
+                             int nreg, int nsrows, int n_time, int t0, int t_begin, int nplanes, int batch, int steps, long hw,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
