@@ -3184,6 +3184,13 @@ __global__ void pack_normalize_kernel(const float* const* __restrict__ srcs, con
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < HW; t += (long)gridDim.x * blockDim.x)
         d[t] = __fdiv_rn(__fsub_rn(src[t], mu), sd);  // normalizer.py:221: (t - means[k]) / stds[k], unfused
 }
+// normalizer.py:236: t * stds[k] + means[k] as torch evaluates it, the product rounded before the sum.  __fadd_rn(__fmul_rn(..))
+// does not say that here: the two are a plain * and + in the HIP headers, and the default contraction fuses them into one fma.
+__device__ __forceinline__ float denormalize(float y, float sd, float mu) {
+#pragma clang fp contract(off)
+    const float p = y * sd;
+    return p + mu;
+}
 __global__ void unpack_denormalize_kernel(const float* __restrict__ src, const float* __restrict__ mean,
                                           const float* __restrict__ stdv, float* const* __restrict__ dsts,
                                           const long* __restrict__ strides, int nch, long HW) {
@@ -3192,7 +3199,7 @@ __global__ void unpack_denormalize_kernel(const float* __restrict__ src, const f
     float* d = dsts[j] + (long)b * strides[j];
     const float mu = mean[j], sd = stdv[j];
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < HW; t += (long)gridDim.x * blockDim.x)
-        d[t] = __fadd_rn(__fmul_rn(s[t], sd), mu);  // normalizer.py:236: t * stds[k] + means[k], two roundings
+        d[t] = denormalize(s[t], sd, mu);
 }
 hipError_t launch_pack_normalize(const float* const* srcs, const long* strides, const float* mean, const float* stdv,
                                  float* dst, int Bt, int nch, long HW, hipStream_t s) {

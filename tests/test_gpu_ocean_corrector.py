@@ -108,6 +108,8 @@ def _cm4(B=2, H=180, W=360, L=19, seed=0):
 
 
 def test_cm4_shape_batch2_against_float64_torch():
+    """On this pole-to-pole grid a lost last partial sum moves the answer by about 4e-7, far inside the bar below: what guards the
+    multi-block reduction is test_gpu_ocean_phys_shapes.py."""
     cfg, di, inp, gen, forcing = _cm4()
     corrector = cfg.get_corrector(di)
     out, _ = corrector(to_dev(inp), to_dev(gen), to_dev(forcing))
