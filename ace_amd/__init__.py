@@ -29,7 +29,7 @@ from .derived_forcings import DerivedForcingsConfig, ForcingDeriver, ForcingWind
 from .multi_call import MultiCallConfig  # noqa: F401
 from .stepper import PrognosticState, Stepper  # noqa: F401
 from .ocean_rollout import OceanRolloutEngine  # noqa: F401
-from .inference import EnginePredict, ForcingWindows, InferenceData, Looper, TensorFileWriter, run_evaluator, run_inference  # noqa: F401
+from .inference import EnginePredict, ForcingWindows, InferenceData, Looper, TensorFileWriter, repeat_members, run_evaluator, run_inference  # noqa: F401
 from .evaluator import InferenceEvaluatorAggregator, InferenceEvaluatorAggregatorConfig  # noqa: F401
 
 __version__ = "0.1.0"

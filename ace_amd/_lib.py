@@ -197,6 +197,9 @@ SIGNATURES = {
     # gen, gen_strides, target, target_strides, rows, bin, bins, regions, srow, mode, wrows, weights, nw, partial, series, nrows,
     # nbins, nreg, nsrows, n_time, t0, t_begin, nplanes, batch, steps, hw, stream
     "ace_diag_calendar_window": (c_int, [c_void_p] * 12 + [c_int] + [c_void_p] * 2 + [c_int] * 10 + [c_long, c_void_p]),
+    # gen, gen_strides, target, target_strides, rows, maps, seen, nrows, slot, nslots, pair_weight, t, nplanes, n_ic, n_members, steps,
+    # hw, stream
+    "ace_diag_ensemble_step": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_double] + [c_int] * 5 + [c_long, c_void_p]),
 }
 
 _lib = None

@@ -31,11 +31,21 @@ compared against a target record, for ``ace_amd.inference.run_evaluator``.  Buil
     seasonal mean maps with bias, anomaly, R2 and area-mean RMSE (``_Calendar`` holds these four).  They group the steps of
     ``record_batch`` by the calendar of ``time=``; a non-strict one that gets no time axis is dropped with a warning and listed
     in ``skipped`` (``uses_time``), a strict one raises (``needs_time``).  As in the reference, annual and enso_index need a
-    record of more than 730 days, ipo_index of more than 80 x 365 days, and the two indices need lat and lon.
+    record of more than 730 days, ipo_index of more than 80 x 365 days, and the two indices need lat and lon;
+  * ``step_means`` (one_step/reduced.py:24-249), built from ``StepMeanMetricConfig`` entries only: ``weighted_rmse``,
+    ``weighted_bias`` and ``weighted_grad_mag_percent_diff`` of the snapshot at time index ``step + n_ic_steps - 1``, or with
+    ``target="norm"`` the normalised RMSE and its ``channel_mean`` (``_StepMeans``: a column of the ``mean`` series, which is
+    then recorded even with ``mean_denorm`` and ``mean_norm`` off);
+  * ``ensembles`` (one_step/ensemble.py:74-505), built from ``EnsembleMetricConfig`` entries only and recorded only when
+    ``build(..., n_ensemble_per_ic=E)`` has ``E > 1``: the samples of a window are ``n_ic x E`` members (sample ``b = i E + e``),
+    and at the step whose time index equals ``step`` - no ``n_ic_steps`` term - the per-pixel almost-fair CRPS (alpha = 0.95),
+    ensemble-mean RMSE and spread-skill-ratio bias, their area-weighted means, with ``log_mean_maps`` the maps and with
+    ``target="norm"`` the channel means (``_Ensembles``).
 
 Not built, skipped at build time with one warning and listed in ``skipped`` as the reference's non-strict path does
-(main.py:143-153): ``step_means``, ``ensembles``, an ``annual``, ``enso_index`` or ``ipo_index`` given as a bare ``MetricConfig`` or
-whose record is too short, an ``enso_coefficient`` without an index or over a record of 1800 days or less, a ``trend`` over fewer
+(main.py:143-153): a ``step_means`` or ``ensembles`` entry given as a bare ``MetricConfig`` (the defaults; listed under the field's
+name) or whose ``step`` exceeds ``n_forward_steps`` (listed under its own name), an ``annual``, ``enso_index`` or ``ipo_index``
+given as a bare ``MetricConfig`` or whose record is too short, an ``enso_coefficient`` without an index or over a record of 1800 days or less, a ``trend`` over fewer
 than two forward steps.  ``video``, a ``seasonal``, ``histogram``, ``trend`` or ``near_zero_fraction`` enabled through a bare
 ``MetricConfig``, the reference-data paths (``annual.reference_data`` among them), a ``variables`` filter on any metric but the
 histogram, the trend, the near-zero fraction, annual and seasonal, HEALPix grids and ``strict=True`` on a skipped metric raise
@@ -54,7 +64,9 @@ spectrum chunk one SHT and one ``ace_diag_spectrum`` for each side, and with the
 read back before ``get_*``), and with any of trend, enso_coefficient and near_zero_fraction on one ``ace_diag_regress_window`` per
 window for the three together (csrc/regress.hip: every plane read once, the fp64 sums of a pixel kept in registers), and with any
 of seasonal, annual, enso_index and ipo_index on one ``ace_diag_calendar_window`` per window for the four together
-(csrc/calendar.hip: every plane read once for the seasonal sums and the regional means, which stay on the device until ``get_*``).
+(csrc/calendar.hip: every plane read once for the seasonal sums and the regional means, which stay on the device until ``get_*``),
+and per ensemble entry one ``ace_diag_ensemble_step`` in the window that holds its step (csrc/ensemble.hip: the members of a pixel in
+registers, the target planes streamed, four fp64 maps per name that stay on the device until ``get_*``).
 It never normalises a field: ``normalize`` is (x - mu) / sigma
 per name (fme/core/normalizer.py:213-227), every per-sample quantity is linear in it (rmse / sigma, bias / sigma, (mean - mu) /
 sigma, std / sigma, and the time-mean RMSE / sigma), so the ``_norm`` outputs are formed from the denormalised fp64 accumulators at
@@ -192,6 +204,43 @@ class SeasonalMetricConfig(MetricConfig):
     name: Optional[str] = "seasonal"
 
 
+@dataclasses.dataclass
+class StepMeanMetricConfig(MetricConfig):
+    """one_step/reduced.py:207-249: the ``mean`` metrics of one forward step, the snapshot at time index
+    ``step + n_ic_steps - 1``.  ``target``: "denorm" (RMSE, bias, gradient-magnitude percent difference per name) or "norm" (RMSE
+    per name and their ``channel_mean`` over ``channel_mean_names``, else the aggregator's, else every name); ``variables``: report
+    the per-name entries of these names only (the channel mean still runs over all).  ``step`` has a default only because the
+    fields of the base class have; ``name`` defaults to ``mean_step_{step}`` / ``mean_step_{step}_norm``."""
+    step: int = 20
+    target: str = "denorm"
+    channel_mean_names: Optional[List[str]] = None
+
+    def __post_init__(self):
+        if self.target not in ("denorm", "norm"):
+            raise ValueError(f"target must be 'denorm' or 'norm', got {self.target!r}")
+        if self.name is None:
+            self.name = f"mean_step_{self.step}" + ("_norm" if self.target == "norm" else "")
+
+
+@dataclasses.dataclass
+class EnsembleMetricConfig(MetricConfig):
+    """one_step/ensemble.py:444-505: CRPS, spread-skill-ratio bias and ensemble-mean RMSE at the window step whose global time
+    index equals ``step`` - with no ``n_ic_steps`` term, unlike the step means (ensemble.py:485-497 hands ``step`` to
+    SelectStepEnsembleAggregator as the global index; reduced.py:231 adds ``n_ic_steps - 1``).  ``log_mean_maps``: also the
+    per-pixel maps; ``target`` and ``channel_mean_names`` as in ``StepMeanMetricConfig``; ``name`` defaults to
+    ``ensemble_step_{step}`` / ``ensemble_step_{step}_norm``."""
+    step: int = 20
+    log_mean_maps: bool = False
+    target: str = "denorm"
+    channel_mean_names: Optional[List[str]] = None
+
+    def __post_init__(self):
+        if self.target not in ("denorm", "norm"):
+            raise ValueError(f"target must be 'denorm' or 'norm', got {self.target!r}")
+        if self.name is None:
+            self.name = f"ensemble_step_{self.step}" + ("_norm" if self.target == "norm" else "")
+
+
 def _off() -> MetricConfig:
     return MetricConfig(enabled=False, strict=True)
 
@@ -231,6 +280,8 @@ class InferenceEvaluatorAggregatorConfig:
     NEVER_BUILT = ("video", "seasonal")
     TYPED = {"histogram": HistogramMetricConfig, "trend": TrendMetricConfig, "near_zero_fraction": NearZeroFractionMetricConfig}
     SKIPPED = ("step_means", "ensembles")                                 # main.py:143-153, the non-strict path
+    # list fields: an entry of the typed class is built (_StepMeans, _Ensembles), a bare MetricConfig is what it always was
+    STEPPED = {"step_means": StepMeanMetricConfig, "ensembles": EnsembleMetricConfig}
     # built by _Calendar from their typed configurations; a bare MetricConfig in one of these fields is what it always was: an
     # enabled annual / enso_index / ipo_index skipped (or raised when strict), an enabled seasonal "not built"
     CALENDAR = {"seasonal": SeasonalMetricConfig, "annual": AnnualMetricConfig, "enso_index": EnsoIndexMetricConfig,
@@ -261,9 +312,15 @@ class InferenceEvaluatorAggregatorConfig:
 
     def build(self, dataset_info, n_ic_steps: int, n_forward_steps: int, normalize, output_dir: Optional[str] = None,
               channel_mean_names: Optional[Sequence[str]] = None, save_diagnostics: bool = False,
-              sht_factory: Optional[Callable[[int, int], Callable]] = None) -> "InferenceEvaluatorAggregator":
+              sht_factory: Optional[Callable[[int, int], Callable]] = None,
+              n_ensemble_per_ic: int = 1) -> "InferenceEvaluatorAggregator":
         """``normalize``: a ``StandardNormalizer``, its bound ``normalize``, or anything exposing per-name ``means`` and ``stds``
-        (the fused path reads the statistics, the torch path calls it); a bare callable serves the torch path only."""
+        (the fused path reads the statistics, the torch path calls it); a bare callable serves the torch path only.
+        ``n_ensemble_per_ic``: the samples of a window are ``n_ic x n_ensemble_per_ic`` members, sample ``b = i * n_ensemble_per_ic +
+        e`` (``inference.repeat_members``); with 1 the ensemble entries are accepted but neither recorded nor reported
+        (main.py:560-562, 604-621)."""
+        if int(n_ensemble_per_ic) < 1:
+            raise ValueError(f"n_ensemble_per_ic must be >= 1, got {n_ensemble_per_ic}")
         if self.monthly_reference_data is not None or self.time_mean_reference_data is not None:
             raise NotImplementedError("monthly_reference_data / time_mean_reference_data are netCDF files and there is no netCDF "
                                       "reader here; compare the maps of get_dataset() offline")
@@ -313,10 +370,25 @@ class InferenceEvaluatorAggregatorConfig:
                     calendar[field] = m
                 else:
                     unbuilt.append(field)
+        stepped: Dict[str, List[MetricConfig]] = {field: [] for field in self.STEPPED}
+        late: List[str] = []
+        for field, typed in self.STEPPED.items():
+            what = "step_mean step" if field == "step_means" else "ensemble step"
+            for m in getattr(self, field):
+                if not (m.enabled and isinstance(m, typed)):
+                    continue
+                if m.step > n_forward_steps:                              # reduced.py:226-230, ensemble.py:486-490
+                    reason = f"{what} {m.step} exceeds n_forward_steps={n_forward_steps}"
+                    if m.strict:
+                        raise NotImplementedError(f"the {m.name} metric is not supported for this configuration: {reason} "
+                                                  "(strict=True)")
+                    late.append(m.name)
+                else:
+                    stepped[field].append(m)
         for field in unbuilt:
             v = getattr(self, field)
             for m in (v if isinstance(v, list) else [v]):
-                if not m.enabled:
+                if not m.enabled or isinstance(m, self.STEPPED.get(field, ())):
                     continue
                 if m.strict and field in why:
                     raise NotImplementedError(f"the {field} metric is not supported for this configuration: {why[field]} "
@@ -325,6 +397,7 @@ class InferenceEvaluatorAggregatorConfig:
                     raise NotImplementedError(f"the {field} metric is not built (strict=True)")
                 if field not in skipped:
                     skipped.append(field)
+        skipped += [n for n in late if n not in skipped]
         if skipped:
             logging.warning("metrics not supported for this configuration, omitting: " + ", ".join(skipped))
         labels = {}
@@ -334,6 +407,15 @@ class InferenceEvaluatorAggregatorConfig:
                 raise NotImplementedError(f"{field}.variables: a per-metric variable filter is not built")
             if m.enabled:
                 labels[default] = m.name or default
+        taken = list(labels.values())                                     # every label that heads a block of the logs and the dataset
+        taken += [m.name or field for field, m in (("histogram", self.histogram), ("trend", trend), ("enso_coefficient", enso),
+                                                   ("near_zero_fraction", self.near_zero_fraction))
+                  if m is not None and m.enabled]
+        taken += [m.name or field for field, m in calendar.items()]
+        for m in stepped["step_means"] + stepped["ensembles"]:
+            if m.name in taken:
+                raise ValueError(f"two metrics are named '{m.name}'; give one of them another name")
+            taken.append(m.name)
         if _is_healpix(dataset_info):
             raise NotImplementedError("the inference evaluator aggregator is built for lat-lon grids only, not HEALPix")
         if getattr(dataset_info, "area_weights", None) is None:
@@ -345,7 +427,8 @@ class InferenceEvaluatorAggregatorConfig:
             report_directional_bias=getattr(self.power_spectrum, "report_directional_bias", True), output_dir=output_dir,
             save_diagnostics=save_diagnostics, sht_factory=sht_factory,
             histogram=self.histogram if self.histogram.enabled else None, trend=trend, enso_coefficient=enso,
-            near_zero_fraction=self.near_zero_fraction if self.near_zero_fraction.enabled else None, calendar=calendar)
+            near_zero_fraction=self.near_zero_fraction if self.near_zero_fraction.enabled else None, calendar=calendar,
+            step_means=stepped["step_means"], ensembles=stepped["ensembles"], n_ensemble_per_ic=int(n_ensemble_per_ic))
 
 
 # ---- the reference's formulas in torch ops (the torch path) ---------------------------------------------------------------------
@@ -1422,6 +1505,249 @@ class _Calendar:
         return logs
 
 
+ENSEMBLE_CRPS_ALPHA = 0.95                                                # one_step/ensemble.py:80
+PRESCRIBED_MSE_RTOL = 1e-6                                                # one_step/ensemble.py:20-23
+MAX_ENSEMBLE_MEMBERS = 32                                                 # ACE_DIAG_ENSEMBLE_MAX_MEMBERS (include/ace_sfno.h)
+ENSEMBLE_METRICS = ("crps", "ensemble_mean_rmse", "ssr_bias")             # sorted, as _get_data walks them (ensemble.py:296)
+
+
+def ssr_bias(total_unbiased_mse: torch.Tensor, total_variance: torch.Tensor) -> torch.Tensor:
+    """SSRBiasMetric.get (one_step/ensemble.py:150-173): spread / skill - 1 per pixel from the totals of mse - variance / E and of
+    the variance.  The unbiased MSE is clamped at 0 before the square root (the correction can go slightly negative with few
+    members); zero skill gives -1 by convention (the limit for spread -> 0 at non-zero skill); a prescribed cell - variance
+    exactly 0 and unbiased MSE at most PRESCRIBED_MSE_RTOL x the field's largest clamped MSE - is a 0 / 0 and reports 0."""
+    spread = total_variance.sqrt()
+    skill = torch.clamp(total_unbiased_mse, min=0.0).sqrt()
+    ssr = torch.where(skill > 0, spread / skill - 1, torch.full_like(spread, -1.0))
+    mse_floor = PRESCRIBED_MSE_RTOL * skill.square().max()
+    prescribed = (total_variance == 0) & (total_unbiased_mse <= mse_floor)
+    return torch.where(prescribed, torch.zeros_like(spread), ssr)
+
+
+def _channel_mean(values: Mapping[str, float], own: Optional[Sequence[str]], fallback: Optional[Sequence[str]],
+                  nan_targets) -> Optional[float]:
+    """reduced_metrics.py:76-116 and ensemble.py:313-332: the mean of ``values`` over ``own`` names, else ``fallback``, else all,
+    without the names whose target is all NaN; a name that is not present raises KeyError; None when no name is left"""
+    names = own or fallback
+    if names is None:
+        names = list(values)
+    missing = [n for n in names if n not in values]
+    if missing:
+        raise KeyError(f"channel_mean_names contains entries not present in the recorded data: {missing}. "
+                       f"Available: {sorted(values)}.")
+    names = [n for n in names if n not in nan_targets]
+    return sum(values[n] for n in names) / len(names) if names else None
+
+
+class _StepMeans:
+    """``step_means`` (MeanAggregator behind StepMeanMetricConfig, one_step/reduced.py:24-249): the column of the ``mean`` series at
+    time index ``step + n_ic_steps - 1`` - the sample-mean ``weighted_rmse``, ``weighted_bias`` and
+    ``weighted_grad_mag_percent_diff`` of that step, averaged over the records that held it - so there is nothing to accumulate
+    beyond what the paired pass (or the torch path's series) already holds; the norm form is the norm series' column.  Only
+    ``record_batch`` feeds it, as in the reference (main.py:602-603, 660-661): an entry whose index lies inside the initial
+    condition, or whose window has not come yet, reports nothing.  Which targets are entirely NaN (left out of the channel mean,
+    reduced_metrics.py:101-110) is decided on the device at the first record of the selected step and read at ``get_*`` time."""
+
+    def __init__(self, agg, configs: Sequence[StepMeanMetricConfig]):
+        self._agg = agg
+        self.configs = list(configs)
+        self.kinds = {c.target for c in self.configs}
+        self._nan: Dict[int, Any] = {}                                    # entry -> (names, device bool (names,))
+
+    def index(self, c) -> int:
+        return c.step + self._agg.n_ic_steps - 1
+
+    def record(self, tgt, i_time_start: int):
+        T = next(iter(tgt.values())).shape[1]
+        for i, c in enumerate(self.configs):
+            k = self.index(c) - i_time_start
+            if c.target == "norm" and i not in self._nan and 0 <= k < T and self.index(c) >= self._agg.n_ic_steps:
+                names = list(tgt)                                           # one stacked reduction over the names
+                self._nan[i] = (names, torch.stack([tgt[n][:, k] for n in names]).isnan().flatten(1).all(dim=1))
+
+    def _entries(self):
+        agg = self._agg
+        series: Dict[str, Any] = {}
+        for i, c in enumerate(self.configs):
+            ti = self.index(c)
+            if ti < agg.n_ic_steps or agg._n_batches[ti] == 0:
+                continue
+            if c.target not in series:
+                series[c.target] = agg._series_data(c.target)
+            metrics = ("weighted_rmse", "weighted_bias", "weighted_grad_mag_percent_diff") if c.target == "denorm" else \
+                ("weighted_rmse",)
+            data: Dict[str, float] = {}
+            for metric in metrics:
+                column = series[c.target][metric]                           # one read of the column per metric
+                values = dict(zip(column, torch.stack([v[ti] for v in column.values()]).tolist())) if column else {}
+                for n, v in values.items():
+                    if c.variables is None or n in c.variables:
+                        data[f"{metric}/{n}"] = v
+                if c.target == "norm":
+                    names, flags = self._nan.get(i, ([], None))
+                    nan_targets = set() if flags is None else {n for n, f in zip(names, flags.tolist()) if f}
+                    cm = _channel_mean(values, c.channel_mean_names, agg._channel_mean_names, nan_targets)
+                    if cm is None:
+                        raise ValueError("All target variables are NaN; cannot compute channel mean.")
+                    data[f"{metric}/channel_mean"] = cm
+            yield c.name, data
+
+    def logs(self) -> Dict[str, Any]:
+        return {f"{label}/{k}": v for label, data in self._entries() for k, v in sorted(data.items())}
+
+    def dataset(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        return {label: {k.replace("/", "-"): torch.tensor(v, dtype=torch.float64) for k, v in data.items()}
+                for label, data in self._entries()}
+
+
+class _Ensembles:
+    """``ensembles`` (SelectStepEnsembleAggregator over _EnsembleAggregator, one_step/ensemble.py:176-441): per entry and name the
+    per-pixel CRPS (``get_crps`` with alpha = 0.95, fme/core/ensemble.py:4-44), ensemble-mean RMSE and spread-skill-ratio bias at
+    the window step whose global time index equals the entry's ``step`` - no ``n_ic_steps`` term, unlike ``_StepMeans`` - averaged
+    over the records that held it.  The samples of a window are ``n_ic x n_members``, sample ``b = i * n_members + e``
+    (``unfold_ensemble_dim``, fme/core/tensors.py:135-155), and the target is unfolded the same way: member ``e`` is compared with
+    its own target plane.  The torch path restates CRPSMetric, EnsembleMeanRMSEMetric and SSRBiasMetric in torch ops on the
+    window's dtype (and on ``normalize`` of the window for a norm entry); the fused path makes one ``ace_diag_ensemble_step`` per
+    entry whose step lies in the window (csrc/ensemble.hip; the header contract in include/ace_sfno.h): four fp64 maps per entry
+    and name - the sums of crps, sqrt(mse), mse - var / E and var - stay on the device until ``get_*``, where a norm entry is
+    formed from them (crps / sigma, rmse / sigma, (mse, var) / sigma^2; a name without statistics is dropped).  An entry whose
+    window has not come yet reports nothing."""
+
+    def __init__(self, agg, configs: Sequence[EnsembleMetricConfig], n_members: int):
+        self._agg = agg
+        self.configs = list(configs)
+        self.kinds = {c.target for c in self.configs}
+        self.n_members = int(n_members)
+        self.calls = 0
+        self._n = [0] * len(self.configs)                                 # records per entry (_n_batches)
+        # torch path: entry -> name -> [crps, rmse, unbiased mse, variance] totals; entry -> name -> 0-dim bool, target all NaN
+        self._t: List[Dict[str, List[torch.Tensor]]] = [{} for _ in self.configs]
+        self._t_nan: List[Optional[Dict[str, torch.Tensor]]] = [None] * len(self.configs)
+        # fused path: _maps (entries, 4, rows, H W) fp64, _seen (entries, rows) int32
+        self._rows: Dict[str, int] = {}
+        self._maps = self._seen = None
+
+    def _selected(self, i_time_start: int, T: int):
+        return [(i, c.step - i_time_start) for i, c in enumerate(self.configs) if i_time_start <= c.step < i_time_start + T]
+
+    # ---- the torch path -----------------------------------------------------------------------------------------------
+    def record_torch(self, kinds, i_time_start: int):
+        """``kinds``: "denorm" (and "norm" when an entry needs it) -> (gen, target) windows"""
+        E = self.n_members
+        first = next(iter(kinds["denorm"][0].values()))
+        B, T = first.shape[:2]
+        eps = (1.0 - ENSEMBLE_CRPS_ALPHA) / 2.0
+        for i, k in self._selected(i_time_start, T):
+            gen, tgt = kinds[self.configs[i].target]
+            unfold = lambda x: x[:, k:k + 1].reshape(B // E, E, 1, *x.shape[2:])      # noqa: E731  [batch, ensemble, time, H, W]
+            for n, yb in tgt.items():
+                g, y = unfold(gen[n]), unfold(yb)
+                e0, e1 = torch.triu_indices(E, E, offset=1, device=g.device)
+                internal = -0.5 * (g[:, e0] - g[:, e1]).abs().mean(dim=1)
+                crps = (torch.mean(torch.abs(g - y), dim=1) + (1.0 - eps) * internal).mean(dim=(0, 1))
+                mse = ((g.mean(dim=1, keepdim=True) - y) ** 2).mean(dim=(0, 1, 2))
+                var = g.var(dim=1, unbiased=True).mean(dim=(0, 1))
+                parts = [crps, mse.sqrt(), mse - var / E, var]
+                tot = self._t[i].get(n)
+                self._t[i][n] = parts if tot is None else [a + b for a, b in zip(tot, parts)]
+            if self._t_nan[i] is None:
+                self._t_nan[i] = {n: torch.isnan(unfold(y)).all() for n, y in tgt.items()}
+            self._n[i] += 1
+
+    # ---- the fused path -----------------------------------------------------------------------------------------------
+    def record_fused(self, gen, tgt, i_time_start: int) -> int:
+        """one ``ace_diag_ensemble_step`` per entry whose step lies in the window, for all paired names (fields with contiguous
+        planes); returns the calls made"""
+        from . import _lib
+        first = next(iter(gen.values()))
+        dev, (B, T, H, W) = first.device, first.shape
+        todo = self._selected(i_time_start, T)
+        if not todo:
+            return 0
+        E, HW = self.n_members, H * W
+        if not 2 <= E <= MAX_ENSEMBLE_MEMBERS:
+            raise ValueError(f"the fused ensemble pass keeps the members of a pixel in registers, at most {MAX_ENSEMBLE_MEMBERS}: "
+                             f"{E} members per initial condition need the torch path (fused = False)")
+        names = list(tgt)
+        new = [n for n in names if n not in self._rows]
+        if new or self._maps is None:
+            for n in new:
+                self._rows[n] = len(self._rows)
+            R = max(1, len(self._rows))
+            self._maps = _grow(self._maps, (len(self.configs), 4, R, HW), torch.float64, dev)
+            self._seen = _grow(self._seen, (len(self.configs), R), torch.int32, dev)
+        values, off = _plane_table(names, gen, tgt)
+        table = _upload(values, torch.int64, dev)
+        at = {k: table.data_ptr() + o for k, o in off.items()}
+        rows32 = _upload([self._rows[n] for n in names], torch.int32, dev)
+        lib = _lib.lib()
+        pair_weight = 0.5 * (1.0 - (1.0 - ENSEMBLE_CRPS_ALPHA) / 2.0)
+        for i, k in todo:
+            with torch.cuda.device(dev):
+                _check(lib.ace_diag_ensemble_step(
+                    at["gen"], at["gen_strides"], at["target"], at["target_strides"], rows32.data_ptr(), self._maps.data_ptr(),
+                    self._seen.data_ptr(), self._maps.shape[2], i, len(self.configs), pair_weight, k, len(names), B // E, E, T, HW,
+                    _lib.current_stream()))
+            self._n[i] += 1
+        self.calls += len(todo)
+        return len(todo)
+
+    # ---- results ------------------------------------------------------------------------------------------------------
+    def _maps_of(self, i: int):
+        """entry i: name -> (crps, ensemble_mean_rmse, ssr_bias) (H, W) maps, and the names whose target is all NaN"""
+        agg, c, nb = self._agg, self.configs[i], self._n[i]
+        out: Dict[str, Any] = {}
+        if self._maps is not None:
+            seen = self._seen[i].tolist()
+            nan_targets = {n for n, r in self._rows.items() if not seen[r]}
+            for n, r in sorted(self._rows.items()):
+                crps, rmse, umse, var = self._maps[i, :, r]
+                if c.target == "norm":
+                    if not agg._has_stats(n):
+                        continue
+                    sigma = agg._stats[n][1]
+                    crps, rmse, umse, var = crps / sigma, rmse / sigma, umse / (sigma * sigma), var / (sigma * sigma)
+                out[n] = (crps / nb, rmse / nb, ssr_bias(umse, var))
+        else:
+            nan_targets = {n for n, f in (self._t_nan[i] or {}).items() if bool(f)}
+            for n, (crps, rmse, umse, var) in sorted(self._t[i].items()):
+                out[n] = (crps / nb, rmse / nb, ssr_bias(umse, var))
+        shape = agg._shape
+        return {n: tuple(agg._reduce_mean(m.reshape(shape)) for m in maps) for n, maps in out.items()}, nan_targets
+
+    def _entries(self):
+        agg = self._agg
+        for i, c in enumerate(self.configs):
+            if self._n[i] == 0:
+                continue
+            maps, nan_targets = self._maps_of(i)
+            data: Dict[str, Any] = {}
+            for j, metric in enumerate(ENSEMBLE_METRICS):
+                values = {}
+                for n, per in maps.items():
+                    m = per[j]
+                    values[n] = float(_wmean(m, agg.weights_for(n, m.device).to(m.dtype)))
+                    if c.variables is None or n in c.variables:
+                        data[f"{metric}/{n}"] = values[n]
+                        if c.log_mean_maps:
+                            data[f"{metric}/mean_map/{n}"] = m.cpu()
+                if c.target == "norm":
+                    cm = _channel_mean(values, c.channel_mean_names, agg._channel_mean_names, nan_targets)
+                    if cm is not None:
+                        data[f"{metric}/channel_mean"] = cm
+            yield c.name, data
+
+    def logs(self) -> Dict[str, Any]:
+        """ensemble.py:291-352 with tensors where the reference logs figures: ``<label>/<metric>/<name>`` the area-weighted mean of
+        the map, with ``log_mean_maps`` ``<label>/<metric>/mean_map/<name>`` the (H, W) map, with ``target="norm"``
+        ``<label>/<metric>/channel_mean``"""
+        return {f"{label}/{k}": v for label, data in self._entries() for k, v in sorted(data.items())}
+
+    def dataset(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        return {label: {k.replace("/", "-"): v if isinstance(v, torch.Tensor) else torch.tensor(v, dtype=torch.float64)
+                        for k, v in data.items()} for label, data in self._entries()}
+
+
 class InferenceEvaluatorAggregator(InferenceAggregator):
     """main.py:526-732 for the sub-aggregators of the module docstring.  Weights, masks, routing and the SHT are the parent's."""
 
@@ -1431,9 +1757,11 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
                  sht_factory=None, spectrum_chunk_bytes: int = 256 << 20, histogram: Optional[HistogramMetricConfig] = None,
                  trend: Optional[TrendMetricConfig] = None, enso_coefficient: Optional[EnsoCoefficientMetricConfig] = None,
                  near_zero_fraction: Optional[NearZeroFractionMetricConfig] = None,
-                 calendar: Optional[Mapping[str, MetricConfig]] = None):
+                 calendar: Optional[Mapping[str, MetricConfig]] = None, step_means: Sequence[StepMeanMetricConfig] = (),
+                 ensembles: Sequence[EnsembleMetricConfig] = (), n_ensemble_per_ic: int = 1):
         super().__init__(dataset_info, n_ic_steps + n_forward_steps, True, output_dir, save_diagnostics, sht_factory,
                          spectrum_chunk_bytes)
+        self.n_ensemble_per_ic = int(n_ensemble_per_ic)
         self._hist = None if histogram is None or not histogram.enabled else _Histograms(histogram)
         on = [None if m is None or not m.enabled else m for m in (trend, enso_coefficient, near_zero_fraction)]
         self._regress = _Regress(self, *on) if any(m is not None for m in on) else None
@@ -1443,6 +1771,10 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         default = InferenceEvaluatorAggregatorConfig.BUILT.values()
         self._labels = dict(labels) if labels is not None else {k: k for k in default}
         self._log_series = "mean" in self._labels or "mean_norm" in self._labels
+        self._steps = _StepMeans(self, step_means) if step_means else None
+        # main.py:560-562, 604-621: with one member per initial condition the ensemble entries are neither recorded nor reported
+        self._ensembles = _Ensembles(self, ensembles, self.n_ensemble_per_ic) if ensembles and self.n_ensemble_per_ic > 1 else None
+        self._record_series = self._log_series or self._steps is not None     # a step mean is a column of the series
         self._channel_mean_names = None if channel_mean_names is None else list(channel_mean_names)
         self._directional = bool(report_directional_bias)
         owner = getattr(normalize, "__self__", normalize)
@@ -1456,7 +1788,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         self._pair_names: List[str] = []
         self._present: Dict[str, Dict[str, List[int]]] = {"gen": {}, "target": {}}     # name -> records per time index
         self._spec_side_counts: List[Dict[str, int]] = [{}, {}]
-        self._need_norm = "mean_norm" in self._labels or "time_mean_norm" in self._labels
+        self._need_norm = "mean_norm" in self._labels or "time_mean_norm" in self._labels or \
+            any(sub is not None and "norm" in sub.kinds for sub in (self._steps, self._ensembles))
         # torch path state
         self._t_series: Dict[str, Dict[str, Dict[str, torch.Tensor]]] = {"denorm": {}, "norm": {}}
         self._t_tsum: Dict[str, List[Dict[str, torch.Tensor]]] = {"denorm": [{}, {}], "norm": [{}, {}]}
@@ -1476,7 +1809,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         """Native launches made so far: one ``ace_diag_paired_window`` per window, one ``ace_diag_hist_window`` per window of
         ``record_batch`` when the histogram is on, one ``ace_diag_regress_window`` per window of ``record_batch`` when any of
         trend, enso_coefficient and near_zero_fraction is on (a second one for the ENSO term of a window at time index 0), and
-        per spectrum chunk of either side one forward SHT and one ``ace_diag_spectrum``."""
+        one ``ace_diag_ensemble_step`` per ensemble entry and window that holds its step, and per spectrum chunk of either side
+        one forward SHT and one ``ace_diag_spectrum``."""
         return self._launches
 
     def calendar_launches(self) -> int:
@@ -1536,7 +1870,7 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         n = next(iter(gen.values())).shape[1]
         if n != self.n_ic_steps:
             raise ValueError(f"Expected {self.n_ic_steps} initial condition steps, but got {n}")
-        if self._log_series:
+        if self._record_series:
             self._record_pair(gen, tgt, 0, with_maps=False)
         self._n_seen = n
         return []
@@ -1550,7 +1884,9 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
             raise ValueError("No prediction values in data")
         if len(target) == 0:
             raise ValueError("No target values in data")
-        n = next(iter(prediction.values())).shape[1]
+        B, n = next(iter(prediction.values())).shape[:2]
+        if B % self.n_ensemble_per_ic != 0:
+            raise ValueError(f"a window of {B} samples is not a multiple of n_ensemble_per_ic = {self.n_ensemble_per_ic}")
         if self.uses_time and time is None:
             self._without_time()
         if self.uses_time:
@@ -1588,7 +1924,7 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         for n in gen:
             if n not in self._series_names:
                 self._series_names.append(n)
-        if self._log_series:
+        if self._record_series:
             for side, d in (("gen", gen), ("target", tgt)):
                 for n in d:
                     seen = self._present[side].setdefault(n, [0] * self._n_time)
@@ -1626,8 +1962,13 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         kinds = {"denorm": (gen, tgt)}
         if self._need_norm:
             kinds["norm"] = (self._normalize_fn(gen), self._normalize_fn(tgt))            # main.py:594-598
+        if with_maps and self._steps is not None:
+            self._steps.record(tgt, i_time_start)
+        if with_maps and self._ensembles is not None:
+            self._ensembles.record_torch(kinds, i_time_start)
         for kind, (g, t) in kinds.items():
-            if ("mean" if kind == "denorm" else "mean_norm") in self._labels:
+            if ("mean" if kind == "denorm" else "mean_norm") in self._labels or \
+                    (self._steps is not None and kind in self._steps.kinds):
                 vals: Dict[str, Dict[str, torch.Tensor]] = {m: {} for m in (SERIES if kind == "denorm" else NORM_SERIES)}
                 for n, x in g.items():
                     w = self.weights_for(n, x.device).to(x.dtype)
@@ -1712,7 +2053,7 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         partial = torch.empty(int(lib.ace_diag_paired_partial_doubles(n, B, T, H, W)), dtype=torch.float64, device=dev)
         at = {k: table.data_ptr() + o for k, o in off.items()}
         series, n_time, t0 = self._series, self._n_time, i_time_start
-        if not self._log_series:
+        if not self._record_series:
             series, n_time, t0 = torch.empty(len(SERIES), len(self._rows), T, dtype=torch.float64, device=dev), T, 0
         zonal = with_maps and "zonal_mean" in self._labels
         zt0 = i_time_start - self._zon_first if zonal else 0
@@ -1730,6 +2071,10 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
                 self._launches += self._regress.record_fused(gen, tgt, i_time_start, time)
             if with_maps and self._calendar is not None:
                 self._calendar.record_fused(gen, tgt, i_time_start, time)
+            if with_maps and self._steps is not None:
+                self._steps.record(tgt, i_time_start)
+            if with_maps and self._ensembles is not None:
+                self._launches += self._ensembles.record_fused(gen, tgt, i_time_start)
             if not with_maps or "power_spectrum" not in self._labels:
                 return
             sht = self._get_sht()
@@ -1907,6 +2252,9 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
             ds.update(self._regress.dataset())
         if self._calendar is not None:
             ds.update(self._calendar.dataset())
+        for sub in (self._steps, self._ensembles):
+            if sub is not None:
+                ds.update(sub.dataset())
         return ds
 
     @torch.no_grad()
@@ -1937,6 +2285,9 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
             logs.update(self._regress.logs())
         if self._calendar is not None:
             logs.update(self._calendar.logs())
+        for sub in (self._steps, self._ensembles):
+            if sub is not None:
+                logs.update(sub.logs())
         key = L.get("time_mean_norm")
         return InferenceSummary(logs=logs, loss=logs.get(f"{key}/rmse/channel_mean") if key else None)
 

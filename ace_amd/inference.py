@@ -105,6 +105,18 @@ class ForcingWindows:
             yield self._with_time(win, i)
 
 
+def repeat_members(mapping: Mapping[str, torch.Tensor], n: int) -> TensorDict:
+    """``repeat_interleave_batch_dim`` (fme/core/tensors.py:119-132): every sample of every tensor repeated ``n`` times along the
+    leading dimension, sample ``b = i * n + e`` a copy of sample ``i`` - the layout the evaluator's ensemble metrics expect
+    (``InferenceEvaluatorAggregatorConfig.build(..., n_ensemble_per_ic=n)``), so an initial condition and its forcing or target
+    windows fan out to ``n_ic x n`` samples.  The expand is a view; the reshape copies."""
+    if n < 1:
+        raise ValueError(f"n must be >= 1, got {n}")
+    if n == 1:
+        return dict(mapping)
+    return {k: v.unsqueeze(1).expand(-1, n, *v.shape[1:]).reshape(-1, *v.shape[1:]) for k, v in mapping.items()}
+
+
 class InferenceData:
     """``InferenceDataABC``: an initial condition and an iterable of aligned forcing windows."""
 

@@ -386,6 +386,35 @@ int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, c
  *                  refuse); needed with the series only.  0 <= nreg <= ACE_DIAG_CALENDAR_MAX_REGIONS = 8; t0 >= 0 and
  *                  t0 + steps <= n_time, or the call is refused.  batch * steps < 2^31.
  *                  One launch, two with the series, however many planes; no allocation, no host synchronisation.
+ *   diag_ensemble_step: the evaluator's ensemble metrics at one step of a window - the almost-fair CRPS, the ensemble-mean RMSE and
+ *                  the two sums behind the spread-skill ratio (fme/ace/aggregator/one_step/ensemble.py:74-173, get_crps of
+ *                  fme/core/ensemble.py:4-44 with alpha = 0.95) - for all names from one read of every plane, in place of the
+ *                  reference's (B, E (E - 1) / 2, H, W) tensor of member pairs and its three torch reductions per name.
+ *                  gen / target / strides / rows: as diag_regress_window, planes of hw contiguous fp32 starting at any 4-byte
+ *                  boundary, fields of batch = n_ic * n_members samples with sample b = i * n_members + e (member e of initial
+ *                  condition i; the target is laid out the same way, member e is compared with its own target plane).  A plane
+ *                  whose rows[j] is out of range [0, nrows), or whose target[j] is NULL, contributes to nothing.  rows must not
+ *                  name one row twice (the += below are not atomic); this is not checked.  maps: DEVICE fp64
+ *                  [nslots][4][nrows][hw]; seen: DEVICE int [nslots][nrows].
+ *                  For plane j and pixel p, with g_e, y_e the fp32 values of member e of initial condition i at step t widened to
+ *                  fp64, E = n_members, every sum in ascending index order and NOT contracted (products are rounded, then added:
+ *                  no fma), so a host statement in plain fp64 arithmetic reproduces it:
+ *                    m   = (sum_e g_e) / E
+ *                    a   = (sum_e |g_e - y_e|) / E
+ *                    s   = (sum_{e<f} |g_e - g_f|, e outer ascending, f inner ascending) / (E (E - 1) / 2)
+ *                    c_i = a - pair_weight * s          (the host passes pair_weight = 0.5 * (1 - (1 - alpha) / 2), alpha = 0.95)
+ *                    q_i = (sum_e (m - y_e)^2) / E
+ *                    v_i = (sum_e (g_e - m)^2) / (E - 1)
+ *                    crps = (sum_i c_i) / n_ic,   mse = (sum_i q_i) / n_ic,   var = (sum_i v_i) / n_ic
+ *                    maps[slot][0][row][p] += crps;  [1] += sqrt(mse);  [2] += mse - var / E;  [3] += var
+ *                  seen[slot][rows[j]] is set to 1 by any thread that meets a target value that is not NaN (a plain 4-byte store
+ *                  of the constant 1, the same value from every writer); it is never cleared.  NaN and infinity propagate.
+ *                  Identical members give v_i exactly 0: for fp32 g and E <= 32 the sum E * g is exact in fp64 (24 + 5 bits) and
+ *                  so is its quotient by E, hence m == g and every (g_e - m)^2 is +0 - the evaluator's prescribed-cell rule tests
+ *                  variance == 0.  A thread keeps the members of its pixels in registers (the target planes are streamed), so
+ *                  2 <= n_members <= ACE_DIAG_ENSEMBLE_MAX_MEMBERS = 32; other counts are refused, as are t outside [0, steps),
+ *                  slot outside [0, nslots) and n_ic < 1.  nplanes == 0 is a no-op.  Each pixel is owned by one thread: no
+ *                  atomics, bitwise repeatable.  One launch however many planes; no allocation, no host synchronisation.
  * ------------------------------------------------------------------------------------------ */
 const char* ace_diag_last_error(void);
 long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
@@ -417,6 +446,10 @@ int ace_diag_calendar_window(const float* const* gen, const long* gen_strides, c
                              const int* wrows, const float* weights, int nw, double* partial, double* series, int nrows, int nbins,
                              int nreg, int nsrows, int n_time, int t0, int t_begin, int nplanes, int batch, int steps, long hw,
                              void* stream);
+#define ACE_DIAG_ENSEMBLE_MAX_MEMBERS 32
+int ace_diag_ensemble_step(const float* const* gen, const long* gen_strides, const float* const* target, const long* target_strides,
+                           const int* rows, double* maps, int* seen, int nrows, int slot, int nslots, double pair_weight,
+                           int t, int nplanes, int n_ic, int n_members, int steps, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
