@@ -173,6 +173,11 @@ SIGNATURES = {
     # srcs, src_strides, mask_idx, hits, nmask, fill, stage, stage_strides, mean, std, dst, npack, nplanes, batch, hw, stream
     "ace_mask_pack_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    "ace_couple_last_error": (c_char_p, []),
+    # srcs, src_strides, dsts, dst_strides, masks, npass, mode, interpolate, n_inner, batch, hw, stream
+    "ace_couple_ocean_to_atmosphere": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_long, c_void_p]),
+    # srcs, src_strides, dsts, dst_strides, slot, nnames, n_inner, batch, hw, stream
+    "ace_couple_atmosphere_to_ocean": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_long, c_void_p]),
     "ace_diag_last_error": (c_char_p, []),
     "ace_diag_partial_doubles": (c_long, [c_int, c_int, c_int, c_long]),
     # srcs, strides, rows, wrows, weights, nw, partial, tsum, series, nrows, n_time, t0, t_begin, do_tsum, nplanes, batch, steps,

@@ -86,6 +86,23 @@ def _normalization_from_state(norm: Mapping[str, Any]) -> NormalizationConfig:
                                fill_nans_on_denormalize=bool(norm.get("fill_nans_on_denormalize", False)))
 
 
+def dataset_info_from_state(ds_state: Mapping[str, Any]) -> DatasetInfo:
+    """``DatasetInfo.from_state`` (fme/core/dataset_info.py:291-345) for the slice the hot path reads."""
+    from .masking import SpatialMaskProvider
+    mp = ds_state.get("mask_provider")
+    provider = SpatialMaskProvider.from_state(mp) if isinstance(mp, Mapping) else None      # drives the output masking (and input_masking)
+    labels = ds_state.get("all_labels") or None
+    # geometry for the conservation correctors: latitudes (or legacy area weights) and hybrid-sigma coefficients
+    hc = ds_state.get("horizontal_coordinates") or {}
+    vc = ds_state.get("vertical_coordinate") or {}
+    go = ds_state.get("gridded_operations") or {}
+    area = go.get("state", {}).get("area_weights") if isinstance(go, Mapping) else None
+    return DatasetInfo(_img_shape_from_dataset_state(ds_state), all_labels=set(labels) if labels else None,
+                       timestep=_timestep_from_dataset_state(ds_state), lat=hc.get("lat"), lon=hc.get("lon"),
+                       ak=vc.get("ak"), bk=vc.get("bk"), area_weights=area, mask_provider=provider,
+                       depth_coordinate=vc if "idepth" in vc else None)
+
+
 def stepper_config_from_state(state: Mapping[str, Any], ignore_unsupported: bool = False):
     """-> (SingleModuleStepConfig, DatasetInfo, module state dict, list of ignored items).  The stepper-level
     ``derived_forcings`` configuration is attached to the step config as ``_derived_forcings`` (a DerivedForcingsConfig), the
@@ -157,22 +174,11 @@ def stepper_config_from_state(state: Mapping[str, Any], ignore_unsupported: bool
         raise ValueError(f"unknown step config fields: {sorted(unknown)}")
     config = SingleModuleStepConfig(builder=ModuleSelector(type=builder["type"], config=dict(builder["config"])),
                                     normalization=normalization, **step_cfg)
-    from .masking import SpatialMaskProvider
-    mp = ds_state.get("mask_provider")
-    provider = SpatialMaskProvider.from_state(mp) if isinstance(mp, Mapping) else None      # drives the output masking (and input_masking)
     if ds_state.get("variable_metadata") is not None:
         ignored.append("dataset_info.variable_metadata")
-    labels = ds_state.get("all_labels") or None
-    # geometry for the conservation correctors: latitudes (or legacy area weights) and hybrid-sigma coefficients
-    hc = ds_state.get("horizontal_coordinates") or {}
     vc_state = ds_state.get("vertical_coordinate")
     vc = vc_state or {}
-    go = ds_state.get("gridded_operations") or {}
-    area = go.get("state", {}).get("area_weights") if isinstance(go, Mapping) else None
-    dataset_info = DatasetInfo(_img_shape_from_dataset_state(ds_state), all_labels=set(labels) if labels else None,
-                               timestep=_timestep_from_dataset_state(ds_state), lat=hc.get("lat"), lon=hc.get("lon"),
-                               ak=vc.get("ak"), bk=vc.get("bk"), area_weights=area, mask_provider=provider,
-                               depth_coordinate=vc if "idepth" in vc else None)
+    dataset_info = dataset_info_from_state(ds_state)
     from .ocean_corrector import OceanCorrectorConfig
     if isinstance(config.corrector, OceanCorrectorConfig) and (vc_state is None or "ak" in vc):
         # DatasetInfo.ocean_vertical_coordinate (fme/core/dataset_info.py:208-217) raises for anything but a depth or a null

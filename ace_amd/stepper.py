@@ -125,6 +125,29 @@ class Stepper:
         return self._step_obj.normalizer
 
     @property
+    def config(self):
+        """The step's configuration: what ``CoupledStepperConfig`` computes the exchange's name sets from."""
+        return self._step_obj.config
+
+    @property
+    def surface_temperature_name(self) -> Optional[str]:
+        """single_module.py:899-901: the surface temperature of the ``ocean`` config, None without one."""
+        ocean = self._step_obj.config.ocean
+        return ocean.surface_temperature_name if ocean is not None else None
+
+    @property
+    def ocean_fraction_name(self) -> Optional[str]:
+        ocean = self._step_obj.config.ocean
+        return ocean.ocean_fraction_name if ocean is not None else None
+
+    def prescribe_sst(self, mask_data: TensorMapping, gen_data: TensorMapping, target_data: TensorMapping) -> TensorDict:
+        """single_module.py:907-922: the ``ocean`` config's prescriber on the generated surface temperature."""
+        ocean = self._step_obj._ocean
+        if ocean is None:
+            raise RuntimeError("The Stepper does not use an ocean model, so prescribe_sst is unavailable.")
+        return ocean.prescriber(mask_data, gen_data, target_data)
+
+    @property
     def _input_only_names(self) -> set:
         return set(self._step_obj.input_names).difference(self._step_obj.output_names)
 

@@ -247,6 +247,51 @@ int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, c
                             const float* std_, float* dst, int npack, int nplanes, int batch, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The exchange of the coupled atmosphere-ocean stepper (fme/coupled/stepper.py:986-1148), ace_amd/coupled.py: two launches per
+ * coupled step.  Tables are DEVICE arrays as in the stepper glue above; strides in floats; every plane has hw contiguous fp32
+ * pixels at any 4-byte alignment.  16-byte accesses only on a row (plane, sample, time level) with hw % 4 == 0 and a 16-byte
+ * aligned address.  Stream-ordered; no allocation, atomics or host synchronisation; argument checks on the host before the
+ * first HIP call (ACE_ERR_INVALID).
+ *
+ * ocean_to_atmosphere: the ocean state as atmosphere forcings over T = n_inner + 1 time levels, and the prescribed initial
+ * surface temperature.  Slot j has a source srcs[j] with (sample, step) strides src_strides[2j], [2j+1], a destination dsts[j]
+ * with dst_strides likewise, and masks[j]: a [hw] fp32 plane or NULL; a destination value is 0 where its mask is 0
+ * (tensor.where(mask != 0, 0)).  Slots:
+ *   0  sea surface temperature: ocean sst -> the atmosphere's surface temperature forcing, one time level
+ *   1  initial surface temperature: the atmosphere's initial condition -> the prescribed one, with m = ocean fraction of
+ *      level 0 and target = slot 0's destination value:  interpolate ? m * target + (1 - m) * gen
+ *                                                                    : (round-half-even(m) == 1 ? target : gen)
+ *   2  ocean fraction over T levels.  ACE_COUPLE_OFRAC_CARRIED: source the atmosphere's own ocean fraction (T levels), the
+ *      destination may be NULL (nothing to mask: the caller keeps its tensor).  Otherwise source the land fraction (T levels):
+ *      sif0 = nan_to_num(slot 3's source) (NaN -> 0, +-inf -> +-FLT_MAX);
+ *      sea_ice(t) = sif0                       ACE_COUPLE_OFRAC_FROM_SIF        (one level: slot 3's step stride is not used)
+ *                 = sif0 * (1 - land(t))       ACE_COUPLE_OFRAC_FROM_OCEAN_SIF  (T levels)
+ *      ocean_fraction(t) = max((1 - land(t)) - sea_ice(t), 0) with NaN kept; each a single fp32 operation, never contracted
+ *   3  (predicting modes only) the ocean's sea-ice field -> sea_ice
+ *   4  (predicting modes only) the same source -> its unchanged values, for an atmosphere that names sea_ice differently;
+ *      destination NULL: not wanted
+ *   then npass pass-through fields of one time level each (3 + npass slots when carried, 5 + npass otherwise).
+ * The output is bitwise the reference's torch result where that is a number, NaN where it is NaN.
+ *
+ * atmosphere_to_ocean: for name j the mean over t of the n_inner planes srcs[j * n_inner + t] (sample stride
+ * src_strides[j * n_inner + t]), summed in t order in fp64, divided by n_inner and rounded to fp32 once, stored at time level
+ * slot[j] (0 or 1) of the two-level window dsts[j] ((sample, step) strides dst_strides[2j], [2j+1]); the other level is
+ * filled with quiet NaN.  NaN and +-inf propagate as the sum gives them.
+ * ------------------------------------------------------------------------------------------ */
+#define ACE_COUPLE_MAX_NAMES 64
+#define ACE_COUPLE_MAX_INNER 4096
+#define ACE_COUPLE_OFRAC_CARRIED 0
+#define ACE_COUPLE_OFRAC_FROM_SIF 1
+#define ACE_COUPLE_OFRAC_FROM_OCEAN_SIF 2
+const char* ace_couple_last_error(void);
+int ace_couple_ocean_to_atmosphere(const float* const* srcs, const long* src_strides, float* const* dsts,
+                                   const long* dst_strides, const float* const* masks, int npass, int mode, int interpolate,
+                                   int n_inner, int batch, long hw, void* stream);
+int ace_couple_atmosphere_to_ocean(const float* const* srcs, const long* src_strides, float* const* dsts,
+                                   const long* dst_strides, const int* slot, int nnames, int n_inner, int batch, long hw,
+                                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inference diagnostics (fme/ace/aggregator/inference: reduced.py, time_mean.py, spectrum.py), ace_amd/aggregator.py.
  * Deterministic: no float atomics, a fixed partition and combine order, fp64 accumulators; stream-ordered, no allocation
  * or host synchronisation.
