@@ -7,7 +7,7 @@ figures, ``get_dataset`` returns plain dicts of tensors, ``flush_diagnostics`` w
 stems (``<sub-aggregator>_diagnostics.pt`` for its ``.nc``, as ``TensorFileWriter`` writes ``restart.pt``), and the spectrum's SHT
 is the project's own forward transform.  Not built: the ``annual`` and ``enso_index`` sub-aggregators, step diagnostics, reference
 time means, HEALPix grids and the NaN flood fill before the spectrum (a masked name is listed in ``omitted`` instead).  The
-evaluator that compares a rollout with a target record (``InferenceEvaluatorAggregator``) is ace_amd/evaluator.py.
+evaluator that compares a rollout with a target record (``InferenceEvaluatorAggregator``) is ace_amd/evaluator/.
 
 Two paths compute the same thing.  The torch path (``fused = False``, any device) is the reference's formulas in fp32 torch ops.
 On the GPU (fp32 (B, T, H, W) fields with contiguous rows) a window is reduced by the HIP kernels of csrc/diag.hip, reading every
@@ -23,6 +23,7 @@ identical runs give bitwise identical diagnostics.  Peak extra device memory of 
 (B * T * names * ceil(H * W / 1024) * 4 * 24 bytes, 9.8 MB at 1 degree with 40 names and 40 steps) plus one spectrum chunk of at
 most ``spectrum_chunk_bytes`` (default 256 MiB: stacked planes and their coefficients)."""
 import dataclasses
+import itertools
 import os
 from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
@@ -168,8 +169,8 @@ class InferenceAggregator:
         forward SHT and one ``ace_diag_spectrum``."""
         return self._launches
 
-    def _pick(self, data: TensorMapping) -> str:
-        path = self.route(data)
+    def _pick(self, *data: TensorMapping) -> str:
+        path = self.route(*data)
         if self._path is None:
             self._path = path
         elif path != self._path:
@@ -279,17 +280,10 @@ class InferenceAggregator:
 
     # ---- the fused path ---------------------------------------------------------------------------------------------------
     def _ensure_rows(self, names: Sequence[str], dev):
-        new = [n for n in names if n not in self._rows]
-        if not new and self._series is not None:
-            return
-        for n in new:
-            self._rows[n] = len(self._rows)
-        R, HW = len(self._rows), self._shape[0] * self._shape[1]
-        lmax = self._get_sht().lmax
-        self._series = _grow(self._series, (2, R, self._n_time), torch.float64, dev)
-        self._tsum = _grow(self._tsum, (R, HW), torch.float64, dev)
-        self._spec = _grow(self._spec, (R, lmax), torch.float64, dev)
-        self._tables.clear()
+        HW = self._shape[0] * self._shape[1]
+        if _grow_rows(self, names, dev, _series=lambda R: (2, R, self._n_time), _tsum=lambda R: (R, HW),
+                      _spec=lambda R: (R, self._get_sht().lmax)):
+            self._tables.clear()
 
     def _weight_rows(self, names, dev) -> torch.Tensor:
         key = ("w", tuple(names))
@@ -324,12 +318,10 @@ class InferenceAggregator:
         self._ensure_rows(names, dev)
         wrows = self._weight_rows(names, dev)
         rows = self._row_table(names, dev)
-        values, off = _plane_table(names, data)
-        table = _upload(values, torch.int64, dev)
+        at, _ = _upload_planes(names, data, None, dev)
         n = len(names)
         lib = _lib.lib()
         partial = torch.empty(int(lib.ace_diag_partial_doubles(n, B, T, HW)), dtype=torch.float64, device=dev)
-        at = {k: table.data_ptr() + o for k, o in off.items()}
         # without the time series the window's series go to scratch (the kernel computes them with the same loads)
         series, n_time, t0 = self._series, self._n_time, i_time_start
         if not self._log_series:
@@ -483,11 +475,24 @@ def _grow(buf: Optional[torch.Tensor], shape, dtype, dev) -> torch.Tensor:
     return fresh
 
 
+def _grow_rows(owner, names: Sequence[str], dev, **buffers) -> bool:
+    """Give every new name of ``names`` the next row of ``owner._rows`` and, when there was one or a buffer is still ``None``, grow
+    the fp64 accumulators ``owner.<attribute>`` to ``shape(number of rows)``; True when it grew them."""
+    new = [n for n in names if n not in owner._rows]
+    if not new and all(getattr(owner, a) is not None for a in buffers):
+        return False
+    for n in new:
+        owner._rows[n] = len(owner._rows)
+    for a, shape in buffers.items():
+        setattr(owner, a, _grow(getattr(owner, a), shape(max(1, len(owner._rows))), torch.float64, dev))
+    return True
+
+
 def _plane_table(names: Sequence[str], gen: TensorMapping, target: Optional[TensorMapping] = None):
     """The int64 table through which the diag kernels read a window's (B, T, H, W) fields in place, and the byte offsets of its
     sections.  Per side (``gen``, then ``target`` when given) one pointer per name, then one (stride(0), stride(1)) pair per name; a
     name ``target`` lacks has pointer 0 and strides 0, 0.  Offsets: ``gen``, ``gen_strides``, with a target ``target`` and
-    ``target_strides``, and ``end``, where a caller appends sections of its own.  Uploading is the caller's (``_upload``)."""
+    ``target_strides``, and ``end``, where a caller appends sections of its own.  Uploading is ``_upload_planes``."""
     values: List[int] = []
     off: Dict[str, int] = {}
     for side, d in (("gen", gen),) if target is None else (("gen", gen), ("target", target)):
@@ -499,6 +504,18 @@ def _plane_table(names: Sequence[str], gen: TensorMapping, target: Optional[Tens
             values += (0, 0) if x is None else x.stride()[:2]
     off["end"] = 8 * len(values)
     return values, off
+
+
+def _upload_planes(names: Sequence[str], gen: TensorMapping, target: Optional[TensorMapping], dev, sections=()):
+    """A window's plane table and the caller's trailing ``sections`` (numpy arrays) to ``dev`` as one pinned blob, without
+    synchronising the host: (the device address of every offset of ``_plane_table``, the device address of every section)."""
+    import numpy as np
+    values, off = _plane_table(names, gen, target)
+    parts = [np.asarray(values, np.int64), *sections]
+    table = torch.from_numpy(np.concatenate([p.reshape(-1).view(np.uint8) for p in parts])).pin_memory().to(dev, non_blocking=True)
+    at = {k: table.data_ptr() + o for k, o in off.items()}
+    at["table"] = table                                                   # the caller keeps the blob alive through its call
+    return at, list(itertools.accumulate([p.nbytes for p in sections[:-1]], initial=at["end"])) if sections else []
 
 
 def _check(rc: int) -> None:

@@ -214,7 +214,7 @@ def test_a_short_tripole_record_emits_the_index_only():
     from ace_amd.evaluator import _Calendar
     c = C.main()
     agg = build(config(), c["info"], c["n_time"])
-    agg._calendar = _Calendar(agg, {"ipo_index": IpoIndexMetricConfig()}, c["info"])          # the build rule would leave it out
+    agg._families.append(_Calendar(agg, {"ipo_index": IpoIndexMetricConfig()}, c["info"]))    # the build rule would leave it out
     for (gen, tgt), time in c["windows"]:
         agg.record_batch(gen, tgt, time=time)
     g = torch.load(GOLDEN, weights_only=False)["main"]

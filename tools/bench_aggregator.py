@@ -7,7 +7,7 @@ window, timed with host syncs around each call after an untimed warm-up:
 and the fused overhead as a fraction of the window's rollout time (target: at most 2 %).
 Writes one JSON file and prints it.  usage: python tools/bench_aggregator.py [--steps 40] [--iters 5] [--out profiles/aggregator_bench.json]
 
---paired times the evaluator aggregator instead (ace_amd/evaluator.py): InferenceEvaluatorAggregator.record_batch on the same window
+--paired times the evaluator aggregator instead (ace_amd/evaluator/): InferenceEvaluatorAggregator.record_batch on the same window
 against a perturbed copy of it as target, fused (one ace_diag_paired_window per window) and on the torch path, alternated call by
 call on the same device, beside the rollout-window time; the JSON (default profiles/evaluator_aggregator_bench.json) states the
 aggregator's share of a window for both paths.  No speed-up is a target."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The evaluator's seasonal, annual, enso_index and ipo_index metrics (ace_amd/evaluator.py ``_Calendar``, csrc/calendar.hip) at 1
+"""The evaluator's seasonal, annual, enso_index and ipo_index metrics (ace_amd/evaluator/ ``_Calendar``, csrc/calendar.hip) at 1
 degree 180 x 360, 50 paired names (one of them ``sst``, which the two index metrics read), B = 1, T = 40 steps per window, on one
 MI355X: InferenceEvaluatorAggregator.record_batch with these four as the only metrics, fused (one ace_diag_calendar_window per
 window) and on the torch path, alternated call by call on the same device.  In ms per window, host syncs around each call after one

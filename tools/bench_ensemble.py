@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The evaluator's ensemble metrics and step means (ace_amd/evaluator.py ``_Ensembles``, ``_StepMeans``, csrc/ensemble.hip) at 1 degree
+"""The evaluator's ensemble metrics and step means (ace_amd/evaluator/ ``_Ensembles``, ``_StepMeans``, csrc/ensemble.hip) at 1 degree
 180 x 360, 50 paired names, 1 initial condition x 8 members, T = 40 steps per window, on one MI355X:
 InferenceEvaluatorAggregator.record_batch of the window that holds step 20, with one EnsembleMetricConfig(step=20) and the
 reference's two default step means (step 20, denorm and norm) as the only metrics, fused (the paired pass and one

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The evaluator's histogram metric (ace_amd/evaluator.py, csrc/hist.hip) at 1 degree 180 x 360, 40 paired names, B = 1, T = 40 steps
+"""The evaluator's histogram metric (ace_amd/evaluator/, csrc/hist.hip) at 1 degree 180 x 360, 40 paired names, B = 1, T = 40 steps
 per window, on one MI355X: InferenceEvaluatorAggregator.record_batch with the histogram as the only metric, fused (one
 ace_diag_hist_window per window) and on the torch path, alternated call by call on the same device, once on Gaussian fields and
 once on zero-inflated ones (a cubed half-Gaussian on 8 % of the pixels, exact zeros elsewhere: precipitation).  In ms per window,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The evaluator's trend, enso_coefficient and near_zero_fraction metrics (ace_amd/evaluator.py, csrc/regress.hip) at 1 degree
+"""The evaluator's trend, enso_coefficient and near_zero_fraction metrics (ace_amd/evaluator/, csrc/regress.hip) at 1 degree
 180 x 360, 50 paired names, B = 1, T = 40 steps per window, on one MI355X: InferenceEvaluatorAggregator.record_batch with these three
 as the only metrics (trend and the ENSO coefficient on every name, the near-zero fraction with maps on every name), fused (one
 ace_diag_regress_window per window) and on the torch path, alternated call by call on the same device.  In ms per window, host
