@@ -766,7 +766,7 @@ struct ace_sfno {
     DevBuf pe_slot;      // dynamic-range slot (64 words) holding max|pos_embed|: the residual bound of that convolution
     DevBuf phys;         // fused post-step physics (ace_step_physics): fp64 global sums, parameters
     int nstrips = 0;
-    DevBuf Wf0, bf0, Wf1, bf1;
+    DevBuf bf0, bf1;
     DevBuf amax;  // [8] uint words: bit patterns of max|X|, max|D|, max|E| of the current block (f16x3 dynamic range)  // instance-norm affine folded into inner_skip / mlp.fc1 weights, per sample
     bool taps_on = false;
     std::vector<DevBuf> taps;
@@ -774,6 +774,8 @@ struct ace_sfno {
     hipStream_t capture_stream = nullptr;
     long weights_generation = 0; // bumped by every ace_sfno_set_weight (ace_sfno_weights_generation)
     bool graphs_stale = false;   // a parameter was uploaded since the graphs were captured: re-capture lazily
+    mutable int norm_batch = 0;  // samples and stream of the last forward that enqueued instance norms (ace_sfno_norm_affine)
+    mutable hipStream_t norm_stream = nullptr;
     Switches sw;                 // measurement switches, read once at ace_sfno_create
 
     const float* w(const std::string& name) const {
@@ -995,11 +997,8 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
     }
     HIP_TRY(n->amax.alloc((size_t)(16 + 12 * c.num_layers + 1) * AMAX_SHARDS));   // + the conditioning field's slot
     if (c.normalization_layer == 1) {
-        const size_t cp = (size_t)((C + 31) & ~31);
-        HIP_TRY(n->Wf0.alloc((size_t)n->Bmax * C * cp));
         HIP_TRY(n->bf0.alloc((size_t)n->Bmax * C));
         if (c.use_mlp) {
-            HIP_TRY(n->Wf1.alloc((size_t)n->Bmax * n->hid * cp));
             HIP_TRY(n->bf1.alloc((size_t)n->Bmax * n->hid));
         }
     }
@@ -1027,7 +1026,7 @@ extern "C" long ace_sfno_workspace_size(const ace_sfno* n, int batch) {
     size_t fl = 0;
     auto add = [&](const DevBuf& b) { fl += b.n; };
     for (const DevBuf* b : {&n->h0, &n->h1, &n->Y, &n->T, &n->R, &n->U, &n->X, &n->D, &n->E, &n->stats, &n->P, &n->cln_stats, &n->inN,
-                            &n->P2, &n->part, &n->Wp0, &n->Wp1, &n->Wq1, &n->Wq0, &n->zero_c, &n->inP, &n->pe_slot, &n->Wf0, &n->bf0, &n->Wf1,
+                            &n->P2, &n->part, &n->Wp0, &n->Wp1, &n->Wq1, &n->Wq0, &n->zero_c, &n->inP, &n->pe_slot, &n->bf0,
                             &n->bf1, &n->amax, &n->phys})
         add(*b);
     for (const auto& t : n->taps) add(t);
@@ -1243,7 +1242,6 @@ struct BlockRoute {
     BlockBody body = BODY_PLAIN;
     ConvEngine skip = CONV_TILE, fc1 = CONV_NONE, fc2 = CONV_NONE;
     int skip_slot = -1, t_slot = -1; // range slots of the inner skip's input (-1: none, fp32 engine) and of the MLP's input
-    bool fold_skip = false, fold_fc1 = false;   // plain body, fp32 mode: the instance-norm affine folded into a per-sample fp32 weight
     bool pfold = false;              // fused body: fc1 folds its norm affine in the kernel's own prologue (conv_wl.hip at the ACE2 width)
     int t_nparts = 0;                // fused body: statistics partials per row the inner skip writes
     // fused body, fc2
@@ -1378,8 +1376,6 @@ static FwdRoute plan_route(const ace_sfno* n, int B, bool has_noise) {
             b.n0_to_planes = cln;
             b.n1_to_planes = cln && c.use_mlp && !n->taps_on;   // followed by the packed MLP, norm1's output exists as planes only
         } else {
-            b.fold_skip = norm && !b.scale_residual && !f16;
-            b.fold_fc1 = norm && c.use_mlp && !f16;
         }
     }
 
@@ -1532,12 +1528,6 @@ static int conv(const Fwd& f, const ConvW& cw, const float* in, long in_bstride,
         return ACE_OK;
     }
     HIP_TRY(launch_gemm(g, f.s));
-    return ACE_OK;
-}
-// the instance-norm affine (a, b) of the conv input folded into its weight: returns the per-sample operand
-static int fold(const Fwd& f, const ConvW& cw, int O, int I, const float* a, const float* b, float* Wf, float* bf, ConvW* out) {
-    HIP_TRY(launch_fold_affine(cw.w, cw.pitch, a, b, cw.bias, Wf, bf, f.B, O, I, f.s));
-    *out = ConvW{Wf, cw.pitch, (long)O * cw.pitch, bf, O};
     return ACE_OK;
 }
 
@@ -2062,16 +2052,17 @@ static int enqueue_packed_body(Fwd& f, int i, const BlockRoute& b) {
 }
 
 // Body of a block on the tile engines (fp32 mode, mixed-grid blocks, shapes the packed engine does not take): the convolutions
-// read fp32 and apply the instance-norm affine on load (f16x3) or from a per-sample folded weight (fp32)
+// read fp32 and apply the instance-norm affine on load.  (The fp32 mode used to fold it into a per-sample weight W diag(a),
+// bias + W b for the direct-to-LDS engine: the products W a x then carry the mean of x through the fp32 accumulation, and at
+// mean / std = 300 a block's output missed twice the fp32 reference's own error - tests/test_gpu_norm_dc.py (c).)
 static int enqueue_plain_body(Fwd& f, int i, const BlockRoute& b) {
     const ace_sfno* n = f.n;
     const int C = n->C, hid = n->hid, act = n->cfg.activation_function, sb = 16 + 12 * i;
     const long actB = f.actB();
     const std::string p = "blocks." + std::to_string(i) + ".";
     ConvW wskip = conv_weight(n, p + "inner_skip.weight", p + "inner_skip.bias");
-    if (b.fold_skip) ACE_TRY(fold(f, wskip, C, C, f.ra, f.rb, n->Wf0.p, n->bf0.p, &wskip));
     ACE_TRY(conv(f, wskip, f.res, actB, C, nullptr, 0, -1, n->T.p, C, n->Y.p, actB, nullptr, nullptr, act,
-                 b.fold_skip ? nullptr : f.ra, b.fold_skip ? nullptr : f.rb, f.slot(b.skip_slot), nullptr, f.slot(sb + 4)));
+                 f.ra, f.rb, f.slot(b.skip_slot), nullptr, f.slot(sb + 4)));
     MARK(ST_INNER_SKIP);
     const float *a1, *b1;
     bool n1_planes;
@@ -2081,9 +2072,8 @@ static int enqueue_plain_body(Fwd& f, int i, const BlockRoute& b) {
         return ACE_OK;
     }
     ConvW wfc1 = conv_weight(n, p + "mlp.fwd.0.weight", p + "mlp.fwd.0.bias");
-    if (b.fold_fc1) ACE_TRY(fold(f, wfc1, hid, C, a1, b1, n->Wf1.p, n->bf1.p, &wfc1));
     ACE_TRY(conv(f, wfc1, n->T.p, actB, C, nullptr, 0, -1, n->U.p, hid, nullptr, 0, nullptr, nullptr, act,
-                 b.fold_fc1 ? nullptr : a1, b.fold_fc1 ? nullptr : b1, f.slot(b.t_slot), nullptr, f.slot(sb + 6)));
+                 a1, b1, f.slot(b.t_slot), nullptr, f.slot(sb + 6)));
     MARK(ST_MLP_FC1);
     ACE_TRY(conv(f, conv_weight(n, p + "mlp.fwd.2.weight", p + "mlp.fwd.2.bias"), n->U.p, (long)hid * f.HW, hid, nullptr, 0, -1, f.hn,
                  C, f.res, actB, f.ra, f.rb, ACT_NONE, nullptr, nullptr, f.slot(sb + 6), nullptr, f.hslot(i + 1)));
@@ -2147,6 +2137,7 @@ static int forward_impl(const ace_sfno* n, const float* in, float* out, int B, h
         if (n->taps_on)
             HIP_TRY(hipMemcpyAsync(n->taps[i + 1].p, f.h, sizeof(float) * B * f.actB(), hipMemcpyDeviceToDevice, s));
     }
+    if (n->cfg.normalization_layer == 1 && n->cfg.num_layers > 0) { n->norm_batch = B; n->norm_stream = s; }
     return enqueue_decoder(f, out);
 }
 
@@ -2191,6 +2182,27 @@ extern "C" long ace_debug_read_workspace(ace_sfno* n, const char* which, void* d
 extern "C" int ace_sfno_sht_route(const ace_sfno* n, int* forward, int* inverse) {
     if (!n || !n->plan_lg) return fail(ACE_ERR_INVALID, "null argument");
     return ace_sht_plan_route(n->plan_lg.get(), forward, inverse);
+}
+// The instance-norm affine the last forward applied: tables (batch, C) of norm0 (which = 0) or norm1 (which = 1) of the LAST block
+// (the tables are shared by all blocks) and the range bound that norm published (maximum over the words of its slot; -1 where the
+// precision publishes none).  Synchronises the stream of that forward, launches nothing.
+extern "C" int ace_sfno_norm_affine(const ace_sfno* n, int which, float* scale, float* shift, float* bound) {
+    if (!n || !scale || !shift || !bound || which < 0 || which > 1) return fail(ACE_ERR_INVALID, "null argument / which outside {0, 1}");
+    if (n->norm_batch <= 0 || !n->stats.p) return fail(ACE_ERR_INVALID, "no instance-norm forward has run on this handle");
+    HIP_TRY(hipStreamSynchronize(n->norm_stream));
+    const size_t bc = (size_t)n->Bmax * n->C, nb = sizeof(float) * n->norm_batch * n->C;
+    const float* sc = n->stats.p + (which ? 2 * bc : 0);
+    HIP_TRY(hipMemcpy(scale, sc, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(shift, sc + bc, nb, hipMemcpyDeviceToHost));
+    *bound = -1.f;
+    if (const unsigned* slot = range_slot(n, 16 + 12 * (n->cfg.num_layers - 1) + (which ? 5 : 3))) {
+        unsigned words[AMAX_SHARDS];
+        HIP_TRY(hipMemcpy(words, slot, sizeof(words), hipMemcpyDeviceToHost));
+        unsigned m = 0;   // bit patterns of non-negative floats order like the floats
+        for (unsigned wd : words) m = wd > m ? wd : m;
+        std::memcpy(bound, &m, sizeof(float));
+    }
+    return ACE_OK;
 }
 extern "C" int ace_sfno_num_stages(void) { return ST_COUNT; }
 extern "C" const char* ace_sfno_stage_name(int i) { return (i >= 0 && i < ST_COUNT) ? kStageNames[i] : nullptr; }

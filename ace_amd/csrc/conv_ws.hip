@@ -55,15 +55,13 @@ constexpr int WS_OOBV = 0x7fffff00;   // buffer offset beyond every resource of 
 #define ACE_WS_VSPAN 8    // interleaved epilogue: its eight values are spread over the first VSPAN twelfths of the stage
 #endif
 
-
-#ifndef ACE_WS_MINMAX
-#define ACE_WS_MINMAX 0   // 1: the statistics epilogues also track a row's running minimum / maximum (rounds 3-6: the norm finaliser's bound came
-#endif                    // from them; it now comes from the variance - kernels.hip: instnorm_finalize_kernel - and the records carry +-3e38 there)
-constexpr bool WS_MINMAX = ACE_WS_MINMAX != 0;
-
-// v_min_f32 / v_max_f32 as single instructions: hipcc puts a canonicalising `v_max x, x` in front of fminf / fmaxf on a computed value
-__device__ __forceinline__ float raw_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float raw_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// Row statistics (STATS modes), one record per (workgroup slot, row) for instnorm_finalize_kernel (kernels.hip):
+//     (sum (x - p), sum (x - p)^2, p, n)   over the n pixels of the row the segment finished,
+// about a pivot p = the row's FIRST finished value of the segment.  Raw fp32 sums of x and x^2 lose (mean / std)^2 ulps of the
+// variance to cancellation (a per-channel constant from a trained bias or pos_embed: mean / std of 30 already misses the 1e-5 bar);
+// a value of the row itself lies within a few standard deviations of its mean wherever the constant comes from (bias, folded
+// residual shift, W . mean(residual) in the accumulator), so the shifted sums stay of the size of the variance.  The finaliser
+// merges records of different pivots in fp64.
 
 template <int KSW, int NSTG, int MODE>
 struct WsGeom {
@@ -127,7 +125,7 @@ MDEV void conv_ws_body(const ConvStripArgs& p, char* smem, const WsPlan pl) {
         // does not reach get a neutral partial; a group's slot is shared by its nslice workgroups, each answers for its slice.
         float4* pq = p.part + ((long)smp * p.nstrips32 + part_q) * p.M;
         for (int r = tid; r < p.M; r += 512)
-            if (ws_answers_for(pl, wk, w, r >> 7) && !ws_reaches(pl, wk, w, r >> 7)) pq[r] = make_float4(0.f, 0.f, 3.0e38f, -3.0e38f);
+            if (ws_answers_for(pl, wk, w, r >> 7) && !ws_reaches(pl, wk, w, r >> 7)) pq[r] = make_float4(0.f, 0.f, 0.f, 0.f);   // n = 0
     }
     if (nseg <= 0) return;   // (whole workgroup: no barrier has been executed yet)
 
@@ -181,8 +179,16 @@ MDEV void conv_ws_body(const ConvStripArgs& p, char* smem, const WsPlan pl) {
     const int T = sg.slice * 4 + (wave & 3);   // 32-row tile of the output channels
     const int NU = np * NSTG;
     if (!first) __syncthreads();               // the ring and the exchange buffers of the previous segment are free
+    if constexpr (RSTATS) {
+        // The idle epilogue pass in front of the first tile reads the partner's exchange buffer of tile parity 0 before anybody
+        // has written it, and it sets the statistics pivots (value - pivot = 0): it has to see FINITE values.  Zeros, visible to
+        // the partner behind the barrier that follows the weight load.
+        char* xw = xch + wave * 2048 + lane * 16;
+        *reinterpret_cast<f32x4*>(xw) = f32x4{0.f, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4*>(xw + 1024) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     if constexpr (STATS && !RSTATS) {          // running row statistics of this segment (lanes 0 - 15 of a wave own its 16 rows)
-        if (lane < 16) Lacc[lane] = f32x4{0.f, 0.f, 3.0e38f, -3.0e38f};
+        if (lane < 16) Lacc[lane] = f32x4{0.f, 0.f, 0.f, 0.f};   // (sum, sum of squares, pivot, count): count 0 = no pivot yet
     }
     // ---- streamed activation: piece k (of PW) of this wave for stage u -> slot u % 2; stages past the end re-fetch the last.
     //      Piece pc = (block pc / 2 of the stage: half hh, k-step jj; plane pc % 2): lane (i, g) fetches k-group 2 J + g, pixel i
@@ -250,14 +256,15 @@ MDEV void conv_ws_body(const ConvStripArgs& p, char* smem, const WsPlan pl) {
         float vals[8];
         f32x4 stv;
     };
-    struct TileCtx { int n0, vo_f, vo_p, vo_s, ncols_ok, i, g; };   // per pixel tile: offsets / validity of this lane
+    struct TileCtx { int n0, vo_f, vo_p, vo_s, ncols_ok, i, g; bool first, setpv; };   // per pixel tile: offsets / validity of this lane; first: the segment's first tile (sets the pivots), setpv: that or an idle pass
     EpiOut eo;
-    // RSTATS (inner skip: registers to spare): running sum / sum of squares / min / max of this lane's pixel column for the
-    // eight rows it finishes; reduced over the 32 pixel lanes once, at the end: ONE partial per workgroup and row instead of
-    // one per 32-pixel tile (80 instead of 2025 for the norm finaliser at 180 x 360), no LDS transpose, no per-tile store
-    float rsm[8], rsq[8], rmn[8], rmx[8];
+    // RSTATS (inner skip: registers to spare): running sum / sum of squares of this lane's pixel column for the eight rows it
+    // finishes, about the lane's OWN pivot rpv (its value of the segment's first tile); brought to a common pivot and reduced
+    // over the 32 pixel lanes once, at the end: ONE partial per workgroup and row instead of one per 32-pixel tile (80 instead
+    // of 2025 for the norm finaliser at 180 x 360), no LDS transpose, no per-tile store
+    float rsm[8], rsq[8], rpv[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { rsm[e] = 0.f; rsq[e] = 0.f; rmn[e] = 3.0e38f; rmx[e] = -3.0e38f; }
+    for (int e = 0; e < 8; ++e) { rsm[e] = 0.f; rsq[e] = 0.f; rpv[e] = 0.f; }
 #pragma unroll
     for (int e = 0; e < 8; ++e) { own[e] = 0.f; res[e] = 0.f; resn[e] = 0.f; eo.vals[e] = 0.f; }
 #pragma unroll
@@ -272,6 +279,8 @@ MDEV void conv_ws_body(const ConvStripArgs& p, char* smem, const WsPlan pl) {
         const bool nok = live && c.n0 + c.i < p.HW;
         c.vo_f = nok ? vf_lane : WS_OOBV; c.vo_p = nok ? vp_lane : WS_OOBV; c.vo_s = live ? vs_lane : WS_OOBV;
         c.ncols_ok = p.HW - c.n0 < 32 ? (p.HW - c.n0 > 0 ? p.HW - c.n0 : 0) : 32;
+        c.first = live && pt == 0;
+        c.setpv = !live || pt == 0;
         return c;
     };
     // item k < 8: value e = k; item 8: the stores of whole P entries and the row statistics
@@ -306,13 +315,10 @@ MDEV void conv_ws_body(const ConvStripArgs& p, char* smem, const WsPlan pl) {
             if (STATS && !RSTATS) St[(8 * g + e) * STP + i] = val;
             if (RSTATS) {
                 const bool ok = c.vo_p != WS_OOBV;   // a stored pixel of a live tile
-                rsm[e] += ok ? val : 0.f;
-                rsq[e] = ok ? fmaf(val, val, rsq[e]) : rsq[e];
-                if constexpr (WS_MINMAX) {
-                    const float lo_ = raw_min(rmn[e], val), hi_ = raw_max(rmx[e], val);
-                    rmn[e] = ok ? lo_ : rmn[e];
-                    rmx[e] = ok ? hi_ : rmx[e];
-                }
+                rpv[e] = c.first ? val : rpv[e];
+                const float vs = ok ? val - rpv[e] : 0.f;   // 0 is neutral for the sums
+                rsm[e] += vs;
+                rsq[e] = fmaf(vs, vs, rsq[e]);
             }
             if (PK) split_put<e>(o.hh, o.ll, cscale, val);
         } else {
@@ -325,37 +331,28 @@ MDEV void conv_ws_body(const ConvStripArgs& p, char* smem, const WsPlan pl) {
                 const int ln = i + 32 * g, r = ln & 15, cq = ln >> 4;
                 const f32x4 a = *reinterpret_cast<const f32x4*>(St + r * STP + 8 * cq);
                 const f32x4 b = *reinterpret_cast<const f32x4*>(St + r * STP + 8 * cq + 4);
-                float sm = 0.f, sq = 0.f, mn = 3.0e38f, mx = -3.0e38f;
+                // the row's pivot: kept with its running statistics once a tile has been counted, until then the first value of this
+                // tile (a live tile has at least one pixel).  The four lanes of a row read the same words: they agree on it.
+                const f32x4 run = Lacc[r];
+                const float pv = run[3] > 0.f ? run[2] : St[r * STP];
+                float sm = 0.f, sq = 0.f;
 #pragma unroll
                 for (int cc = 0; cc < 8; ++cc) {
                     const float x = cc < 4 ? a[cc & 3] : b[cc & 3];
                     const bool ok = 8 * cq + cc < c.ncols_ok;
-                    const float xs_ = ok ? x : 0.f;                                         // 0 is neutral for the sums
+                    const float xs_ = ok ? x - pv : 0.f;                                    // 0 is neutral for the sums
                     sm += xs_;
                     sq = fmaf(xs_, xs_, sq);
-                    if constexpr (WS_MINMAX) {
-                        const float xm_ = ok ? x : __builtin_nanf("");                      // a NaN for min / max
-                        mn = raw_min(mn, xm_);
-                        mx = raw_max(mx, xm_);
-                    }
                 }
 #pragma unroll
                 for (int off = 16; off <= 32; off <<= 1) {
                     sm += __shfl_xor(sm, off, 64);
                     sq += __shfl_xor(sq, off, 64);
-                    if constexpr (WS_MINMAX) {
-                        mn = raw_min(mn, __shfl_xor(mn, off, 64));
-                        mx = raw_max(mx, __shfl_xor(mx, off, 64));
-                    }
                 }
                 // ONE partial per workgroup and row instead of one per 32-pixel tile (r03: the norm finaliser read 2025 partials per
                 // channel, 6 KiB apart, and took 10 us): the row's running statistics live in LDS, always updated by the same lane
-                if (c.vo_s != WS_OOBV) {
-                    f32x4 acc = Lacc[ln];
-                    acc[0] += sm; acc[1] += sq;
-                    if constexpr (WS_MINMAX) { acc[2] = raw_min(acc[2], mn); acc[3] = raw_max(acc[3], mx); }
-                    Lacc[ln] = acc;
-                }
+                // (the other lanes' reads of it above are this wave's own, in program order)
+                if (c.vo_s != WS_OOBV) Lacc[ln] = f32x4{run[0] + sm, run[1] + sq, pv, run[3] + (float)c.ncols_ok};
             }
         }
     };
@@ -380,18 +377,15 @@ MDEV void conv_ws_body(const ConvStripArgs& p, char* smem, const WsPlan pl) {
             const float val = gelu_stage2(gst);
             gst.val = val;
             if (RSTATS) {
-                const bool ok = c.vo_p != WS_OOBV;   // a stored pixel of a live tile
-                // two selects instead of four: 0 is neutral for the sums, a NaN for v_min_f32 / v_max_f32 (they return the other operand)
-                const float vs = ok ? val : 0.f;
+                // (this form runs between the MFMAs of the NEXT tile only: the tile it finishes is not the segment's last, so every
+                // pixel of it exists - the one tile of a plane that can be ragged is the last of its segment, finished by epi_item -
+                // or it is the idle pass in front of the first tile.)  One wave-uniform select: while the pivot is being (re)set
+                // the value counts with deviation 0, which also keeps the idle pass out of the sums.
+                rpv[e] = c.setpv ? val : rpv[e];
+                const float vs = val - rpv[e];
                 rsm[e] += vs;
                 rsq[e] = fmaf(vs, vs, rsq[e]);
-                if constexpr (WS_MINMAX) {
-                    const float vm = ok ? val : __builtin_nanf("");
-                    rmn[e] = raw_min(rmn[e], vm);
-                    rmx[e] = raw_max(rmx[e], vm);
-                    asm volatile("" : "+v"(rmn[e]), "+v"(rmx[e]));
-                }
-                asm volatile("" : "+v"(rsm[e]), "+v"(rsq[e]));
+                asm volatile("" : "+v"(rsm[e]), "+v"(rsq[e]), "+v"(rpv[e]));
             }
             asm volatile("" : "+v"(gst.val));
         } else {
@@ -454,7 +448,7 @@ MDEV void conv_ws_body(const ConvStripArgs& p, char* smem, const WsPlan pl) {
 #pragma unroll
                 for (int k = 0; k < PW; ++k) piece(u + 1, k);
             }
-            TileCtx ctx = {0, WS_OOBV, WS_OOBV, WS_OOBV, 0, 0, 0};
+            TileCtx ctx = {0, WS_OOBV, WS_OOBV, WS_OOBV, 0, 0, 0, false, true};
             if constexpr (q == 0) {
                 read_partner(pt > 0 ? pt - 1 : 0);
                 if constexpr (INTER) {
@@ -554,24 +548,32 @@ MDEV void conv_ws_body(const ConvStripArgs& p, char* smem, const WsPlan pl) {
     read_partner(np - 1);
     epilogue(np - 1, true, eo_last);
     if constexpr (RSTATS) {   // statistics of the whole pixel range: reduce over the 32 pixel lanes (same g), one store per row
+        // this lane's pixel column counted nl tiles; the segment npx pixels.  Each lane's sums move from its own pivot to the one of
+        // its half's lane 0 (pixel 0 of the segment, always counted) - d is a difference of two values of the row, of the size of
+        // its standard deviation, so fp32 is enough: sum (x - P) = s + n d, sum (x - P)^2 = q + d (2 s + n d), d = p - P
+        const int rem = p.HW - 32 * tile0 - (lane & 31);
+        const float nl = (float)(rem <= 0 ? 0 : ((rem + 31) / 32 < np ? (rem + 31) / 32 : np));
+        const float npx = (float)(p.HW - 32 * tile0 < 32 * np ? p.HW - 32 * tile0 : 32 * np);
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
+        for (int e = 0; e < 8; ++e) {
+            const float P = __shfl(rpv[e], lane & 32, 64);
+            const float d = rpv[e] - P, nd = nl * d;
+            rsq[e] = fmaf(d, fmaf(2.f, rsm[e], nd), rsq[e]);
+            rsm[e] += nd;
+            rpv[e] = P;
 #pragma unroll
             for (int off = 1; off <= 16; off <<= 1) {
                 rsm[e] += __shfl_xor(rsm[e], off, 64);
                 rsq[e] += __shfl_xor(rsq[e], off, 64);
-                if constexpr (WS_MINMAX) {
-                    rmn[e] = fminf(rmn[e], __shfl_xor(rmn[e], off, 64));
-                    rmx[e] = fmaxf(rmx[e], __shfl_xor(rmx[e], off, 64));
-                }
             }
+        }
         // lanes 0 and 32 hold rows row0 + 8 g + e; part[(sample, slot) x M + row], slot = part_q of this workgroup
         const auto rsG = __builtin_amdgcn_make_buffer_rsrc(p.part + ((long)smp * p.nstrips32 + part_q) * p.M, 0, p.M * 16, 0x00020000);
         const int gq = lane >> 5;
         const int vo = (lane & 31) == 0 ? (row0 + 8 * gq) * 16 : WS_OOBV;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            st8[e] = f32x4{rsm[e], rsq[e], rmn[e], rmx[e]};
+            st8[e] = f32x4{rsm[e], rsq[e], rpv[e], npx};
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, st8[e]), rsG, vo, e * 16, 0);
         }
     }

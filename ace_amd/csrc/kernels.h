@@ -130,8 +130,8 @@ struct Gemm4Args {
     unsigned* cslot = nullptr;
     const unsigned* cinb = nullptr;
     const unsigned* rmax = nullptr;
-    // optional per-row statistics of the final values, one float4 (sum, sum sq, min, max) per (batch, 64-column strip,
-    // row): part[((batch * tilesN * WN + strip) * M + row)]
+    // optional per-row statistics of the final values, one float4 (sum (x - p), sum (x - p)^2, pivot p, count) per (batch,
+    // 64-column strip, row): part[((batch * tilesN * WN + strip) * M + row)]  (instnorm_finalize_kernel merges them)
     float4* part = nullptr;
     unsigned* omax = nullptr;                   // fp32 output: atomicMax of bits(max|C|)
     const float* bias = nullptr; long sbias = 0;
@@ -214,7 +214,7 @@ struct ConvStripArgs {
     const _Float16* Rhi = nullptr; const _Float16* Rlo = nullptr; long sRp = 0; const unsigned* rslot = nullptr;
     float cw = 0.f, cb = 0.f; const unsigned* cinb = nullptr; const unsigned* rmax = nullptr;   // output bound (see Gemm4Args)
     _Float16* Chi = nullptr; _Float16* Clo = nullptr; long sCp = 0; unsigned* cslot = nullptr;  // output planes [M/8][HW][8]
-    float4* part = nullptr; int nstrips32 = 0;        // optional row statistics per (sample, 32-pixel strip, row)
+    float4* part = nullptr; int nstrips32 = 0;        // optional row statistics per (sample, workgroup slot, row), same record
     int C = 0, M = 0, HW = 0, nbatch = 1, act = ACT_NONE;
     // second MLP convolution: fp32 output, per-row affine of the residual, range maximum
     float* Cf = nullptr; long sCf = 0;
@@ -357,11 +357,6 @@ hipError_t launch_expand_dhconv_weight(const float* w, float* wx, int Cin, int C
 // y = x * sc[row] + sh[row] + (r ? r * rsc[row] + rsh[row] : 0), rows of length n  (use_mlp=False tail, rare)
 hipError_t launch_rowaffine_add(const float* x, const float* sc, const float* sh, const float* r, const float* rsc,
                                 const float* rsh, float* y, long rows, long n, hipStream_t s);
-
-// fold a per-(sample, input-channel) affine (a, b) into a conv weight: Wf = W diag(a) (pitch ldw, zero padded),
-// bf = bias + W b.  W is (O, I) with pitch ldw.
-hipError_t launch_fold_affine(const float* W, long ldw, const float* a, const float* b, const float* bias, float* Wf,
-                              float* bf, int nsamples, int O, int I, hipStream_t s);
 
 // stepper glue (packer.py:45-52 + normalizer.py:213-236 fused)
 //   pack:   dst[b][j][:] = (src_j[b][:] - mean[j]) / std[j]   where src_j = srcs[j] + b*strides[j]

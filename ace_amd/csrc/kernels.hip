@@ -1913,7 +1913,7 @@ DEVINL void gemm4_body(const Gemm4Args& q, const int tilesM, const int tilesN) {
     // disjoint regions.
     //   phase 2 - read back row-contiguous (4 rows x 256 B per wave instruction): scales, bias, residual (16-byte loads),
     //             activation; optional fp32 store (16 B per lane); optional per-row statistics of the final values
-    //             (sum, sum of squares, min, max over this wave's 64 columns -> `part`, reduced later by
+    //             (shifted sum and sum of squares, their pivot, the count over this wave's 64 columns -> `part`, reduced later by
     //             instnorm_finalize_kernel: the fused instance norm of the NEXT layer needs no pass over the tensor);
     //   phase 3 - optional P-format output: final values go back to LDS and are re-read 8 rows x 1 column per lane,
     //             split hi/lo and stored as whole 16-byte entries (1 KiB per wave instruction).
@@ -2073,18 +2073,19 @@ DEVINL void gemm4_body(const Gemm4Args& q, const int tilesM, const int tilesN) {
                 if (ok) vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
                 if (PK) *reinterpret_cast<float4*>(Ts + rl * 64 + c4) = make_float4(o[0], o[1], o[2], o[3]);
                 if (part) {   // wave-uniform branch
-                    float sm = ok ? (o[0] + o[1]) + (o[2] + o[3]) : 0.f;
-                    float sq = ok ? fmaf(o[0], o[0], o[1] * o[1]) + fmaf(o[2], o[2], o[3] * o[3]) : 0.f;
-                    float mn = ok ? fminf(fminf(o[0], o[1]), fminf(o[2], o[3])) : 3.0e38f;
-                    float mx = ok ? fmaxf(fmaxf(o[0], o[1]), fmaxf(o[2], o[3])) : -3.0e38f;
+                    // sums about a pivot - the row's first value of this strip - so that a constant on the row costs the variance
+                    // nothing (record layout: instnorm_finalize_kernel).  A strip wholly beyond N counts nothing.
+                    const float pv = __shfl(o[0], lane & 48, 64);
+                    const float d0 = o[0] - pv, d1 = o[1] - pv, d2 = o[2] - pv, d3 = o[3] - pv;
+                    float sm = ok ? (d0 + d1) + (d2 + d3) : 0.f;
+                    float sq = ok ? fmaf(d0, d0, d1 * d1) + fmaf(d2, d2, d3 * d3) : 0.f;
 #pragma unroll
                     for (int off = 8; off > 0; off >>= 1) {   // the 16 lanes that share this row
                         sm += __shfl_xor(sm, off, 64);
                         sq += __shfl_xor(sq, off, 64);
-                        mn = fminf(mn, __shfl_xor(mn, off, 64));
-                        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
                     }
-                    if ((lane & 15) == 0 && row < M) part[row] = make_float4(sm, sq, mn, mx);
+                    const int left = N - (n0 + wn * 64);
+                    if ((lane & 15) == 0 && row < M) part[row] = make_float4(sm, sq, pv, (float)(left < 0 ? 0 : left > 64 ? 64 : left));
                 }
             }
         }
@@ -2718,10 +2719,10 @@ __global__ __launch_bounds__(512) void instnorm_stats_kernel(const float* __rest
             const float4 v = x4[j];
             lo = fminf(lo, fminf(fminf(v.x, v.y), fminf(v.z, v.w)));
             hi = fmaxf(hi, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
-            const float ps = (v.x + v.y) + (v.z + v.w);
-            const float pq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, v.w * v.w)));
-            s += (double)ps;
-            ss += (double)pq;
+            // every term in fp64: a sum of four squares rounded to fp32 first loses (mean / std)^2 ulps of the variance
+            const double a = (double)v.x, b = (double)v.y, c = (double)v.z, d = (double)v.w;
+            s += (a + b) + (c + d);
+            ss += fma(a, a, b * b) + fma(c, c, d * d);
         }
     } else {
         for (long j = threadIdx.x; j < HW; j += blockDim.x) {
@@ -2761,20 +2762,38 @@ __global__ __launch_bounds__(512) void instnorm_stats_kernel(const float* __rest
         scale[plane] = (float)sc;
         shift[plane] = (float)(bt - mean * sc);
         if (omax) {  // bound of |x * scale + shift| over the plane: consumers of the normalised field scale by it
+            // ... of the plane in exact arithmetic too: x, a and b each carry half an ulp of their own size, which a large mean
+            // (|a x| ~ |b| >> |a x + b|) turns into 2^-23 (|a| max|x| + |b|) of the result
             const float a = (float)sc, b = (float)(bt - mean * sc);
             const float bound = fmaxf(fabsf(fmaf(lo, a, b)), fabsf(fmaf(hi, a, b)));
-            atomicMax(omax + (plane & 63), __float_as_uint(bound));
+            const float slack = 1.1920929e-7f * fmaf(fabsf(a), fmaxf(fabsf(lo), fabsf(hi)), fabsf(b));
+            atomicMax(omax + (plane & 63), __float_as_uint(bound + slack));
         }
     }
 }
 
-// Second half of the fused instance norm: reduce the per-strip row statistics written by the producing GEMM's epilogue
-// (Gemm4Args::part) to the per-(sample, channel) affine, in fp64 and in a fixed order (deterministic).
-// The bound of the normalised plane published in `omax` is |a| sqrt(HW var) + |beta| >= max |a (x - mean) + beta| (no sample
+// Second half of the fused instance norm: merge the per-strip row statistics written by the producing kernel's epilogue
+// (Gemm4Args::part, ConvStripArgs::part) to the per-(sample, channel) affine, in fp64 and in a fixed order (deterministic).
+// A record is (sum (x - p), sum (x - p)^2, p, n): sums over n values of the row about a pivot p the producer chose among them
+// (n = 0: a neutral record).  The variance comes from the MERGED second central moment - no sum x^2 / HW - mean^2, whose
+// cancellation costs (mean / std)^2 ulps (and can publish a bound of 0 for a plane that is not constant):
+// two sets of sums merge pairwise by bringing the second to the pivot of the first:  d = p_b - p_a,
+//       sum (x - p_a) = s_a + s_b + n_b d,   sum (x - p_a)^2 = q_a + q_b + d (2 s_b + n_b d)
+// - the pairwise update of Chan et al. about a carried pivot instead of the running mean (no division per merge); d is a
+// difference of two values of the row, so in fp64 nothing cancels.  At the end mean = p + s / n, M2 = q - s^2 / n.
+// The bound of the normalised plane published in `omax` is |a| sqrt(M2) + |beta| >= max |a (x - mean) + beta| (no sample
 // lies further from the mean than sqrt(sum (x - mean)^2)): it needs no running minimum / maximum in the producers' epilogues
 // (12 % of their vector instructions).  It is up to sqrt(HW) / (max |x - mean| / sigma) - 2^5 .. 2^6 at 180 x 360 - looser than
-// the true maximum; the hi / lo operands keep their 22 bits while a bound is within 2^14 of the maximum.  The
-// (min, max) fields of a record are ignored.
+// the true maximum; the hi / lo operands keep their 22 bits while a bound is within 2^14 of the maximum.
+struct PivotSums { double n, s, q, p; };   // count, sum (x - p), sum (x - p)^2, pivot
+__device__ __forceinline__ void pivot_merge(PivotSums& a, double nb, double sb, double qb, double pb) {
+    const double p = a.n > 0.0 ? a.p : pb;   // an empty set takes the other's pivot (then d = 0)
+    const double d = pb - p;
+    a.s += sb + nb * d;
+    a.q += qb + d * (2.0 * sb + nb * d);
+    a.n += nb;
+    a.p = p;
+}
 __global__ __launch_bounds__(256) void instnorm_finalize_kernel(const float4* __restrict__ part, int nparts, int C,
                                                                 long HW, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, float eps,
@@ -2788,40 +2807,29 @@ __global__ __launch_bounds__(256) void instnorm_finalize_kernel(const float4* __
     const int b = blockIdx.y;
     const int cs = threadIdx.x & 3, pr = threadIdx.x >> 2;   // 0..3, 0..63
     const int c = blockIdx.x * 4 + cs;
-    double s = 0.0, ss = 0.0;
-    float lo = 3.0e38f, hi = -3.0e38f;
+    PivotSums t = {0.0, 0.0, 0.0, 0.0};
     if (c < C) {
         const float4* base = part + (long)b * nparts * C + c;
 #pragma unroll 4
         for (int p = pr; p < nparts; p += 64) {
             const float4 v = base[(long)p * C];
-            s += (double)v.x;
-            ss += (double)v.y;
-            lo = fminf(lo, v.z);
-            hi = fmaxf(hi, v.w);
+            pivot_merge(t, (double)v.w, (double)v.x, (double)v.y, (double)v.z);
         }
     }
 #pragma unroll
-    for (int off = 4; off < 64; off <<= 1) {   // lanes of this wave with the same channel sub-index
-        s += __shfl_xor(s, off, 64);
-        ss += __shfl_xor(ss, off, 64);
-        lo = fminf(lo, __shfl_xor(lo, off, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    }
-    __shared__ double rs[4][4], rss[4][4];
-    __shared__ float rlo[4][4], rhi[4][4];
+    for (int off = 4; off < 64; off <<= 1)   // lanes of this wave with the same channel sub-index (lanes 0 - 3 keep the result)
+        pivot_merge(t, __shfl_xor(t.n, off, 64), __shfl_xor(t.s, off, 64), __shfl_xor(t.q, off, 64), __shfl_xor(t.p, off, 64));
+    __shared__ double rn[4][4], rs[4][4], rq[4][4], rp[4][4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane < 4) { rs[wave][lane] = s; rss[wave][lane] = ss; rlo[wave][lane] = lo; rhi[wave][lane] = hi; }
+    if (lane < 4) { rn[wave][lane] = t.n; rs[wave][lane] = t.s; rq[wave][lane] = t.q; rp[wave][lane] = t.p; }
     __syncthreads();
     if (threadIdx.x < 4 && c < C) {
-        s = rs[0][cs]; ss = rss[0][cs]; lo = rlo[0][cs]; hi = rhi[0][cs];
-        for (int k = 1; k < 4; ++k) {
-            s += rs[k][cs]; ss += rss[k][cs];
-            lo = fminf(lo, rlo[k][cs]); hi = fmaxf(hi, rhi[k][cs]);
-        }
-        const double mean = s / (double)HW;
-        double var = ss / (double)HW - mean * mean;  // biased variance
-        if (var < 0.0) var = 0.0;
+        t = PivotSums{rn[0][cs], rs[0][cs], rq[0][cs], rp[0][cs]};
+        for (int k = 1; k < 4; ++k) pivot_merge(t, rn[k][cs], rs[k][cs], rq[k][cs], rp[k][cs]);
+        const double mean = t.n > 0.0 ? t.p + t.s / t.n : 0.0;
+        double m2 = t.n > 0.0 ? t.q - t.s * t.s / t.n : 0.0;
+        if (m2 < 0.0) m2 = 0.0;
+        const double var = m2 / (double)HW;   // biased variance (the records cover the HW pixels of the plane: n == HW)
         const double rstd = 1.0 / sqrt(var + (double)eps);
         const double g = gamma ? (double)gamma[c] : 1.0;
         const double bt = beta ? (double)beta[c] : 0.0;
@@ -2829,8 +2837,7 @@ __global__ __launch_bounds__(256) void instnorm_finalize_kernel(const float4* __
         const float a = (float)sc, bb = (float)(bt - mean * sc);
         scale[(long)b * C + c] = a;
         shift[(long)b * C + c] = bb;
-        (void)lo; (void)hi;
-        if (omax) atomicMax(omax + ((b * C + c) & 63), __float_as_uint((float)(fabs(sc) * sqrt((double)HW * var) * (1.0 + 1e-6) + fabs(bt))));
+        if (omax) atomicMax(omax + ((b * C + c) & 63), __float_as_uint((float)(fabs(sc) * sqrt(m2) * (1.0 + 1e-6) + fabs(bt))));
     }
 }
 hipError_t launch_instnorm_finalize(const float4* part, int nparts, int Bt, int C, long HW, const float* gamma,
@@ -3088,9 +3095,9 @@ hipError_t launch_expand_dhconv_weight(const float* w, float* wx, int Cin, int C
 // normalized_shape = (H, W), eps 1e-6, elementwise affine of shape (H, W) shared by all channels): per (sample, channel) plane
 //     y[p] = (x[p] - mean) / sqrt(var + eps) * gamma[p] + beta[p]        (biased variance, fp64 sums in a fixed order)
 // One workgroup per plane, two passes (the second one's reads come from L2); in place allowed.  omax (optional): atomicMax of the bit
-// pattern of max |y| - the range slot of the packed convolutions that read y.
-__global__ __launch_bounds__(512) void spatial_layer_norm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, float eps, long HW, float* __restrict__ y,
+// pattern of max |y| - the range slot of the packed convolutions that read y.  (x and y are NOT __restrict__: every caller passes x == y.)
+__global__ __launch_bounds__(512) void spatial_layer_norm_kernel(const float* x, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, float eps, long HW, float* y,
                                                                  unsigned* omax) {
     const float* xp = x + (long)blockIdx.x * HW;
     float* yp = y + (long)blockIdx.x * HW;
@@ -3215,44 +3222,6 @@ hipError_t launch_unpack_denormalize(const float* src, const float* mean, const 
     if (gx > 64) gx = 64;
     hipLaunchKernelGGL(unpack_denormalize_kernel, dim3(gx, nch, Bt), dim3(256), 0, s, src, mean, stdv, dsts, strides,
                        nch, HW);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// fold a per-(sample, input-channel) affine into a 1x1-conv weight:  W (a x + b) + bias = (W diag(a)) x + (W b + bias)
-//   Wf[s][o][i] = W[o][i] * a[s][i]  (columns i in [I, ldw) are zero),   bf[s][o] = bias[o] + sum_i W[o][i] * b[s][i]
-// This is how the instance norm (sfnonet.py:218-221, 234-238) reaches the direct-to-LDS GEMM, which cannot touch its
-// B operand: ~0.6-1.2 MB of work per conv instead of a 100 MB normalised activation.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(128) void fold_affine_kernel(const float* __restrict__ W, long ldw,
-                                                          const float* __restrict__ a, const float* __restrict__ b,
-                                                          const float* __restrict__ bias, float* __restrict__ Wf,
-                                                          float* __restrict__ bf, int O, int I) {
-    const int o = blockIdx.x, smp = blockIdx.y;
-    const float* wr = W + (long)o * ldw;
-    float* wo = Wf + ((long)smp * O + o) * ldw;
-    const float* as = a + (long)smp * I;
-    const float* bs = b + (long)smp * I;
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < (int)ldw; i += blockDim.x) {
-        float v = 0.f;
-        if (i < I) {
-            const float w = wr[i];
-            v = w * as[i];
-            acc += (double)w * (double)bs[i];
-        }
-        wo[i] = v;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    __shared__ double red[2];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) bf[(long)smp * O + o] = (float)((bias ? (double)bias[o] : 0.0) + red[0] + red[1]);
-}
-hipError_t launch_fold_affine(const float* W, long ldw, const float* a, const float* b, const float* bias, float* Wf,
-                              float* bf, int nsamples, int O, int I, hipStream_t s) {
-    hipLaunchKernelGGL(fold_affine_kernel, dim3(O, nsamples), dim3(128), 0, s, W, ldw, a, b, bias, Wf, bf, O, I);
     return hipGetLastError();
 }
 

@@ -200,6 +200,10 @@ int ace_sfno_forward_conditioned_timed(ace_sfno* net, const float* in, const flo
 int ace_sfno_num_stages(void);
 /* ace_sht_plan_route of the network's internal (legendre-gauss) plan after a forward. */
 int ace_sfno_sht_route(const ace_sfno* net, int* forward, int* inverse);
+/* Test instrumentation: the instance-norm affine the last forward applied.  which 0: norm0, 1: norm1, of the LAST block (all blocks
+   share the tables).  scale / shift: host arrays of batch * embed_dim floats; bound: the range bound that norm published (-1 when the
+   precision publishes none).  Synchronises the stream of that forward; ACE_ERR_INVALID when no instance-norm forward has run. */
+int ace_sfno_norm_affine(const ace_sfno* net, int which, float* scale, float* shift, float* bound);
 const char* ace_sfno_stage_name(int i);
 int ace_sfno_forward_timed(ace_sfno* net, const float* in, float* out, int batch, void* stream, float* ms_host,
                            int* calls_host);

@@ -70,6 +70,28 @@ def test_instance_norm(dev, n, c, hw):
     assert rel_max(y, ref) <= OP_TOL
 
 
+@pytest.mark.parametrize("mean_over_std", [0, 30, 300, 1e4])
+@pytest.mark.parametrize("n,c,hw", [(2, 16, 162), (3, 5, 77), (2, 16, 164), (1, 3, 2052)])   # H W % 4 != 0: the scalar branch; the float4 one, a row per thread and four
+def test_instance_norm_under_a_large_mean(dev, n, c, hw, mean_over_std):
+    """The stand-alone ace_instance_norm (instnorm_stats_kernel: fp64 sums of x and x^2) when every channel carries a constant of
+    mean_over_std standard deviations, random sign per channel.  Truth: F.instance_norm in fp64; bar max(OP_TOL, 4 floor) with the
+    floor F.instance_norm in fp32 gives on the same data (2 for another rounding order x 2 for the fp32 affine the kernel applies)."""
+    from ace_amd import _lib
+    g = torch.Generator().manual_seed(7)
+    sign = torch.randint(0, 2, (c,), generator=g).float() * 2 - 1
+    x = torch.randn(n, c, hw, generator=g) * 3 + (3 * mean_over_std * sign)[None, :, None]
+    gamma, beta = torch.randn(c, generator=g), torch.randn(c, generator=g)
+    ref = torch.nn.functional.instance_norm(x.double(), weight=gamma.double(), bias=beta.double(), eps=1e-6)
+    floor = rel_max(torch.nn.functional.instance_norm(x, weight=gamma, bias=beta, eps=1e-6), ref)
+    xd, gd, bd = x.to(dev), gamma.to(dev), beta.to(dev)
+    y = torch.empty_like(xd)
+    _lib.check(_lib.lib().ace_instance_norm(_lib.ptr(xd), _lib.ptr(gd), _lib.ptr(bd), 1e-6,
+                                            _lib.ptr(y), n, c, hw, _lib.current_stream()))
+    err = rel_max(y, ref)
+    print(f"instance norm ({n}, {c}, {hw}) mean/std {mean_over_std:g}: err {err:.3e}, fp32 reference floor {floor:.3e}")
+    assert err <= max(OP_TOL, 4 * floor), (err, floor)
+
+
 # ---------------------------------------------------------------------------------- SHT
 @pytest.mark.parametrize("n,c,j,hw,affine,cond", [(2, 16, 8, 288, True, True), (1, 384, 32, 4132, True, True),
                                                    (3, 5, 4, 64, False, True), (2, 24, 0, 100, True, False),
