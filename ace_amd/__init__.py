@@ -31,6 +31,7 @@ from .stepper import PrognosticState, Stepper  # noqa: F401
 from .ocean_rollout import OceanRolloutEngine  # noqa: F401
 from .coupled import (ComponentConfig, ComponentStepPrediction, CoupledDatasetInfo, CoupledOceanFractionConfig,  # noqa: F401
                       CoupledStepper, CoupledStepperConfig, Coupler, load_coupled_stepper)
+from .coupled_rollout import CoupledEnginePredict, CoupledRolloutEngine, plan_coupled_window  # noqa: F401
 from .inference import EnginePredict, ForcingWindows, InferenceData, Looper, TensorFileWriter, repeat_members, run_evaluator, run_inference  # noqa: F401
 from .evaluator import InferenceEvaluatorAggregator, InferenceEvaluatorAggregatorConfig  # noqa: F401
 

@@ -177,6 +177,7 @@ SIGNATURES = {
     "ace_couple_last_error": (c_char_p, []),
     # srcs, src_strides, dsts, dst_strides, masks, npass, mode, interpolate, n_inner, batch, hw, stream
     "ace_couple_ocean_to_atmosphere": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_long, c_void_p]),
+    "ace_couple_ocean_to_atmosphere_window": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_long, c_void_p]),      # the same arguments
     # srcs, src_strides, dsts, dst_strides, slot, nnames, n_inner, batch, hw, stream
     "ace_couple_atmosphere_to_ocean": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_long, c_void_p]),
     "ace_diag_last_error": (c_char_p, []),

@@ -17,7 +17,8 @@ on any device; on CUDA fp32 (the default there) the exchange is two native calls
 ocean -> atmosphere products are bitwise the torch path's.  The means differ by rounding only: the kernel accumulates in fp64 and
 rounds once, the reference's fp32 ``mean`` rounds at every addition.
 
-Not here (follow-ups): a coupled rollout engine / graph capture, a coupled inference loop, aggregators, training, ensembles."""
+The coupled rollout on static windows with graph capture is ``CoupledRolloutEngine`` (coupled_rollout.py).  Not here
+(follow-ups): a coupled inference loop, aggregators, training, ensembles."""
 import dataclasses
 import datetime
 import pathlib

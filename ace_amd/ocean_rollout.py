@@ -51,13 +51,14 @@ def _refuse(what: str) -> NotImplementedError:
 
 
 class OceanRolloutEngine(WindowEngine):
-    def __init__(self, stepper: Stepper, batch: int, n_forward_steps: int, graph: Optional[str] = "step"):
-        self._check_graph(graph)
+    @staticmethod
+    def check_supported(stepper: Stepper):
+        """The refusals that need no device, raised before any device work (the constructor's first act).  Returns the stepper's
+        (input masker, output masker), each None when it is no static spatial masking."""
         from .ocean_corrector import OceanCorrector
         from .samudra import Samudra
         step = stepper._step_obj
         cfg = step.config
-        # ---- refusals: all before any device work
         net = step.module.torch_module
         if not isinstance(net, Samudra):
             if hasattr(net, "_ensure_native"):      # the SFNO family
@@ -86,6 +87,14 @@ class OceanRolloutEngine(WindowEngine):
                         raise _refuse(f"the mask '{k}' of shape {tuple(t.shape)} is not a 2-D {tuple(step._img_shape)} plane")
         if next(net.parameters()).device.type != "cuda":
             raise RuntimeError("OceanRolloutEngine runs on an MI355X: load the stepper onto a 'cuda' device (there is no CPU path)")
+        return in_mask, out_mask
+
+    def __init__(self, stepper: Stepper, batch: int, n_forward_steps: int, graph: Optional[str] = "step"):
+        self._check_graph(graph)
+        in_mask, out_mask = self.check_supported(stepper)
+        step = stepper._step_obj
+        net = step.module.torch_module
+        corrector = step._corrector
 
         super().__init__(stepper, net, batch, n_forward_steps, graph)
         dev, B, T, H, W, HW = self.device, batch, n_forward_steps, self.H, self.W, self.HW

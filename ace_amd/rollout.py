@@ -44,10 +44,14 @@ class WindowEngine:
         if graph not in (None, "step", "window"):
             raise ValueError("graph must be None, 'step' or 'window'")
 
-    def __init__(self, stepper: Stepper, net, batch: int, n_forward_steps: int, graph: Optional[str], next_data=()):
+    def __init__(self, stepper: Stepper, net, batch: int, n_forward_steps: int, graph: Optional[str], next_data=(),
+                 in_override: Optional[Mapping[Tuple[str, int], torch.Tensor]] = None):
+        """``in_override``: (name, s) -> the (B, H, W) plane input `name` of step s is read from instead of the window's own
+        (a coupled rollout's prescribed initial surface temperature, coupled_rollout.py); none by default."""
         step = stepper._step_obj
         cfg = step.config
         self.stepper, self.net, self.graph_mode = stepper, net, graph
+        self._in_override = dict(in_override or {})
         self.device = dev = next(net.parameters()).device
         self.B, self.T = B, T = batch, n_forward_steps
         self.H, self.W = H, W = step._img_shape
@@ -85,7 +89,10 @@ class WindowEngine:
 
     # -- the window layout: the (B, H, W) plane of a name at window position s
     def in_plane(self, n: str, s: int, forcing: Optional[Mapping[str, torch.Tensor]] = None) -> torch.Tensor:
-        """Input n of step s: the initial condition / step s - 1's output, or the forcing at s (s + 1 for next_step_forcing_names)."""
+        """Input n of step s: the initial condition / step s - 1's output, or the forcing at s (s + 1 for next_step_forcing_names);
+        an override of (n, s) given at construction comes first."""
+        if (n, s) in self._in_override:
+            return self._in_override[(n, s)]
         if n in self.ic:
             return self.ic[n][:, 0] if s == 0 else self.out[n][:, s - 1]
         return (self.forcing if forcing is None else forcing)[n][:, s + 1 if n in self.next_step_forcing else s]
@@ -189,14 +196,11 @@ class RolloutEngine(WindowEngine):
     # graph="step" (ADVICE r05).  8 GiB = a 40-step window of ~290 conditioning channels at 1 degree.
     max_window_conditioning_bytes = 8 << 30
 
-    def __init__(self, stepper: Stepper, batch: int, n_forward_steps: int, graph: Optional[str] = "step"):
-        self._check_graph(graph)
+    @staticmethod
+    def check_supported(stepper: Stepper, graph: Optional[str]) -> None:
+        """What the engine refuses of a stepper as it stands, raised before any device work (the constructor's first act)."""
         step = stepper._step_obj
-        cfg = step.config
-        # secondary decoder (fme/core/step/secondary_decoder.py): column-local diagnostics decoded from the network's normalised
-        # output tensor - one more native module call on the static y buffer per step and a second fused unpack
-        self._secondary = getattr(step, "secondary_decoder", None)
-        if self._secondary is not None and graph == "window":
+        if getattr(step, "secondary_decoder", None) is not None and graph == "window":
             raise NotImplementedError("graph='window' with a secondary decoder: its module call is not captured; use graph='step'")
         from .ocean_corrector import OceanCorrector
         if isinstance(step._corrector, OceanCorrector):
@@ -205,11 +209,21 @@ class RolloutEngine(WindowEngine):
         if getattr(stepper, "_masks", False):
             raise NotImplementedError("RolloutEngine: static spatial masking of the step inputs / outputs (input_masking, the dataset's "
                                       "mask provider) is applied by Stepper.predict")
+        if getattr(stepper, "_multi_call_config", None) is not None and graph == "window":
+            raise NotImplementedError("graph='window' with multi-call diagnostics is not captured; use graph='step'")
+
+    def __init__(self, stepper: Stepper, batch: int, n_forward_steps: int, graph: Optional[str] = "step",
+                 in_override: Optional[Mapping[Tuple[str, int], torch.Tensor]] = None):
+        self._check_graph(graph)
+        self.check_supported(stepper, graph)
+        step = stepper._step_obj
+        cfg = step.config
+        # secondary decoder (fme/core/step/secondary_decoder.py): column-local diagnostics decoded from the network's normalised
+        # output tensor - one more native module call on the static y buffer per step and a second fused unpack
+        self._secondary = getattr(step, "secondary_decoder", None)
         # multi-call diagnostics (fme/core/step/multi_call.py): per multiplier one more pack (the scaled forcing) / forward / unpack
         # into scratch planes / hooks per step, selected outputs copied under their suffixed names
         self._mc = getattr(stepper, "_multi_call_config", None)
-        if self._mc is not None and graph == "window":
-            raise NotImplementedError("graph='window' with multi-call diagnostics is not captured; use graph='step'")
         # post-step hooks (corrector, prescribed-SST ocean): torch ops on the static buffers between the fused unpack of
         # step s and the pack of step s + 1 - stream ordered, no host synchronisation.  The corrector state (dry-air
         # reference mass) is seeded by the first step after load() and survives continue_from_last().
@@ -245,7 +259,7 @@ class RolloutEngine(WindowEngine):
         # next-step data the hooks read that is not a network forcing input (e.g. the prescribed SST: prognostic AND target)
         self.prescribed = list(cfg.prescribed_prognostic_names)
         extra = set(cfg.ocean.forcing_names) if cfg.ocean is not None else set()
-        super().__init__(stepper, net, batch, n_forward_steps, graph, next_data=extra | set(self.prescribed))
+        super().__init__(stepper, net, batch, n_forward_steps, graph, next_data=extra | set(self.prescribed), in_override=in_override)
         dev, B, T, H, W = self.device, batch, n_forward_steps, self.H, self.W
         f32 = dict(dtype=torch.float32, device=dev)
         i64 = dict(dtype=torch.int64, device=dev)
@@ -416,6 +430,10 @@ class RolloutEngine(WindowEngine):
 
     def load(self, initial_condition: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor]):
         super().load(initial_condition, forcing)
+        self._after_load()
+
+    def _after_load(self):
+        """What a freshly loaded window resets besides its buffers."""
         self._corrector_state = None        # a new initial condition re-seeds the corrector
         self._mc_state = None
         if self._mc is not None:
@@ -451,6 +469,9 @@ class RolloutEngine(WindowEngine):
             if self._conditioned and self.graph_mode == "window":
                 self._draw_window_conditioning()
             super().run_window()
+        self._after_window()
+
+    def _after_window(self):
         if self.graph_mode == "window" and self._have_ref is not None and self._physics is None:
             # host-side view of the hook state the captured region keeps in its static buffer (a replay does not run
             # the Python that set it at capture time); a copy, so that a state handed out survives the next load()
