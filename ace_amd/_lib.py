@@ -207,6 +207,9 @@ SIGNATURES = {
     # gen, gen_strides, target, target_strides, rows, maps, seen, nrows, slot, nslots, pair_weight, t, nplanes, n_ic, n_members, steps,
     # hw, stream
     "ace_diag_ensemble_step": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_double] + [c_int] * 5 + [c_long, c_void_p]),
+    "ace_diag_fill_scratch_doubles": (c_long, [c_int, c_int, c_int, c_int, c_int]),
+    # srcs, strides, tab, layers, blurred, nmasks, scratch, dst, nnames, batch, steps, nlat, nlon, stream
+    "ace_diag_fill_planes": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
 }
 
 _lib = None

@@ -24,7 +24,9 @@ reference's non-strict path does (main.py:143-153; ``strict=True`` raises), are 
 ENSO coefficient whose record is too short, an ``enso_coefficient`` without an index, a ``trend`` over fewer than two forward steps.
 ``video``, a bare enabled ``seasonal``, ``histogram``, ``trend`` or ``near_zero_fraction``, the reference-data paths, a ``variables``
 filter on a paired metric and HEALPix grids raise ``NotImplementedError``.  As in ace_amd/aggregator.py, tensors and floats stand
-where the reference logs images and figures, and a name whose mask has zeros is left out of the spectrum and listed in ``omitted``.
+where the reference logs images and figures, and a name whose mask has zeros is left out of the spectrum and listed in ``omitted`` - unless ``power_spectrum.fill_masked`` is on
+(the reference's behaviour; off by default): then its masked pixels are flood-filled before the SHT (ace_amd/fill.py, fused:
+``ace_diag_fill_planes``), it takes part in the spectrum and the bias scores and is listed in ``filled``.
 
 Paired metrics cover the names present in both mappings, ``weighted_mean_gen`` / ``weighted_std_gen`` every generated name; a target
 name without a prediction is refused (the reference indexes ``gen[name]`` for every target name, reduced.py:190-196).

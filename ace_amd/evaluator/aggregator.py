@@ -26,9 +26,9 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
                  trend: Optional[TrendMetricConfig] = None, enso_coefficient: Optional[EnsoCoefficientMetricConfig] = None,
                  near_zero_fraction: Optional[NearZeroFractionMetricConfig] = None,
                  calendar: Optional[Mapping[str, MetricConfig]] = None, step_means: Sequence[StepMeanMetricConfig] = (),
-                 ensembles: Sequence[EnsembleMetricConfig] = (), n_ensemble_per_ic: int = 1):
+                 ensembles: Sequence[EnsembleMetricConfig] = (), n_ensemble_per_ic: int = 1, fill_masked: bool = False):
         super().__init__(dataset_info, n_ic_steps + n_forward_steps, True, output_dir, save_diagnostics, sht_factory,
-                         spectrum_chunk_bytes)
+                         spectrum_chunk_bytes, fill_masked_spectrum=fill_masked)
         self.n_ensemble_per_ic = int(n_ensemble_per_ic)
         self.n_ic_steps = int(n_ic_steps)
         self.skipped = list(skipped)
@@ -80,7 +80,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         ``record_batch`` when the histogram is on, one ``ace_diag_regress_window`` per window of ``record_batch`` when any of
         trend, enso_coefficient and near_zero_fraction is on (a second one for the ENSO term of a window at time index 0), and
         one ``ace_diag_ensemble_step`` per ensemble entry and window that holds its step, and per spectrum chunk of either side
-        one forward SHT and one ``ace_diag_spectrum``."""
+        one forward SHT and one ``ace_diag_spectrum`` - three with ``power_spectrum.fill_masked``: one ``ace_diag_fill_planes``
+        ahead of them."""
         return self._launches
 
     def calendar_launches(self) -> int:

@@ -24,7 +24,11 @@ class ZonalMeanMetricConfig(MetricConfig):
 
 @dataclasses.dataclass
 class PowerSpectrumMetricConfig(MetricConfig):
+    """``fill_masked`` (not a field of the reference, which always fills): flood-fill the masked pixels of a masked name before the
+    SHT (``SmoothFloodFill(num_steps=4)``, spectrum.py:331; ace_amd/fill.py) instead of omitting the name.  The reference's
+    behaviour is ``True``; the default ``False`` keeps what the evaluator computed before the fill was built."""
     report_directional_bias: bool = True                                  # spectrum.py:317-322
+    fill_masked: bool = False
 
 
 @dataclasses.dataclass
@@ -344,4 +348,4 @@ class InferenceEvaluatorAggregatorConfig:
             report_directional_bias=getattr(self.power_spectrum, "report_directional_bias", True), output_dir=output_dir,
             save_diagnostics=save_diagnostics, sht_factory=sht_factory,
             histogram=self.histogram if self.histogram.enabled else None, calendar=calendar, **regress, **stepped,
-            n_ensemble_per_ic=int(n_ensemble_per_ic))
+            n_ensemble_per_ic=int(n_ensemble_per_ic), fill_masked=bool(getattr(self.power_spectrum, "fill_masked", False)))

@@ -333,9 +333,11 @@ class _Paired:
 
 class _Spectrum:
     """``power_spectrum`` (spectrum.py:112-276): the mean spectra of prediction and target over samples and steps and their bias
-    scores, of the names whose mask has no zeros (``agg.omitted`` lists the others).  Torch path: the running mean of
-    metrics.py:388-408 per name; fused path: per chunk of names one SHT and one ``ace_diag_spectrum`` for each side, adding to
-    ``_spec`` (2, rows, lmax) fp64, rows by ``agg._rows``."""
+    scores, of the names whose mask has no zeros (``agg.omitted`` lists the others) and, with ``fill_masked`` - the reference's
+    behaviour, off by default - of the masked names with a valid pixel too, flood-filled first (``agg.filled``; ace_amd/fill.py).
+    Torch path: the running mean of metrics.py:388-408 per name; fused path: per chunk of names one SHT and one
+    ``ace_diag_spectrum`` for each side, adding to ``_spec`` (2, rows, lmax) fp64, rows by ``agg._rows``; with ``fill_masked`` one
+    ``ace_diag_fill_planes`` builds the SHT's input in place of the ``torch.stack``, three launches per chunk and side."""
     needs_time = uses_time = needs_norm = False
     counted = True
 
@@ -355,7 +357,7 @@ class _Spectrum:
             for n in names:
                 old = self._counts[side].get(n, 0)
                 if not w.fused:
-                    mean_ps = torch.mean(torch.sum(abs(sht(d[n])) ** 2, dim=-1), dim=(0, 1))      # metrics.py:388-408
+                    mean_ps = torch.mean(torch.sum(abs(sht(agg._fill_torch(n, d[n]))) ** 2, dim=-1), dim=(0, 1))      # metrics.py:388-408
                     acc = self._t_spec[side]
                     acc[n] = mean_ps if n not in acc else (BT * mean_ps + old * acc[n]) / (BT + old)
                 self._counts[side][n] = old + BT
@@ -368,12 +370,15 @@ class _Spectrum:
             self._spec = _grow(self._spec, (2, len(agg._rows), L), torch.float64, dev)
         k = max(1, agg.spectrum_chunk_bytes // (w.B * w.T * (H * W * 4 + L * M * 8)))
         acc = self._spec.data_ptr() + side * self._spec.shape[1] * L * 8
+        total = 0
         for c0 in range(0, len(names), k):
             chunk = names[c0:c0 + k]
-            coeffs = sht(torch.stack(fields[c0:c0 + k]))                          # (k, B, T, L, M) complex64
+            planes, made = agg._spectrum_input(chunk, fields[c0:c0 + k], dev)
+            coeffs = sht(planes)                                                  # (k, B, T, L, M) complex64
             _check(_lib.lib().ace_diag_spectrum(coeffs.data_ptr(), agg._row_table(chunk, dev).data_ptr(), acc, self._spec.shape[1],
                                                 len(chunk), w.B * w.T, L, M, _lib.current_stream()))
-        return 2 * len(range(0, len(names), k))
+            total += 2 + made
+        return total
 
     def _spectra(self) -> Dict[str, torch.Tensor]:
         """spectrum.py:67-77, 207-215: name -> (2, lmax) [prediction, target] mean spectra; the target row of a name without a

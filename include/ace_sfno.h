@@ -477,6 +477,42 @@ int ace_couple_atmosphere_to_ocean(const float* const* srcs, const long* src_str
  *                  2 <= n_members <= ACE_DIAG_ENSEMBLE_MAX_MEMBERS = 32; other counts are refused, as are t outside [0, steps),
  *                  slot outside [0, nslots) and n_ic < 1.  nplanes == 0 is a no-op.  Each pixel is owned by one thread: no
  *                  atomics, bitwise repeatable.  One launch however many planes; no allocation, no host synchronisation.
+ *   diag_fill_planes: the smooth flood fill of masked fields ahead of the spectrum (fme/core/fill.py: SmoothFloodFill with its only
+ *                  instantiation, num_steps = ACE_DIAG_FILL_STEPS = 4 and a 5-tap Gaussian of sigma 1; spectrum.py:331), fused with
+ *                  the stacking of a spectrum chunk: dst, a contiguous DEVICE fp32 [nnames][batch][steps][nlat][nlon], is the
+ *                  SHT's whole input.  srcs / strides: as diag_window, planes of nlat * nlon contiguous fp32 starting at any
+ *                  4-byte boundary.  tab: DEVICE int [nnames], the mask table of name n in [0, nmasks); any other value (-1):
+ *                  the planes of name n are copied unchanged, bit for bit.  Tables, built once per distinct mask on the host
+ *                  (ace_amd/fill.py: fill_tables): layers DEVICE uint8 [nmasks][nlat * nlon], blurred DEVICE fp32
+ *                  [nmasks][nlat * nlon].
+ *                  Valid set of a mask: where it is non-zero (the rule of the weights and of ``omitted``; not the reference's
+ *                  "NaN pattern of the first plane seen" - the two agree when the data is NaN exactly where the mask is zero).
+ *                  A value at a masked pixel is never read into the result.
+ *                  layers.  grow(S) = S and every pixel with a pixel of S in its 3 x 3 neighbourhood, longitude circular, rows
+ *                  beyond the poles empty.  Simulation A: A_0 = valid, A_k = grow(A_k-1); what A_4 leaves out is the interior,
+ *                  layer 5.  Simulation B: B_0 = valid and interior (the reference marks the interior valid before its expansion
+ *                  loop, fill.py:267-268), B_k = grow(B_k-1); a masked pixel first in B_k has layer k (1..4), a valid pixel layer
+ *                  0.  A pixel beside the interior is filled from the inside at step 1: layers taken from simulation A alone
+ *                  are wrong there.  A byte above 5 marks a pixel that is never known and never filled.
+ *                  blurred = blur(the 0 / 1 valid plane) computed in fp64 and rounded once to fp32, with blur(x) = the 5-tap
+ *                  Gaussian g (exp(-q^2 / 2) / their sum, q = -2..2, fp64) along latitude, rows clamped to [0, nlat - 1]
+ *                  (replicate), then along longitude, circular.
+ *                  Per plane: x = the source at valid pixels, 0 at masked ones, then m = (sum of x over valid pixels) / (their
+ *                  number) at interior pixels (computed only when the table has one).  For k = 1..4 every layer-k pixel takes (sum
+ *                  of x over its 3 x 3 neighbours of layer 0, 5 or < k) / (their number), longitude circular, rows beyond the
+ *                  poles not counted.  Then out = x * bv + blur(x) * (1 - bv), bv = blurred; where bv == 1 out = x and the blur
+ *                  is not formed.  m, every neighbour sum, each blur pass and the blend are fp64 without contraction, in a fixed
+ *                  order, and each is rounded once to fp32 (at most eight fp32 roundings on the way to a pixel; every stage is a
+ *                  convex combination, so |out - the fp64 statement| <= 2^-21 max|valid x|).  A plane of a table with no valid
+ *                  pixel comes out all NaN.  A non-finite value at a valid pixel propagates; how far is not specified.
+ *                  scratch: DEVICE fp64 of ace_diag_fill_scratch_doubles(nnames, batch, steps, nlat, nlon) values (-1 for arguments
+ *                  this call would refuse); may be NULL when nmasks is 0.  Smallest grid: nlat >= ACE_DIAG_FILL_MIN_NLAT = 2,
+ *                  nlon >= ACE_DIAG_FILL_MIN_NLON = 8; nnames * batch * steps * ceil(nlat / ACE_DIAG_FILL_TILE_H) *
+ *                  ceil(nlon / ACE_DIAG_FILL_TILE_W) < 2^31.  A refused call returns ACE_ERR_INVALID and writes nothing;
+ *                  nnames == 0 is a no-op.  One workgroup per ACE_DIAG_FILL_TILE_H x ACE_DIAG_FILL_TILE_W tile and plane holds the
+ *                  tile and a halo of 6 in LDS: one read of the source, one write of dst, no intermediate in device memory.  Two
+ *                  launches (the plane means, the tiles), one when nmasks is 0; each pixel is written by one thread: no atomics,
+ *                  bitwise repeatable; no allocation, no host synchronisation.
  * ------------------------------------------------------------------------------------------ */
 const char* ace_diag_last_error(void);
 long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
@@ -512,6 +548,15 @@ int ace_diag_calendar_window(const float* const* gen, const long* gen_strides, c
 int ace_diag_ensemble_step(const float* const* gen, const long* gen_strides, const float* const* target, const long* target_strides,
                            const int* rows, double* maps, int* seen, int nrows, int slot, int nslots, double pair_weight,
                            int t, int nplanes, int n_ic, int n_members, int steps, long hw, void* stream);
+#define ACE_DIAG_FILL_STEPS 4
+#define ACE_DIAG_FILL_TILE_H 32
+#define ACE_DIAG_FILL_TILE_W 64
+#define ACE_DIAG_FILL_MIN_NLAT 2
+#define ACE_DIAG_FILL_MIN_NLON 8
+long ace_diag_fill_scratch_doubles(int nnames, int batch, int steps, int nlat, int nlon);
+int ace_diag_fill_planes(const float* const* srcs, const long* strides, const int* tab, const unsigned char* layers,
+                         const float* blurred, int nmasks, double* scratch, float* dst, int nnames, int batch, int steps, int nlat,
+                         int nlon, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
