@@ -51,6 +51,8 @@ Switches read_switches() {
     sw.no_strip = on("ACE_NO_STRIP");
     sw.no_fold = on("ACE_NO_FOLD");
     sw.no_dhconv_strip = on("ACE_NO_DHCONV_STRIP");
+    sw.no_polar_cut = on("ACE_NO_POLAR_CUT");
+    sw.polar_poison = on("ACE_POLAR_POISON");
 #ifdef ACE_MEASUREMENT_SWITCHES   // historical routings: measurement builds only (tools/mkvar.sh NAME -DACE_MEASUREMENT_SWITCHES)
     sw.no_pk = on("ACE_NO_PK");
     sw.no_pk_sht = on("ACE_NO_PK_SHT");
@@ -101,6 +103,14 @@ struct DevBuf {
         return e;
     }
     hipError_t ensure(size_t count) { return count <= n ? hipSuccess : alloc(count); }
+    // a spectral scratch X[m][lat][...]: zeroed, or (ACE_POLAR_POISON) quiet NaNs - once, when it is allocated.  The polar cut leaves
+    // the dead entries unwritten, so a kernel that read one would show
+    hipError_t alloc_x(size_t count, bool poison) {
+        hipError_t e = alloc(count);
+        if (e == hipSuccess && poison && count) e = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), 0x7fc00000, count);
+        return e;
+    }
+    hipError_t ensure_x(size_t count, bool poison) { return count <= n ? hipSuccess : alloc_x(count, poison); }
     hipError_t upload(const std::vector<float>& h) {
         hipError_t e = alloc(h.size(), false);
         if (e != hipSuccess) return e;
@@ -127,6 +137,11 @@ struct ace_sht_plan {
     // ... and in the equatorially folded form (strip_fold.hip) when the tables are mirror-symmetric about the equator
     DevBuf wt_ffrag, pt_ffrag, wt_foff, pt_foff;
     bool fold = false;
+    // ... with the polar cut (strip_pack.h, PolarCut): r0[mmax] / mcut[nlat] as device int arrays; kdrop: the forward fragments start
+    // at k16-step r0[m] / 16 (small form)
+    DevBuf cut_r0, cut_mcut;
+    bool cut = false, kdrop = false;
+    double cut_share = 0.0;
     DevBuf slots;   // standalone transforms in f16x3 mode: dynamic-range slots (max|X|, max|coefficients|)
     Switches sw;    // measurement switches, read when the plan was built
     // which kernel family the last Legendre launch of each direction took (ace_sht_plan_route): 0 tile engine, 1 strip.hip,
@@ -196,11 +211,31 @@ static int plan_build(int nlat, int nlon, int lmax, int mmax, Grid g, std::uniqu
         if ((t.nlat + 1) / 2 <= 16 * FOLD_NKP_BIG && (t.lmax + 1) / 2 <= 16 * FOLD_NKP_BIG && !p->sw.no_fold &&
             fold_symmetry_error(t.wt.data(), t.mmax, t.nlat, t.lmax, t.Hp, 0) < 2e-6 &&
             fold_symmetry_error(t.pt.data(), t.mmax, t.nlat, t.lmax, t.Lp, 1) < 2e-6) {
-            StripPack sp;
+            StripPack sp, spi;
             pack_legendre_fold(t.wt.data(), t.mmax, t.nlat, t.lmax, t.Hp, 0, p->wt_scale, sp);
+            pack_legendre_fold(t.pt.data(), t.mmax, t.nlat, t.lmax, t.Lp, 1, p->pt_scale, spi);
+            if (!p->sw.no_polar_cut) {
+                // the (m, folded latitude) pairs whose fragments are all zero in both packs: never stored, loaded or multiplied
+                const PolarCut pc = derive_polar_cut(sp, spi, t.mmax, t.nlat, t.lmax);
+                if (pc.ok && pc.dead_share > 0.0) {
+                    auto upi = [](const std::vector<int>& v, DevBuf& d) -> hipError_t {
+                        const hipError_t e = d.alloc(v.size(), false);
+                        return e != hipSuccess ? e : hipMemcpy(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice);
+                    };
+                    HIP_TRY(upi(pc.r0, p->cut_r0));
+                    HIP_TRY(upi(pc.mcut, p->cut_mcut));
+                    p->cut = true;
+                    p->cut_share = pc.dead_share;
+                    if (fold_geom(0, 0, t.lmax, t.nlat).nkp2 <= FOLD_NKP_SMALL) {   // small form: the wholly dead leading k16-steps leave the table
+                        std::vector<int> kskip(pc.r0.size());
+                        for (size_t m = 0; m < kskip.size(); ++m) kskip[m] = pc.r0[m] / 16;
+                        pack_legendre_fold(t.wt.data(), t.mmax, t.nlat, t.lmax, t.Hp, 0, p->wt_scale, sp, kskip.data());
+                        p->kdrop = true;
+                    }
+                }
+            }
             HIP_TRY(up(sp, p->wt_ffrag, p->wt_foff));
-            pack_legendre_fold(t.pt.data(), t.mmax, t.nlat, t.lmax, t.Lp, 1, p->pt_scale, sp);
-            HIP_TRY(up(sp, p->pt_ffrag, p->pt_foff));
+            HIP_TRY(up(spi, p->pt_ffrag, p->pt_foff));
             p->fold = true;
         }
     }
@@ -212,8 +247,9 @@ static int plan_build(int nlat, int nlon, int lmax, int mmax, Grid g, std::uniqu
 static int run_dft_forward(const ace_sht_plan& pl, const float* x, const float* sc, const float* sh, float* X, int Bt,
                            int C, hipStream_t s, unsigned* xmax = nullptr, const _Float16* xhi = nullptr,
                            const _Float16* xlo = nullptr, long sxp = 0, const unsigned* xslot = nullptr,
-                           const PackFragArgs* ride = nullptr, bool* rode = nullptr) {
+                           const PackFragArgs* ride = nullptr, bool* rode = nullptr, const int* mcut = nullptr) {
     DftArgs a;
+    a.mcut = mcut;   // forward_pair_mcut: only when the Legendre launch that follows honours the cut
     if (rode) *rode = false;
     if (ride && rode) { a.ride = *ride; a.nride = pack_frag_blocks(*ride); a.rode = rode; }   // a weight-packing job riding in the launch (pack_frag.h)
     a.omax = xmax;
@@ -223,18 +259,24 @@ static int run_dft_forward(const ace_sht_plan& pl, const float* x, const float* 
     HIP_TRY(launch_dft_forward(a, s));
     return ACE_OK;
 }
-static int run_dft_inverse(const ace_sht_plan& pl, const float* X, const float* bias, float* y, int Bt, int C,
-                           hipStream_t s, unsigned* ymax = nullptr) {
+static DftArgs dft_inverse_args(const ace_sht_plan& pl, const float* X, const float* bias, float* y, int Bt, int C, unsigned* ymax) {
     DftArgs a;
     a.omax = ymax;
     a.spec = X; a.y = y; a.tc = pl.gc.p; a.ts = pl.gs.p; a.ldt = pl.Kfp; a.bias = bias;
     a.Bt = Bt; a.C = C; a.H = pl.nlat; a.W = pl.nlon; a.Mm = pl.mmax; a.no_fft = pl.sw.no_fft;
+    return a;
+}
+static int run_dft_inverse(const ace_sht_plan& pl, const float* X, const float* bias, float* y, int Bt, int C,
+                           hipStream_t s, unsigned* ymax = nullptr, const int* mcut = nullptr) {
+    DftArgs a = dft_inverse_args(pl, X, bias, y, Bt, C, ymax);
+    a.mcut = mcut;   // inverse_pair: only behind the folded Legendre kernel
     HIP_TRY(launch_dft_inverse(a, s));
     return ACE_OK;
 }
 // D[l][m][n2] = sum_k wt[m][l][k] X[m][k][n2]   (sht_fix.py:134-138), batched over m, rows l >= m only
+// dry: decide the route (pl.route[0]) without launching anything
 static int run_legendre_forward(const ace_sht_plan& pl, const float* X, float* D, long N2, hipStream_t s,
-                                const unsigned* xmax = nullptr, unsigned* dmax = nullptr, bool planes = false) {
+                                const unsigned* xmax = nullptr, unsigned* dmax = nullptr, bool planes = false, bool dry = false) {
     GemmArgs g;
     g.omax = planes ? nullptr : dmax;
     g.A = pl.wt.p; g.lda = pl.Hp; g.sA = (long)pl.lmax * pl.Hp;
@@ -259,19 +301,21 @@ static int run_legendre_forward(const ace_sht_plan& pl, const float* X, float* D
         if (pl.fold && !pl.sw.no_fold) {   // half the contraction: sums / differences of mirror latitudes (strip_fold.hip)
             LegStripArgs f = a;
             f.A = reinterpret_cast<const _Float16*>(pl.wt_ffrag.p); f.tile_off = reinterpret_cast<const int*>(pl.wt_foff.p);
+            if (pl.cut) { f.r0 = reinterpret_cast<const int*>(pl.cut_r0.p); f.kdrop = pl.kdrop; }   // the window is safe behind any producer
             if (legendre_fold_eligible(f)) {
-                HIP_TRY(launch_legendre_fold(f, s));
+                if (!dry) HIP_TRY(launch_legendre_fold(f, s));
                 pl.route[0] = fold_route(f);
                 return ACE_OK;
             }
         }
         if (pl.strip && legendre_strip_eligible(a)) {
-            HIP_TRY(launch_legendre_strip(a, s));
+            if (!dry) HIP_TRY(launch_legendre_strip(a, s));
             pl.route[0] = 1;
             return ACE_OK;
         }
     }
     pl.route[0] = 0;
+    if (dry) return ACE_OK;
     if (planes) {
         // D as fp16 hi/lo planes in D's own layout [l][m][n2] (the buffer holds two planes instead of one fp32 tensor):
         // the dhconv contracts over n2's channel index, so this IS the v4 engine's A operand.  dmax receives the bound.
@@ -290,8 +334,9 @@ static int run_legendre_forward(const ace_sht_plan& pl, const float* X, float* D
 }
 // X[m][k][n2] = sum_{l>=m} pt[m][k][l] E[l][m][n2]   (sht_fix.py:208-219), batched over m
 // dry: decide the route (pl.route[1]) without launching anything
+// skip_dead (inverse_pair): the folded kernel neither stores nor computes the entries of the polar cut
 static int run_legendre_inverse(const ace_sht_plan& pl, const float* E, float* X, long N2, hipStream_t s,
-                                const unsigned* emax = nullptr, bool dry = false) {
+                                const unsigned* emax = nullptr, bool dry = false, bool skip_dead = false) {
     GemmArgs g;
     g.A = pl.pt.p; g.lda = pl.Lp; g.sA = (long)pl.nlat * pl.Lp;
     g.B = E; g.ldb = (long)pl.mmax * N2; g.sB = N2;
@@ -308,6 +353,7 @@ static int run_legendre_inverse(const ace_sht_plan& pl, const float* E, float* X
         if (pl.fold && !pl.sw.no_fold) {   // even / odd degrees separately, rows and mirror rows from their sum and difference
             LegStripArgs f = a;
             f.A = reinterpret_cast<const _Float16*>(pl.pt_ffrag.p); f.tile_off = reinterpret_cast<const int*>(pl.pt_foff.p);
+            if (pl.cut && skip_dead) f.r0 = reinterpret_cast<const int*>(pl.cut_r0.p);
             if (legendre_fold_eligible(f)) {
                 if (!dry) HIP_TRY(launch_legendre_fold(f, s));
                 pl.route[1] = fold_route(f);
@@ -328,6 +374,38 @@ static int run_legendre_inverse(const ace_sht_plan& pl, const float* E, float* X
     }
     HIP_TRY(launch_gemm(g, s));
     return ACE_OK;
+}
+
+// ---- pairing of the polar cut -------------------------------------------------------------------------------------------------
+// An entry of X that its producer does not store is only safe when the consumer does not read it.  Both halves of a pair are
+// decided HERE, before the pair's first kernel is enqueued, from the predicates the launches themselves use (the dry route queries):
+//   forward   the FFT drops its dead stores only when the Legendre launch that follows takes the folded kernel of the same plan (whose
+//             descriptor window is on whenever the plan has a cut: reading less is safe behind any producer)
+//   inverse   the folded Legendre kernel skips its dead stores and tiles only when the two-level FFT follows with the cutoff; the FFT
+//             drops its dead loads whenever the Legendre launch was the folded one (exact zeros there; the tile engine and the fp32
+//             path leave rounding-level values, which it keeps reading)
+// Everything else - matrix DFT widths, ACE_NO_FFT / ACE_NO_FOLD / ACE_NO_STRIP, strip.hip, fp32 plans - runs as without the cut.
+static const int* forward_pair_mcut(const ace_sht_plan& pl, const float* X, float* D, long N2, const unsigned* xmax, unsigned* dmax,
+                                    bool planes) {
+    if (!pl.cut) return nullptr;
+    const int before = pl.route[0];
+    const int rc = run_legendre_forward(pl, X, D, N2, nullptr, xmax, dmax, planes, true);
+    const bool folded = rc == ACE_OK && pl.route[0] >= 2;
+    pl.route[0] = before;
+    return folded ? reinterpret_cast<const int*>(pl.cut_mcut.p) : nullptr;   // (the matrix DFT kernels do not look at it)
+}
+struct InversePair { bool skip_dead = false; const int* mcut = nullptr; };
+static InversePair inverse_pair(const ace_sht_plan& pl, const float* E, float* X, long N2, const unsigned* emax, float* y, int Bt, int C) {
+    InversePair pr;
+    if (!pl.cut) return pr;
+    const int before = pl.route[1];
+    const int rc = run_legendre_inverse(pl, E, X, N2, nullptr, emax, true);
+    const bool folded = rc == ACE_OK && pl.route[1] >= 2;
+    pl.route[1] = before;
+    if (!folded) return pr;
+    pr.mcut = reinterpret_cast<const int*>(pl.cut_mcut.p);
+    pr.skip_dead = dft_inverse_fft_takes(dft_inverse_args(pl, X, nullptr, y, Bt, C, nullptr));
+    return pr;
 }
 
 extern "C" int ace_sht_plan_create_ex(int nlat, int nlon, int lmax, int mmax, const char* grid, int precision,
@@ -367,7 +445,7 @@ extern "C" int ace_sht_forward(ace_sht_plan* p, const float* x, float* coeffs, i
     if (!p || !x || !coeffs || n <= 0) return fail(ACE_ERR_INVALID, "ace_sht_forward: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long N2 = 2L * n;
-    HIP_TRY(p->X.ensure(((size_t)p->mmax * p->nlat + LEG_STRIP_SLACK_ROWS) * N2));
+    HIP_TRY(p->X.ensure_x(((size_t)p->mmax * p->nlat + LEG_STRIP_SLACK_ROWS) * N2, p->sw.polar_poison));
     HIP_TRY(p->D.ensure(((size_t)p->lmax + LEG_STRIP_SLACK_ROWS) * p->mmax * N2));
     // coefficients with l < m are never written by the triangular Legendre stage: the layout converter writes their zeros
     // without reading the scratch (no memset)
@@ -376,8 +454,10 @@ extern "C" int ace_sht_forward(ace_sht_plan* p, const float* x, float* coeffs, i
         xmax = reinterpret_cast<unsigned*>(p->slots.p);
         HIP_TRY(launch_zero_u32(xmax, 2 * AMAX_SHARDS, s));
     }
-    ACE_TRY(run_dft_forward(*p, x, nullptr, nullptr, p->X.p, 1, n, s, xmax));
-    ACE_TRY(run_legendre_forward(*p, p->X.p, p->D.p, N2, s, xmax, xmax ? xmax + AMAX_SHARDS : nullptr));
+    unsigned* dmax = xmax ? xmax + AMAX_SHARDS : nullptr;
+    const int* mcut = forward_pair_mcut(*p, p->X.p, p->D.p, N2, xmax, dmax, false);
+    ACE_TRY(run_dft_forward(*p, x, nullptr, nullptr, p->X.p, 1, n, s, xmax, nullptr, nullptr, 0, nullptr, nullptr, nullptr, mcut));
+    ACE_TRY(run_legendre_forward(*p, p->X.p, p->D.p, N2, s, xmax, dmax));
     HIP_TRY(launch_spec_to_ref(p->D.p, coeffs, 1, n, p->lmax, p->mmax, s));
     return ACE_OK;
 }
@@ -385,7 +465,7 @@ extern "C" int ace_sht_inverse(ace_sht_plan* p, const float* coeffs, float* x, i
     if (!p || !x || !coeffs || n <= 0) return fail(ACE_ERR_INVALID, "ace_sht_inverse: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long N2 = 2L * n;
-    HIP_TRY(p->X.ensure(((size_t)p->mmax * p->nlat + LEG_STRIP_SLACK_ROWS) * N2));
+    HIP_TRY(p->X.ensure_x(((size_t)p->mmax * p->nlat + LEG_STRIP_SLACK_ROWS) * N2, p->sw.polar_poison));
     HIP_TRY(p->D.ensure(((size_t)p->lmax + LEG_STRIP_SLACK_ROWS) * p->mmax * N2));
     unsigned* emax = nullptr;
     if (p->f16 && p->slots.p) {   // f16x3: range of the coefficients, taken by the layout converter as it reads them (round 5: a pass
@@ -395,8 +475,9 @@ extern "C" int ace_sht_inverse(ace_sht_plan* p, const float* coeffs, float* x, i
     // the strip kernels are exactly triangular: the converter then neither reads nor writes the entries with m > l (half the tensor)
     ACE_TRY(run_legendre_inverse(*p, p->D.p, p->X.p, N2, s, emax, true));
     HIP_TRY(launch_ref_to_spec(coeffs, p->D.p, 1, n, p->lmax, p->mmax, s, emax, p->route[1] != 0));
-    ACE_TRY(run_legendre_inverse(*p, p->D.p, p->X.p, N2, s, emax));
-    ACE_TRY(run_dft_inverse(*p, p->X.p, nullptr, x, 1, n, s));
+    const InversePair pr = inverse_pair(*p, p->D.p, p->X.p, N2, emax, x, 1, n);
+    ACE_TRY(run_legendre_inverse(*p, p->D.p, p->X.p, N2, s, emax, false, pr.skip_dead));
+    ACE_TRY(run_dft_inverse(*p, p->X.p, nullptr, x, 1, n, s, nullptr, pr.mcut));
     return ACE_OK;
 }
 
@@ -871,7 +952,7 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
         if (rl < 1 || rm < 1) return fail(ACE_ERR_INVALID, "residual_filter_factor leaves no modes");
         ACE_TRY(plan_build(c.nlat, c.nlon, rl, rm, (Grid)c.data_grid, n->plan_res, false));
         const size_t n2 = (size_t)n->Bmax * 2 * c.in_chans;
-        HIP_TRY(n->resX.alloc(((size_t)rm * c.nlat + LEG_STRIP_SLACK_ROWS) * n2));
+        HIP_TRY(n->resX.alloc_x(((size_t)rm * c.nlat + LEG_STRIP_SLACK_ROWS) * n2, n->sw.polar_poison));
         HIP_TRY(n->resD.alloc(((size_t)rl + LEG_STRIP_SLACK_ROWS) * rm * n2));
         HIP_TRY(n->inF.alloc((size_t)n->Bmax * c.in_chans * n->HW));
     }
@@ -987,7 +1068,7 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
             HIP_TRY(n->Wp1.alloc((size_t)n->Bmax * ((n->hid + 15) / 16 * 16) * cp, true));
         }
     }
-    HIP_TRY(n->X.alloc(spec_x));
+    HIP_TRY(n->X.alloc_x(spec_x, n->sw.polar_poison));
     HIP_TRY(n->D.alloc(spec_d));
     HIP_TRY(n->E.alloc(spec_d));
     HIP_TRY(n->stats.alloc((size_t)4 * n->Bmax * C));
@@ -1692,10 +1773,13 @@ static int enqueue_big_skip_source(Fwd& f, const float* in) {
         HIP_TRY(launch_absmax(f.noise, (long)f.B * c.noise_embed_dim * f.HW, f.slot(16 + 12 * c.num_layers), f.s));
     if (n->plan_res) {   // residual = residual_filter_up(residual_filter_down(x)) (sfnonet.py:715-716), exact fp32; its range into slot 7
         const long NR = (long)f.B * 2 * Cin;
-        ACE_TRY(run_dft_forward(*n->plan_res, in, nullptr, nullptr, n->resX.p, f.B, Cin, f.s));
+        // (an fp32 plan: no folded kernels, so neither pair takes the polar cut - asked all the same, in the one place that decides)
+        const int* mcut = forward_pair_mcut(*n->plan_res, n->resX.p, n->resD.p, NR, nullptr, nullptr, false);
+        ACE_TRY(run_dft_forward(*n->plan_res, in, nullptr, nullptr, n->resX.p, f.B, Cin, f.s, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, mcut));
         ACE_TRY(run_legendre_forward(*n->plan_res, n->resX.p, n->resD.p, NR, f.s));
-        ACE_TRY(run_legendre_inverse(*n->plan_res, n->resD.p, n->resX.p, NR, f.s));
-        ACE_TRY(run_dft_inverse(*n->plan_res, n->resX.p, nullptr, n->inF.p, f.B, Cin, f.s, f.slot(7)));
+        const InversePair pr = inverse_pair(*n->plan_res, n->resD.p, n->resX.p, NR, nullptr, n->inF.p, f.B, Cin);
+        ACE_TRY(run_legendre_inverse(*n->plan_res, n->resD.p, n->resX.p, NR, f.s, nullptr, false, pr.skip_dead));
+        ACE_TRY(run_dft_inverse(*n->plan_res, n->resX.p, nullptr, n->inF.p, f.B, Cin, f.s, f.slot(7), pr.mcut));
         f.skip_in = n->inF.p;
         f.skip_in_slot = f.slot(7);
     }
@@ -1756,18 +1840,20 @@ static int enqueue_forward_transform(Fwd& f, int i, const BlockRoute& b) {
         skip_pack.b = f.b0; skip_pack.bias = f.wt(p + "inner_skip.bias").buf.p; skip_pack.bf = n->bf0.p; skip_pack.nsamples = B;
     }
     const PackFragArgs* ride = b.ride_skip_pack ? &skip_pack : nullptr;
+    const int* mcut = forward_pair_mcut(*b.fwd, n->X.p, n->D.p, N2, xmax, dmax, b.dplanes);
     if (b.in_planes_only)
-        ACE_TRY(run_dft_forward(*b.fwd, nullptr, f.a0, f.b0, n->X.p, B, C, f.s, xmax, f.PBh, f.PBl, (long)C * f.HW, f.hslot(i), ride, &f.skip_pack_rode));
+        ACE_TRY(run_dft_forward(*b.fwd, nullptr, f.a0, f.b0, n->X.p, B, C, f.s, xmax, f.PBh, f.PBl, (long)C * f.HW, f.hslot(i), ride, &f.skip_pack_rode, mcut));
     else
-        ACE_TRY(run_dft_forward(*b.fwd, f.h, f.a0, f.b0, n->X.p, B, C, f.s, xmax, nullptr, nullptr, 0, nullptr, ride, &f.skip_pack_rode));
+        ACE_TRY(run_dft_forward(*b.fwd, f.h, f.a0, f.b0, n->X.p, B, C, f.s, xmax, nullptr, nullptr, 0, nullptr, ride, &f.skip_pack_rode, mcut));
     MARK(ST_DFT_FWD);
     ACE_TRY(run_legendre_forward(*b.fwd, n->X.p, n->D.p, N2, f.s, xmax, dmax, b.dplanes));
     MARK(ST_LEGENDRE_FWD);
     f.res = f.h; f.ra = f.a0; f.rb = f.b0;
     if (b.scale_residual) {
-        ACE_TRY(run_legendre_inverse(*b.inv, n->D.p, n->X.p, N2, f.s, dmax));
+        const InversePair pr = inverse_pair(*b.inv, n->D.p, n->X.p, N2, dmax, n->R.p, B, C);
+        ACE_TRY(run_legendre_inverse(*b.inv, n->D.p, n->X.p, N2, f.s, dmax, false, pr.skip_dead));
         MARK(ST_LEGENDRE_INV);
-        ACE_TRY(run_dft_inverse(*b.inv, n->X.p, nullptr, n->R.p, B, C, f.s));
+        ACE_TRY(run_dft_inverse(*b.inv, n->X.p, nullptr, n->R.p, B, C, f.s, nullptr, pr.mcut));
         MARK(ST_DFT_INV);
         f.res = n->R.p; f.ra = nullptr; f.rb = nullptr;
     }
@@ -1826,9 +1912,10 @@ static int enqueue_contraction(Fwd& f, int i, const BlockRoute& b) {
 static int enqueue_inverse_transform(Fwd& f, int i, const BlockRoute& b) {
     const ace_sfno* n = f.n;
     const int sb = 16 + 12 * i;
-    ACE_TRY(run_legendre_inverse(*b.inv, n->E.p, n->X.p, (long)f.B * 2 * n->C, f.s, f.slot(sb + 2)));
+    const InversePair pr = inverse_pair(*b.inv, n->E.p, n->X.p, (long)f.B * 2 * n->C, f.slot(sb + 2), n->Y.p, f.B, n->C);
+    ACE_TRY(run_legendre_inverse(*b.inv, n->E.p, n->X.p, (long)f.B * 2 * n->C, f.s, f.slot(sb + 2), false, pr.skip_dead));
     MARK(ST_LEGENDRE_INV);
-    ACE_TRY(run_dft_inverse(*b.inv, n->X.p, f.W("blocks." + std::to_string(i) + ".filter.filter.bias"), n->Y.p, f.B, n->C, f.s, f.slot(sb + 7)));
+    ACE_TRY(run_dft_inverse(*b.inv, n->X.p, f.W("blocks." + std::to_string(i) + ".filter.filter.bias"), n->Y.p, f.B, n->C, f.s, f.slot(sb + 7), pr.mcut));
     MARK(ST_DFT_INV);
     f.HW = b.hw_out;
     return ACE_OK;

@@ -188,6 +188,10 @@ __global__ __launch_bounds__(R * N2, N1 * N2 == 360 ? (PLN ? ACE_FFT_FWD_PLN_WAV
     const long HW = (long)p.H * W;
     constexpr int NPF = (R * (W / 4) + NT - 1) / NT;   // 16-byte row pieces per thread
     const int rlast = (p.C - c0 < R ? p.C - c0 : R) - 1;   // ragged last channel block: its missing rows repeat the last one
+    // polar cut: at this latitude the wavenumbers from mcut[lat] on are never read by the folded Legendre kernel: their stores are
+    // dropped like those beyond Mm.  The range maximum still covers them (the published bound, and with it every downstream scale,
+    // stays what it is without the cut).  A scalar, requested here and used behind three barriers
+    const int Mc = p.mcut ? min(p.Mm, p.mcut[k]) : p.Mm;
 
     // fused instance-norm affine of this thread's row in level 1 (one load pair per thread, applied in registers).  The three small
     // loads (scale, shift, range slot) are REQUESTED behind the rows' own loads: in front of them hipcc waited for the slot's value
@@ -298,27 +302,32 @@ __global__ __launch_bounds__(R * N2, N1 * N2 == 360 ? (PLN ? ACE_FFT_FWD_PLN_WAV
             const long ms = (long)p.H * p.Bt * 2 * p.C;
             char* obase = reinterpret_cast<char*>(p.spec_out + (long)kb * 2 * p.C + c0);
             // Entries beyond Mm (and the mirror of the self-conjugate columns 0 and N1/2) are dropped by the descriptor's range
-            // check: their lane offset is replaced by one past num_records - no branch per store.
+            // check: their lane offset is replaced by one past num_records - no branch per store.  So are the entries of the polar
+            // cut, from wavenumber Mc on: kc / kd carry the cutoff in the lane's own registers (k1 + N1 q < Mc  <=>  kc + N1 q < 0;
+            // (N1 - k1) + N1 k2 < Mc  <=>  N1 (k2 + 1) < kd)
             constexpr unsigned kDrop = 0xF0000000u;
             const unsigned od = (unsigned)(k1 * ms + r) * 4u, om = (unsigned)((N1 - k1) * ms + r) * 4u;
             const int imoff = p.C * 4;
             const bool has_mirror = k1 > 0 && k1 < N1 / 2;
+            const int kc = k1 - Mc, kd = has_mirror ? k1 + Mc : 0;
             const v2f* zcol = Zs + k1 * ZP + r;
             sfft::CFft<N2, false, v2f>::run([&](int bb) { return zcol[bb * R]; }, [&](int q, v2f out) {
                 const float mag = FULLM ? 0.f : fmaxf(fabsf(out.x), fabsf(out.y));
                 if (FULLM) vmax = fmaxf(vmax, fmaxf(fabsf(out.x), fabsf(out.y)));   // v_max3_f32
                 if (q < K2N) {
-                    const bool ok = k1 + N1 * q < p.Mm && (ACE_FFT_ABL != 1 || out.x == 1.2345e-30f);
+                    const bool ok = k1 + N1 * q < p.Mm;
+                    const bool st = kc + N1 * q < 0 && (ACE_FFT_ABL != 1 || out.x == 1.2345e-30f);
                     const auto rs = wide_rsrc(obase + (long)q * N1 * ms * 4);
-                    const int off = (int)(ok ? od : kDrop);
+                    const int off = (int)(st ? od : kDrop);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(out.x), rs, off, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(out.y), rs, off, imoff, 0);
                     if (!FULLM) vmax = fmaxf(vmax, ok ? mag : 0.f);
                 }
                 if (q >= N2 / 2) {   // k2 = N2 - 1 - q <= N2 / 2 - 1 (k2 = N2 / 2 would be beyond W / 2 for every mirrored column)
-                    const bool ok = has_mirror && (N1 - k1) + N1 * (N2 - 1 - q) < p.Mm && (ACE_FFT_ABL != 1 || out.x == 1.2345e-30f);
+                    const bool ok = has_mirror && (N1 - k1) + N1 * (N2 - 1 - q) < p.Mm;
+                    const bool st = N1 * (N2 - q) < kd && (ACE_FFT_ABL != 1 || out.x == 1.2345e-30f);
                     const auto rs = wide_rsrc(obase + (long)(N2 - 1 - q) * N1 * ms * 4);
-                    const int off = (int)(ok ? om : kDrop);
+                    const int off = (int)(st ? om : kDrop);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(out.x), rs, off, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(-out.y), rs, off, imoff, 0);
                     if (!FULLM) vmax = fmaxf(vmax, ok ? mag : 0.f);
@@ -327,8 +336,13 @@ __global__ __launch_bounds__(R * N2, N1 * N2 == 360 ? (PLN ? ACE_FFT_FWD_PLN_WAV
         }
     }
     if (p.omax) {   // one atomic per workgroup (Z is dead: reduce the wave maxima through LDS)
+        // The lane index is taken afresh here: shared with the range-slot reduction at the top of the planes-input kernel, the
+        // exchange addresses stayed live across the whole kernel - one register more than its 72 (seven waves per SIMD) hold.
+        int ln = tid & 63;
+        asm volatile("" : "+v"(ln));
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
+        for (int off = 32; off > 0; off >>= 1)
+            vmax = fmaxf(vmax, __int_as_float(__builtin_amdgcn_ds_bpermute((ln ^ off) << 2, __float_as_int(vmax))));
         __syncthreads();
         if ((tid & 63) == 0) smem[tid >> 6] = vmax;
         __syncthreads();
@@ -410,6 +424,9 @@ __global__ __launch_bounds__(R * N2, N1 * N2 == 360 ? ACE_FFT_INV_WAVES : (N1 * 
             constexpr unsigned kDrop = 0xF0000000u;
             const unsigned od = (unsigned)(k1 * ms + rr) * 4u, om = (unsigned)((N1 - k1) * ms + rr) * 4u;
             const int imoff = p.C * 4;
+            // polar cut: the wavenumbers from mcut[lat] on are exact zeros of the folded inverse Legendre kernel (or not written at
+            // all): read as zeros without a memory transaction, like those beyond Mm
+            const int Mc = p.mcut ? min(p.Mm, p.mcut[k]) : p.Mm;
             v2f f[N2];
 #pragma unroll
             for (int k2 = 0; k2 < N2; ++k2) {
@@ -420,15 +437,15 @@ __global__ __launch_bounds__(R * N2, N1 * N2 == 360 ? ACE_FFT_INV_WAVES : (N1 * 
                     // k1 = 0: the entry W/2 itself (block N2/2, real); otherwise mirrored from block N2/2 - 1
                     const auto rs0 = wide_rsrc(sbase + (long)(N2 / 2) * N1 * ms * 4);
                     const auto rs1 = wide_rsrc(sbase + (long)(N2 / 2 - 1) * N1 * ms * 4);
-                    const int off0 = (int)((k1 == 0 && N1 * (N2 / 2) < p.Mm) ? od : kDrop);
-                    const int off1 = (int)((k1 > 0 && m < p.Mm) ? om : kDrop);
+                    const int off0 = (int)((k1 == 0 && N1 * (N2 / 2) < Mc) ? od : kDrop);
+                    const int off1 = (int)((k1 > 0 && m < Mc) ? om : kDrop);
                     const float re0 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs0, off0, 0, 0));
                     const float re1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs1, off1, 0, 0));
                     const float im1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs1, off1, imoff, 0));
                     f[k2] = v2f{re0 + re1, -im1};                     // (one of the two is a dropped load: zero)
                 } else {
                     const auto rs = wide_rsrc(sbase + (long)blk * N1 * ms * 4);
-                    const int off = (int)(m < p.Mm ? (mir ? om : od) : kDrop);
+                    const int off = (int)(m < Mc ? (mir ? om : od) : kDrop);
                     const float re = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
                     const float im = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, imoff, 0));
                     f[k2] = v2f{re, mir ? -im : ((k2 == 0 && k1 == 0) ? 0.f : im)};   // F[0] is real
@@ -540,9 +557,13 @@ bool launch_dft_forward_fft(const DftArgs& a, hipStream_t s, hipError_t* err) {
 
 bool dft_fft_has_width(int W) { return W == 360 || W == 1440 || W == 720 || W == 48 || W == 24 || W == 16; }
 
+bool dft_inverse_fft_takes(const DftArgs& a) {
+    return !(a.no_fft || (reinterpret_cast<uintptr_t>(a.y) & 15) != 0 || a.Mm > a.W / 2 + 1 || a.H > 65535 || a.Bt > 65535 || !lane_offsets_fit(a)) &&
+           dft_fft_has_width(a.W);
+}
+
 bool launch_dft_inverse_fft(const DftArgs& a, hipStream_t s, hipError_t* err) {
-    if (a.no_fft || (reinterpret_cast<uintptr_t>(a.y) & 15) != 0 || a.Mm > a.W / 2 + 1 || a.H > 65535 || a.Bt > 65535 || !lane_offsets_fit(a))
-        return false;
+    if (!dft_inverse_fft_takes(a)) return false;
     switch (a.W) {
         case 360: *err = launch_inv<20, 18, ACE_FFT_INV_ROWS>(a, s); return true;   // 32 channel rows per workgroup: 128-byte runs on the spectral side (r02: 81.7 -> 75.6 us; the forward kernel is faster with 16)
         case 1440: *err = launch_inv<40, 36, ACE_FFT_QROWS>(a, s); return true;

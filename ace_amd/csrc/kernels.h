@@ -27,6 +27,8 @@ struct Switches {
     bool fused_pack = true;        // ACE_FUSED_PACK=0: the norm-folded weights of inner skip / fc1 from a pack_conv_frag launch behind every norm (r05) instead of
                                    // rider workgroups of the forward FFT (inner skip) / the convolution's own prologue (fc1 on conv_wl.hip)
     bool planes_stream = true;     // ACE_PLANES_STREAM=0: fc2 also writes the block output as fp32 (the residual stream round-trips twice)
+    bool no_polar_cut = false;     // ACE_NO_POLAR_CUT: SHT plans without the polar cut (strip_pack.h): every entry of X is stored and loaded
+    bool polar_poison = false;     // ACE_POLAR_POISON: every X buffer is filled with quiet NaNs when it is allocated - a read of an entry the cut leaves unwritten shows
     bool dense_grouped_filter = false;   // ACE_DENSE_GROUPED_FILTER: a grouped (block-diagonal) csfno filter expanded to the dense (C x C) form (r04)
                                          // instead of stored as the reference stores it, (G, L, C/G, C/G, 2) blocks only
 };
@@ -176,6 +178,11 @@ struct LegStripArgs {
     int R = 0;        // row extent (forward: lmax, inverse: nlat)
     int nbatch = 0;   // mmax
     int mode = 0;     // 0 forward (rows l >= m), 1 inverse (contraction over l >= m)
+    // folded form only: the polar cut (strip_pack.h, PolarCut::r0, device array of nbatch ints; NULL = none).  Forward: the folded
+    // latitudes kf < r0[m] and their mirror rows are not loaded (they read as zeros; always safe).  Inverse: they are NOT STORED and
+    // their wholly dead 32-row tiles do not run - only for a consumer that does not read them (the FFT form with DftArgs::mcut).
+    const int* r0 = nullptr;
+    bool kdrop = false;   // forward, small form: A / tile_off were packed with kskip[m] = r0[m] / 16 (those k16-steps are not run)
 };
 // the kernels read up to 15 rows (of b_kstride elements) past the last contraction row of the last batch: buffers they read
 // must carry this many rows of slack
@@ -288,6 +295,9 @@ struct DftArgs {
     int Bt = 1, C = 0, H = 0, W = 0, Mm = 0;
     unsigned* omax = nullptr;  // atomicMax of bits(max|output|)
     bool no_fft = false;       // Switches::no_fft of the owning plan
+    // FFT form only: the polar cut (strip_pack.h, PolarCut::mcut, device array of H ints; NULL = none): at latitude lat the wavenumbers
+    // m >= mcut[lat] are not stored (forward; the range maximum still covers them) / read as zeros without a load (inverse)
+    const int* mcut = nullptr;
     // forward, FFT form only: a weight-packing job whose workgroups ride in this launch (pack_frag.h); nride = pack_frag_blocks()
     // per sample, 0 = none.  launch_dft_forward reports through `rode` whether the launch took them along.
     PackFragArgs ride; int nride = 0; bool* rode = nullptr;
@@ -298,6 +308,7 @@ hipError_t launch_dft_inverse(const DftArgs& a, hipStream_t s);
 bool launch_dft_forward_fft(const DftArgs& a, hipStream_t s, hipError_t* err);
 bool launch_dft_inverse_fft(const DftArgs& a, hipStream_t s, hipError_t* err);
 bool dft_fft_has_width(int W);   // widths with an instantiated two-level FFT
+bool dft_inverse_fft_takes(const DftArgs& a);   // would launch_dft_inverse_fft handle this launch?
 
 // Conditional layer norm in one pass (cln_mfma.hip): statistics + the two conditioning 1x1 convolutions on MFMA + apply, for
 // C % 256 == 0 and H W % 32 == 0.  As / Ab: W_scale / W_bias as packed MFMA A fragments [C / 32][ceil(J / 16)][hi 512 | lo 512] halves

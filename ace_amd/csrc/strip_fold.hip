@@ -70,8 +70,12 @@ FDEV int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 struct RowMap { int rbase, rstep, vlo, vhi; };
 
 // OUT: 0 = fp32, 16-byte stores (N % 4 == 0, aligned); 1 = fp16 hi/lo planes, 8-byte stores; 2 = fp32 scalar stores
+// Polar cut (strip_pack.h): r0 = dead folded latitudes of this wavenumber (0 without the cut), j0 = k16-steps dropped from the front
+// of the forward contraction (the table was packed from step j0 on; gm is fold_geom_cut's).  Forward: the rows kf < r0 and their
+// mirror rows fall outside the two descriptors and read as zeros.  Inverse: the pairs tp < r0 / 32 are neither streamed nor run,
+// and the store masks start at r0 (north) / end at H - r0 (south).
 template <int NH, int OUT, bool FULLN, int MODE>
-FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int grp, const FoldGeom gm) {
+FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int grp, const FoldGeom gm, const int r0, const int j0) {
     constexpr int NKP = 2 * NH;       // k16-steps per unit; a unit = 4 NH pieces, NH per wave
     constexpr int FSLOT_BYTES = NKP * 2048;   // one unit of A fragments (hi + lo)
     constexpr bool BIG = NH > NH_MAX; // 0.25-degree form: one wave per SIMD, both operands (2 x NKP x 8 registers) still resident
@@ -86,12 +90,14 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
     const int nc = n < N ? n : N - 1;
     char* ring = smem;
     char* Ts = smem + FNSLOT * FSLOT_BYTES + wave * FTS_BYTES;
-    const int nunits = 2 * gm.npairs;
+    const int tp0 = MODE == 1 ? r0 >> 5 : 0;                                  // wholly dead leading pairs (inverse)
+    const int npairs = gm.npairs > tp0 ? gm.npairs - tp0 : 0;                 // pairs this workgroup runs: tp0 .. gm.npairs - 1
+    const int nunits = 2 * npairs;
 
     const unsigned raw_b = slot_load(p.bmax + lane);
 
     // ---- table stream
-    const _Float16* Am = p.A + (long)p.tile_off[m] * 1024;
+    const _Float16* Am = p.A + ((long)p.tile_off[m] + (long)tp0 * 2 * NKP) * 1024;
     auto issue_unit = [&](int u) {   // unit u -> slot u % 3; units past the end re-fetch the last one (uniform count)
         const int uu = u < nunits ? u : nunits - 1;
         const _Float16* src = Am + (long)uu * NKP * 1024 + lane * 8;
@@ -119,13 +125,16 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
         // offset of such an index is negative and wraps to the top of the unsigned range (far beyond num_records).
         const float* Xm = p.B + (long)m * p.b_moff;
         const long rowb = ks * 4;
-        const auto rsD = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xm), 0, (unsigned)((long)gm.Hh * rowb), 0x00020000);
-        const auto rsM = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xm + (long)gm.Hh * ks), 0, (unsigned)((long)(H - gm.Hh) * rowb), 0x00020000);
+        // Polar cut: the direct descriptor is based at row r0 (rows below it wrap to the top of the offset range like the mirror of
+        // an out-of-range index), the mirror descriptor ends r0 rows early; k-step jj of the unit is the rows from 16 (j0 + jj) on.
+        const int nD = gm.Hh - r0, nM = H - gm.Hh - r0;    // rows either descriptor covers (nM = -1: all dead, odd H)
+        const auto rsD = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xm + (long)r0 * ks), 0, (unsigned)((long)(nD > 0 ? nD : 0) * rowb), 0x00020000);
+        const auto rsM = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xm + (long)gm.Hh * ks), 0, (unsigned)((long)(nM > 0 ? nM : 0) * rowb), 0x00020000);
         unsigned vd[8], vm[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            vd[e] = (unsigned)(((long)(8 * g + e) * ks + nc) * 4);
-            vm[e] = (unsigned)(((long)(H - 1 - gm.Hh - (8 * g + e)) * ks + nc) * 4);   // row (H - 1 - kf) - Hh of the mirror descriptor
+            vd[e] = (unsigned)(((long)(16 * j0 + 8 * g + e - r0) * ks + nc) * 4);
+            vm[e] = (unsigned)(((long)(H - 1 - gm.Hh - (16 * j0 + 8 * g + e)) * ks + nc) * 4);   // row (H - 1 - kf) - Hh of the mirror descriptor
         }
         // small form: every row of the strip in flight at once; big form: in chunks of CHK k-steps (the raw fp32 values of a whole
         // 0.25-degree strip would not fit beside the fragments they become)
@@ -206,7 +215,9 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
         }
     };
     auto store_tile = [&](const RowMap rm, const f32x16& acc, auto inner_tag) {
-        constexpr bool NOMASK = decltype(inner_tag)::value && FULLN;
+        // (inverse: the first live tile of a cut wavenumber is an inner tile with a row mask - rows are always checked there)
+        constexpr bool NOMASK = decltype(inner_tag)::value && FULLN && MODE == 0;
+        constexpr bool NOCOL = decltype(inner_tag)::value && FULLN;
         if (OUT == 2) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -242,7 +253,7 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
                 const int rl = ps * 8 + (lane >> 3);           // row within this half
                 const int row = rm.rbase + rm.rstep * (16 * hf + rl);
                 const u32x4 d = *reinterpret_cast<const u32x4*>(T32 + rl * 32 + c4);
-                const bool ok = NOMASK || (row >= rm.vlo && row < rm.vhi && ncol < N);
+                const bool ok = NOMASK || (row >= rm.vlo && row < rm.vhi && (NOCOL || ncol < N));
                 if (OUT == 1) {
                     u32x2 hi2, lo2;
                     hi2[0] = (d[0] & 0xffffu) | (d[1] << 16);
@@ -268,8 +279,9 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
     // row maps.  Forward, unit (tp, par): degrees l = m + par + 2 (32 tp + rl), stored below lmax.  Inverse, pair tp: north rows
     // kf = 32 tp + rl below Hh; south rows H - 1 - kf, stored when they are not a north row (at or beyond Hh)
     auto fwd_map = [&](int tp, int par) { return RowMap{m + par + 64 * tp, 2, 0, R}; };
-    auto north_map = [&](int tp) { return RowMap{32 * tp, 1, 0, gm.Hh}; };
-    auto south_map = [&](int tp) { return RowMap{H - 1 - 32 * tp, -1, gm.Hh, H}; };
+    // (tp counts from the first pair that runs, tp0)
+    auto north_map = [&](int tp) { return RowMap{32 * (tp0 + tp), 1, r0, gm.Hh}; };
+    auto south_map = [&](int tp) { return RowMap{H - 1 - 32 * (tp0 + tp), -1, gm.Hh, H - r0}; };
 
     // one unit: wait for its pieces, barrier, refill the slot of the unit before it, `under()` (the deferred epilogue), MFMAs
     auto unit = [&](int u, auto par_tag, auto&& under) -> f32x16 {
@@ -330,14 +342,14 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
 #pragma unroll
     for (int r = 0; r < 16; ++r) { pa[r] = 0.f; pb[r] = 0.f; }
     if constexpr (MODE == 0) {
-        for (int tp = 0; tp < gm.npairs; ++tp) {
+        for (int tp = 0; tp < npairs; ++tp) {
             const f32x16 ev = unit(2 * tp, T0{}, [&] {
                 if (tp > 0) {
                     if (OUT != 1) tile_max(fwd_map(tp - 1, 1), pb, std::true_type{});
                     store_tile(fwd_map(tp - 1, 1), pb, std::true_type{});
                 }
             });
-            const bool last = tp + 1 == gm.npairs;
+            const bool last = tp + 1 == npairs;
             pb = unit(2 * tp + 1, T1{}, [&] {
                 if (!last) {
                     if (OUT != 1) tile_max(fwd_map(tp, 0), ev, std::true_type{});
@@ -349,11 +361,11 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
     } else if constexpr (BIG) {
         // big form: no deferred epilogue (its two held tiles are 32 registers the 384-register operands leave no room for); the rows
         // of a pair are stored as soon as both parities are in - the stores themselves still retire under the next pair's MFMAs
-        for (int tp = 0; tp < gm.npairs; ++tp) {
+        for (int tp = 0; tp < npairs; ++tp) {
             const f32x16 ev = unit(2 * tp, T0{}, [] {});
             const f32x16 od = unit(2 * tp + 1, T1{}, [] {});
             f32x16 t = ev + od;
-            const bool inner = tp + 1 < gm.npairs;
+            const bool inner = tp + 1 < npairs;
             if (inner) { tile_max(north_map(tp), t, std::true_type{}); store_tile(north_map(tp), t, std::true_type{}); }
             else { tile_max(north_map(tp), t, std::false_type{}); store_tile(north_map(tp), t, std::false_type{}); }
             __builtin_amdgcn_sched_barrier(0);   // one 16-register tile at a time through the transpose buffer
@@ -363,7 +375,7 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
             __builtin_amdgcn_sched_barrier(0);
         }
     } else {
-        for (int tp = 0; tp < gm.npairs; ++tp) {
+        for (int tp = 0; tp < npairs; ++tp) {
             const f32x16 ev = unit(2 * tp, T0{}, [&] {
                 if (tp > 0) {
                     tile_max(north_map(tp - 1), pa, std::true_type{});
@@ -384,9 +396,9 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // last pair: masked.  The range reduction (shuffles, an LDS round trip) runs before the last stores (strip.hip)
     constexpr bool STORED_IN_LOOP = BIG && MODE == 1;   // (the big inverse form has stored every pair already)
-    const int tl = gm.npairs - 1;
+    const int tl = npairs - 1;
     const RowMap ma = MODE == 0 ? fwd_map(tl, 0) : north_map(tl), mb = MODE == 0 ? fwd_map(tl, 1) : south_map(tl);
-    if (OUT != 1 && gm.npairs > 0 && !STORED_IN_LOOP) {
+    if (OUT != 1 && npairs > 0 && !STORED_IN_LOOP) {
         tile_max(ma, pa, std::false_type{});
         tile_max(mb, pb, std::false_type{});
     }
@@ -400,7 +412,7 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
         if (tid == 0) atomicMax(p.omax + (blockIdx.x & 63), __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
         __syncthreads();        // ... before the transpose buffer of the last tiles re-uses the LDS
     }
-    if (gm.npairs > 0 && !STORED_IN_LOOP) {
+    if (npairs > 0 && !STORED_IN_LOOP) {
         store_tile(ma, pa, std::false_type{});
         store_tile(mb, pb, std::false_type{});
     }
@@ -422,11 +434,13 @@ __global__ __launch_bounds__(256, 2) void legendre_fold_kernel(LegStripArgs p, i
     const int m = (idx / G) * 8 + xcd;
     const int grp = idx % G;
     if (m >= p.nbatch) return;
-    const FoldGeom gm = fold_geom(MODE, m, p.R, p.K);
+    const int r0 = p.r0 ? p.r0[m] : 0;
+    const int j0 = MODE == 0 && p.kdrop ? r0 >> 4 : 0;
+    const FoldGeom gm = fold_geom_cut(MODE, m, p.R, p.K, j0);
     switch (gm.nkp2) {
-        case 2: fold_body<1, OUT, FULLN, MODE>(p, smem, m, grp, gm); break;
-        case 4: fold_body<2, OUT, FULLN, MODE>(p, smem, m, grp, gm); break;
-        case 6: fold_body<3, OUT, FULLN, MODE>(p, smem, m, grp, gm); break;
+        case 2: fold_body<1, OUT, FULLN, MODE>(p, smem, m, grp, gm, r0, j0); break;
+        case 4: fold_body<2, OUT, FULLN, MODE>(p, smem, m, grp, gm, r0, j0); break;
+        case 6: fold_body<3, OUT, FULLN, MODE>(p, smem, m, grp, gm, r0, j0); break;
         default: break;
     }
 #ifdef ACE_LF_TRACE
@@ -450,16 +464,18 @@ __global__ __launch_bounds__(256, 1) void legendre_fold_big_kernel(LegStripArgs 
     const int grp = idx % G;
     if (m >= p.nbatch) return;
     const FoldGeom gm = fold_geom(MODE, m, p.R, p.K);
+    const int r0 = p.r0 ? p.r0[m] : 0;   // the big form keeps its k-steps (kdrop is never set for it): descriptor window, store mask, tile skip
+    constexpr int j0 = 0;
     switch (gm.nkp2) {
-        case 12: fold_body<6, OUT, true, MODE>(p, smem_big, m, grp, gm); break;
-        case 18: fold_body<9, OUT, true, MODE>(p, smem_big, m, grp, gm); break;
-        case 24: fold_body<12, OUT, true, MODE>(p, smem_big, m, grp, gm); break;
+        case 12: fold_body<6, OUT, true, MODE>(p, smem_big, m, grp, gm, r0, j0); break;
+        case 18: fold_body<9, OUT, true, MODE>(p, smem_big, m, grp, gm, r0, j0); break;
+        case 24: fold_body<12, OUT, true, MODE>(p, smem_big, m, grp, gm, r0, j0); break;
         default:
             if constexpr (MODE == 1) {   // the inverse's contraction shrinks with m: the high wavenumbers need the small unit sizes too
                 switch (gm.nkp2) {
-                    case 2: fold_body<1, OUT, true, MODE>(p, smem_big, m, grp, gm); break;
-                    case 4: fold_body<2, OUT, true, MODE>(p, smem_big, m, grp, gm); break;
-                    case 6: fold_body<3, OUT, true, MODE>(p, smem_big, m, grp, gm); break;
+                    case 2: fold_body<1, OUT, true, MODE>(p, smem_big, m, grp, gm, r0, j0); break;
+                    case 4: fold_body<2, OUT, true, MODE>(p, smem_big, m, grp, gm, r0, j0); break;
+                    case 6: fold_body<3, OUT, true, MODE>(p, smem_big, m, grp, gm, r0, j0); break;
                     default: break;
                 }
             }

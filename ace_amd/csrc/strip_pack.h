@@ -200,21 +200,39 @@ inline double fold_symmetry_error(const float* tab, int mmax, int nlat, int lmax
     return mx > 0.0 ? worst / mx : 0.0;
 }
 
+// The forward contraction with its first j0 k16-steps dropped (the polar cut below: folded latitudes whose table entries all pack
+// to zero): the unit shrinks to the steps from 16 j0 on.  j0 = 0 is fold_geom.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline FoldGeom fold_geom_cut(int mode, int m, int R, int K, int j0) {
+    FoldGeom g = fold_geom(mode, m, R, K);
+    if (mode == 0 && j0 > 0) {
+        g.nkp = g.nkp > j0 ? g.nkp - j0 : 0;
+        g.nkp2 = fold_round_nkp(g.nkp);
+    }
+    return g;
+}
+
 // tab as for pack_legendre_strip.  nlat / lmax: logical extents.  The folded entry is the mean of the two mirror entries (they
 // differ by fp32 rounding of the fp64 recursion at most); the middle row of an odd nlat keeps its own value.
-inline void pack_legendre_fold(const float* tab, int mmax, int nlat, int lmax, int pitch, int mode, float scale, StripPack& out) {
+// kskip (forward only, optional): per m, the k16-steps dropped from the front of the contraction (fold_geom_cut): block jj of a
+// unit then holds the folded latitudes from 16 (kskip[m] + jj) on.
+inline void pack_legendre_fold(const float* tab, int mmax, int nlat, int lmax, int pitch, int mode, float scale, StripPack& out,
+                               const int* kskip = nullptr) {
     const int R = mode == 0 ? lmax : nlat, K = mode == 0 ? nlat : lmax;
     out.tile_off.assign((size_t)mmax, 0);
     long blocks = 0;
     for (int m = 0; m < mmax; ++m) {
-        const FoldGeom g = fold_geom(mode, m, R, K);
+        const FoldGeom g = fold_geom_cut(mode, m, R, K, kskip ? kskip[m] : 0);
         out.tile_off[m] = (int)blocks;
         blocks += (long)g.npairs * 2 * g.nkp2;
     }
     out.blocks = blocks;
     out.frags.assign((size_t)blocks * 1024, 0);
     for (int m = 0; m < mmax; ++m) {
-        const FoldGeom g = fold_geom(mode, m, R, K);
+        const int j0 = mode == 0 && kskip ? kskip[m] : 0;
+        const FoldGeom g = fold_geom_cut(mode, m, R, K, j0);
         for (int u = 0; u < 2 * g.npairs; ++u) {
             const int tp = u >> 1, p = u & 1;
             for (int jj = 0; jj < g.nkp; ++jj) {
@@ -222,7 +240,7 @@ inline void pack_legendre_fold(const float* tab, int mmax, int nlat, int lmax, i
                 for (int lane = 0; lane < 64; ++lane) {
                     const int i = lane & 31, gg = lane >> 5;
                     for (int e = 0; e < 8; ++e) {
-                        const int c = 16 * jj + 8 * gg + e;
+                        const int c = 16 * (j0 + jj) + 8 * gg + e;
                         // forward: row = degree index, column = folded latitude; inverse: row = folded latitude, column = degree index
                         const int kf = mode == 0 ? c : 32 * tp + i;
                         const int l = m + p + 2 * (mode == 0 ? 32 * tp + i : c);
@@ -243,6 +261,76 @@ inline void pack_legendre_fold(const float* tab, int mmax, int nlat, int lmax, i
             }
         }
     }
+}
+
+// ---- polar cut ---------------------------------------------------------------------------------------------------------------
+// Near the poles P_l^m of a high order m is so small that every fp16 hi / lo fragment element of a folded latitude kf packs to zero,
+// for every degree, in BOTH folded tables.  Such an (m, kf) contributes exact zeros to the forward contraction and receives exact
+// zeros from the inverse one, so X[m][kf] and its mirror row need not be stored, loaded, multiplied or computed at all.  The dead
+// rows of a wavenumber are a prefix kf < r0[m] (counted from the pole) and r0 does not decrease with m; per latitude that is one
+// cutoff mcut[lat]: every m >= mcut[lat] is dead there.  Both shapes are CHECKED, on the packed bits themselves (no threshold on
+// the fp32 tables); a table that does not have them gets no cut.
+struct PolarCut {
+    std::vector<int> r0;     // [mmax]  dead folded rows of wavenumber m: kf < r0[m] (<= Hh)
+    std::vector<int> mcut;   // [nlat]  first dead wavenumber of latitude lat (kf = min(lat, nlat - 1 - lat)); mmax = none
+    bool ok = false;         // prefix-shaped and monotone
+    double dead_share = 0.0; // dead entries of X / all entries
+};
+// is any packed element (hi or lo, either parity, any tile) of folded latitude kf of wavenumber m non-zero?  `sp` packed WITHOUT kskip
+inline bool fold_pack_row_live(const StripPack& sp, int mode, int m, int kf, int nlat, int lmax) {
+    const int R = mode == 0 ? lmax : nlat, K = mode == 0 ? nlat : lmax;
+    const FoldGeom g = fold_geom(mode, m, R, K);
+    const uint16_t* base = sp.frags.data() + (size_t)sp.tile_off[m] * 1024;
+    auto nz = [](const uint16_t* blk, int at) { return ((blk[at] | blk[512 + at]) & 0x7fffu) != 0; };
+    for (int u = 0; u < 2 * g.npairs; ++u) {
+        if (mode == 0) {   // column kf of every row: block kf / 16, lanes (i, g = (kf % 16) / 8), element kf % 8
+            const int jj = kf / 16, gg = (kf % 16) / 8, e = kf % 8;
+            if (jj >= g.nkp) continue;
+            const uint16_t* blk = base + ((size_t)u * g.nkp2 + jj) * 1024;
+            for (int i = 0; i < 32; ++i)
+                if (nz(blk, (i + 32 * gg) * 8 + e)) return true;
+        } else {           // row kf of tile kf / 32: lanes (kf % 32, g), every block, every element
+            if ((u >> 1) != kf / 32) continue;
+            for (int jj = 0; jj < g.nkp; ++jj) {
+                const uint16_t* blk = base + ((size_t)u * g.nkp2 + jj) * 1024;
+                for (int gg = 0; gg < 2; ++gg)
+                    for (int e = 0; e < 8; ++e)
+                        if (nz(blk, (kf % 32 + 32 * gg) * 8 + e)) return true;
+            }
+        }
+    }
+    return false;
+}
+inline PolarCut derive_polar_cut(const StripPack& fwd, const StripPack& inv, int mmax, int nlat, int lmax) {
+    PolarCut c;
+    const int Hh = (nlat + 1) / 2;
+    c.r0.assign((size_t)mmax, 0);
+    c.mcut.assign((size_t)nlat, mmax);
+    c.ok = true;
+    long dead = 0;
+    for (int m = 0; m < mmax; ++m) {
+        int r = Hh;
+        for (int kf = 0; kf < Hh; ++kf) {
+            const bool live = fold_pack_row_live(fwd, 0, m, kf, nlat, lmax) || fold_pack_row_live(inv, 1, m, kf, nlat, lmax);
+            if (live) r = r < kf ? r : kf;
+            else if (r < Hh) c.ok = false;   // a dead row beyond a live one: not a prefix
+        }
+        c.r0[m] = r;
+        if (m > 0 && r < c.r0[m - 1]) c.ok = false;
+    }
+    if (!c.ok) {
+        c.r0.assign((size_t)mmax, 0);
+        return c;
+    }
+    for (int lat = 0; lat < nlat; ++lat) {
+        const int kf = lat < nlat - 1 - lat ? lat : nlat - 1 - lat;
+        int mc = mmax;
+        for (int m = mmax - 1; m >= 0 && c.r0[m] > kf; --m) mc = m;
+        c.mcut[lat] = mc;
+        dead += mmax - mc;
+    }
+    c.dead_share = mmax > 0 && nlat > 0 ? (double)dead / ((double)mmax * nlat) : 0.0;
+    return c;
 }
 
 // ---- conditional layer norm on MFMA (cln_mfma.hip): a (C x J) 1x1-convolution weight as error-compensated A fragments of
