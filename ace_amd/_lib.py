@@ -87,6 +87,7 @@ SIGNATURES = {
     "ace_sht_plan_destroy": (None, [c_void_p]),
     "ace_sht_plan_dims": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "ace_sht_plan_route": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "ace_sht_plan_cut": (c_int, [c_void_p, POINTER(c_double), POINTER(c_int)]),
     "ace_sht_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "ace_sht_inverse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "ace_sht_tables_host": (c_int, [c_int, c_int, c_int, c_int, c_char_p, c_int, c_void_p]),
@@ -111,6 +112,7 @@ SIGNATURES = {
     "ace_sfno_forward_conditioned": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "ace_sfno_forward_conditioned_timed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "ace_sfno_sht_route": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "ace_sfno_sht_cut": (c_int, [c_void_p, POINTER(c_double), POINTER(c_int)]),
     "ace_sfno_norm_affine": (c_int, [c_void_p, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
     "ace_sfno_num_stages": (c_int, []),
     "ace_sfno_stage_name": (c_char_p, [c_int]),
@@ -213,7 +215,7 @@ SIGNATURES = {
 }
 
 _lib = None
-TEST_INSTRUMENTATION = ("ace_sht_plan_route", "ace_sfno_sht_route", "ace_sfno_norm_affine", "ace_ocean_phys_launches")   # queries of the parity tests, not used by the product path
+TEST_INSTRUMENTATION = ("ace_sht_plan_route", "ace_sht_plan_cut", "ace_sfno_sht_route", "ace_sfno_sht_cut", "ace_sfno_norm_affine", "ace_ocean_phys_launches")   # queries of the parity tests, not used by the product path
 
 
 class AceLibraryMissing(RuntimeError):

@@ -441,6 +441,13 @@ extern "C" int ace_sht_plan_route(const ace_sht_plan* p, int* forward, int* inve
     return ACE_OK;
 }
 
+extern "C" int ace_sht_plan_cut(const ace_sht_plan* p, double* dead_share, int* kdrop) {
+    if (!p) return fail(ACE_ERR_INVALID, "null plan");
+    if (dead_share) *dead_share = p->cut ? p->cut_share : 0.0;
+    if (kdrop) *kdrop = p->cut && p->kdrop ? 1 : 0;
+    return ACE_OK;
+}
+
 extern "C" int ace_sht_forward(ace_sht_plan* p, const float* x, float* coeffs, int n, void* stream) {
     if (!p || !x || !coeffs || n <= 0) return fail(ACE_ERR_INVALID, "ace_sht_forward: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2269,6 +2276,10 @@ extern "C" long ace_debug_read_workspace(ace_sfno* n, const char* which, void* d
 extern "C" int ace_sfno_sht_route(const ace_sfno* n, int* forward, int* inverse) {
     if (!n || !n->plan_lg) return fail(ACE_ERR_INVALID, "null argument");
     return ace_sht_plan_route(n->plan_lg.get(), forward, inverse);
+}
+extern "C" int ace_sfno_sht_cut(const ace_sfno* n, double* dead_share, int* kdrop) {
+    if (!n || !n->plan_lg) return fail(ACE_ERR_INVALID, "null argument");
+    return ace_sht_plan_cut(n->plan_lg.get(), dead_share, kdrop);
 }
 // The instance-norm affine the last forward applied: tables (batch, C) of norm0 (which = 0) or norm1 (which = 1) of the LAST block
 // (the tables are shared by all blocks) and the range bound that norm published (maximum over the words of its slot; -1 where the

@@ -137,8 +137,10 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
             vm[e] = (unsigned)(((long)(H - 1 - gm.Hh - (16 * j0 + 8 * g + e)) * ks + nc) * 4);   // row (H - 1 - kf) - Hh of the mirror descriptor
         }
         // small form: every row of the strip in flight at once; big form: in chunks of CHK k-steps (the raw fp32 values of a whole
-        // 0.25-degree strip would not fit beside the fragments they become)
-        constexpr int CHK = BIG ? 4 : NKP;
+        // 0.25-degree strip would not fit beside the fragments they become).  The chunk divides the unit: 18 k16-steps go in threes (a
+        // ragged last chunk of four would index the operand arrays at steps 18 and 19 - bh[0][18] IS bh[1][0])
+        constexpr int CHK = !BIG ? NKP : (NKP % 4 == 0 ? 4 : 3);
+        static_assert(NKP % CHK == 0, "the load chunk must divide the k16-steps of a unit");
 #pragma unroll
         for (int j0 = 0; j0 < NKP; j0 += CHK) {
             float ra[CHK][8], rb[CHK][8];
@@ -171,6 +173,7 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
 #pragma unroll
         for (int e = 0; e < 8; ++e) ve[e] = (unsigned)(((long)(m + 2 * (8 * g + e)) * ks + nc) * 4);
         constexpr int CHK = BIG ? 2 : NKP;
+        static_assert(NKP % CHK == 0, "the load chunk must divide the k16-steps of a unit");
 #pragma unroll
         for (int j0 = 0; j0 < NKP; j0 += CHK) {
             float r0[CHK][8], r1[CHK][8];
@@ -302,6 +305,7 @@ FDEV void fold_body(const LegStripArgs& p, char* smem, const int m, const int gr
         // table fragments: the whole unit up front (small form: 48 registers at most) or in groups of FG k-steps, the next group
         // requested before the MFMAs of the current one (big form)
         constexpr int FG = BIG ? (MODE == 1 ? 1 : 2) : NKP;   // (the big inverse form also holds the even parity's tile: one k-step of read-ahead)
+        static_assert(NKP % FG == 0, "the fragment group must divide the k16-steps of a unit");
         half8 fh[2][FG], fl[2][FG];
 #pragma unroll
         for (int q = 0; q < FG; ++q) {

@@ -53,6 +53,10 @@ int ace_sht_plan_dims(const ace_sht_plan* plan, int* nlat, int* nlon, int* lmax,
  * launch they check really ran the kernel they mean to check): 0 tile engine, 1 register-resident strip kernel, 2 equatorially
  * folded strip kernel, 3 its big form (more than 96 folded latitudes: the 0.25-degree grid); -1 = no launch yet. */
 int ace_sht_plan_route(const ace_sht_plan* plan, int* forward, int* inverse);
+/* The plan's polar cut (test instrumentation, read-only): dead_share = the share of the spectral scratch X[m][lat] that is neither
+ * stored nor loaded, kdrop = 1 when the forward table was also packed without its wholly dead leading k16-steps (small form only).
+ * A plan without a cut (fp32 plans, ACE_NO_POLAR_CUT, tables without dead rows) reports 0.0 and 0. */
+int ace_sht_plan_cut(const ace_sht_plan* plan, double* dead_share, int* kdrop);
 
 /* RealSHT.forward (fme/sht_fix.py:119-139): x (n, nlat, nlon) f32 -> coeffs (n, lmax, mmax) complex64
  * stored interleaved (re, im) as 2*n*lmax*mmax floats.  May grow plan-owned scratch (hipMalloc) on
@@ -200,6 +204,8 @@ int ace_sfno_forward_conditioned_timed(ace_sfno* net, const float* in, const flo
 int ace_sfno_num_stages(void);
 /* ace_sht_plan_route of the network's internal (legendre-gauss) plan after a forward. */
 int ace_sfno_sht_route(const ace_sfno* net, int* forward, int* inverse);
+/* ace_sht_plan_cut of the same plan. */
+int ace_sfno_sht_cut(const ace_sfno* net, double* dead_share, int* kdrop);
 /* Test instrumentation: the instance-norm affine the last forward applied.  which 0: norm0, 1: norm1, of the LAST block (all blocks
    share the tables).  scale / shift: host arrays of batch * embed_dim floats; bound: the range bound that norm published (-1 when the
    precision publishes none).  Synchronises the stream of that forward; ACE_ERR_INVALID when no instance-norm forward has run. */

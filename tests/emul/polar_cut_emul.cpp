@@ -10,7 +10,16 @@
 // from k16-step r0 / 16 on, pairs below r0 / 32 not run, store masks [r0, Hh) / [Hh, H - r0), FFT stores and loads compared with
 // min(Mm, mcut[lat])) are restated as in strip_fold_emul.cpp, arithmetic in double in the kernel's order.  With X's dead entries set
 // to NaN the forward and the inverse must equal the run without the cut BIT FOR BIT, every live element written exactly once and no
-// dead element written.  Test infrastructure only (built and run by tests/test_polar_cut_cpu.py).
+// dead element written.
+//
+// Big form (legendre_fold_big_kernel: more than 96 folded latitudes or degrees per parity at m = 0, i.e. nlat or lmax > 192): units
+// of 12, 18 or 24 k16-steps, the inverse falling through to 2 / 4 / 6 as its contraction shrinks with m; j0 = 0 (the forward table
+// keeps every k16-step: no kdrop), whole 128-column groups only; the cut is the descriptor window, the store masks and the tile skip.
+// Grids 194 x 48, 360 x 720, 385 x 720 legendre-gauss and 361 x 720 equiangular at N = 128, dead shares of the three 720-wide ones
+// within 0.01 of 0.2850, 0.2586 and 0.2860.  Test infrastructure only (built and run by tests/test_polar_cut_cpu.py).
+#if defined(__GNUC__) && !defined(__clang__)
+#pragma GCC optimize("O3")   // the test builds with -O2; the contraction loops of the 720-wide grids want the vectoriser (twice as fast)
+#endif
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -63,11 +72,17 @@ static void run_fold(int mode, const Plan& P, const StripPack& sp, const int* r0
     const long b_kstride = mode == 0 ? N : (long)M * N, b_moff = mode == 0 ? (long)H * N : N;
     const long c_rstride = mode == 0 ? (long)M * N : N, c_moff = mode == 0 ? N : (long)H * N;
     const int G = (N + 127) / 128;
+    // launch_legendre_fold: the size at m = 0 picks the kernel.  The big form takes whole 128-column groups only (legendre_fold_eligible),
+    // ignores kdrop (j0 = 0, gm = fold_geom) and has bodies for 12, 18, 24 k16-steps, the inverse also for 2, 4, 6
+    const bool big = fold_geom(mode, 0, R, K).nkp2 > FOLD_NKP_SMALL;
+    if (big && (N % 128 != 0 || kdrop)) { std::printf("big form: N %d is not whole column groups, or kdrop is set\n", N); *fault = true; return; }
     for (int m = 0; m < M; ++m) {
         const int r0 = r0v ? r0v[m] : 0;
-        const int j0 = mode == 0 && kdrop ? r0 >> 4 : 0;
-        const FoldGeom gm = fold_geom_cut(mode, m, R, K, j0);
-        if (!(gm.nkp2 == 2 || gm.nkp2 == 4 || gm.nkp2 == 6) || gm.nkp2 < gm.nkp) { std::printf("bad nkp2 %d\n", gm.nkp2); *fault = true; return; }
+        const int j0 = !big && mode == 0 && kdrop ? r0 >> 4 : 0;
+        const FoldGeom gm = big ? fold_geom(mode, m, R, K) : fold_geom_cut(mode, m, R, K, j0);
+        const bool small_body = gm.nkp2 == 2 || gm.nkp2 == 4 || gm.nkp2 == 6, big_body = gm.nkp2 == 12 || gm.nkp2 == 18 || gm.nkp2 == 24;
+        const bool has_body = big ? (big_body || (mode == 1 && small_body)) : small_body;
+        if (!has_body || gm.nkp2 < gm.nkp) { std::printf("bad nkp2 %d (mode %d m %d, %s form)\n", gm.nkp2, mode, m, big ? "big" : "small"); *fault = true; return; }
         const int NKP = gm.nkp2;
         const int tp0 = mode == 1 ? r0 >> 5 : 0;
         const int npairs = gm.npairs > tp0 ? gm.npairs - tp0 : 0;
@@ -75,6 +90,8 @@ static void run_fold(int mode, const Plan& P, const StripPack& sp, const int* r0
         const size_t a_at = ((size_t)sp.tile_off[m] + (size_t)tp0 * 2 * NKP) * 1024;
         if (a_at + (size_t)nunits * NKP * 1024 > sp.frags.size()) { std::printf("table stream past the end (m %d)\n", m); *fault = true; return; }
         const uint16_t* Am = sp.frags.data() + a_at;
+        std::vector<double> Ad((size_t)nunits * NKP * 1024);   // this wavenumber's fragments as doubles, once for every column strip
+        for (size_t q = 0; q < Ad.size(); ++q) Ad[q] = (double)f16_bits_to_f32(Am[q]);
         for (int grp = 0; grp < G; ++grp)
             for (int wave = 0; wave < 4; ++wave) {
                 const int n0 = grp * 128 + wave * 32;
@@ -117,25 +134,30 @@ static void run_fold(int mode, const Plan& P, const StripPack& sp, const int* r0
                 }
                 // a unit's contraction in the kernel's k order, the table's lo and hi fragments as separate chains (the data operand
                 // stays one double here): a dropped k-step or a dead row only removes terms that are zero times a finite value
+                // (the 32 columns of a row advance together, each in that k order: bt is bf with the column index innermost)
+                std::vector<double> bt((size_t)2 * NKP * 16 * 32);
+                for (int par = 0; par < 2; ++par)
+                    for (int jj = 0; jj < NKP; ++jj)
+                        for (int lane = 0; lane < 64; ++lane)
+                            for (int e = 0; e < 8; ++e)
+                                bt[((((size_t)par * NKP + jj) * 2 + (lane >> 5)) * 8 + e) * 32 + (lane & 31)] = BF(par, jj, lane, e);
                 auto mfma_unit = [&](int u, double D[32][32]) {
                     const int par = u & 1;
-                    const uint16_t* unit = Am + (size_t)u * NKP * 1024;
-                    for (int ii = 0; ii < 32; ++ii)
-                        for (int jc = 0; jc < 32; ++jc) {
-                            double a0 = 0.0, a2 = 0.0;
-                            for (int jj = 0; jj < NKP; ++jj) {
-                                const uint16_t* blk = unit + (size_t)jj * 1024;
-                                for (int g = 0; g < 2; ++g)
-                                    for (int e = 0; e < 8; ++e) {
-                                        const double hi = (double)f16_bits_to_f32(blk[(ii + 32 * g) * 8 + e]);
-                                        const double lo = (double)f16_bits_to_f32(blk[512 + (ii + 32 * g) * 8 + e]);
-                                        const double b = BF(par, jj, jc + 32 * g, e);
-                                        a0 += lo * b;
-                                        a2 += hi * b;
-                                    }
-                            }
-                            D[ii][jc] = a0 + a2;
+                    const double* unit = Ad.data() + (size_t)u * NKP * 1024;
+                    for (int ii = 0; ii < 32; ++ii) {
+                        double a0[32], a2[32];
+                        for (int jc = 0; jc < 32; ++jc) a0[jc] = a2[jc] = 0.0;
+                        for (int jj = 0; jj < NKP; ++jj) {
+                            const double* blk = unit + (size_t)jj * 1024;
+                            for (int g = 0; g < 2; ++g)
+                                for (int e = 0; e < 8; ++e) {
+                                    const double hi = blk[(ii + 32 * g) * 8 + e], lo = blk[512 + (ii + 32 * g) * 8 + e];
+                                    const double* b = &bt[((((size_t)par * NKP + jj) * 2 + g) * 8 + e) * 32];
+                                    for (int jc = 0; jc < 32; ++jc) { a0[jc] += lo * b[jc]; a2[jc] += hi * b[jc]; }
+                                }
                         }
+                        for (int jc = 0; jc < 32; ++jc) D[ii][jc] = a0[jc] + a2[jc];
+                    }
                 };
                 auto store = [&](const RowMap rm, double D[32][32], bool inner) {
                     const bool fulln = N % 128 == 0;
@@ -239,7 +261,7 @@ static void check_tables(const Plan& P, const char* name, double lo_share, doubl
     }
     const double share = (double)dead / ((double)M * H);
     CHECK(std::fabs(share - c.dead_share) < 1e-12, "%s: dead share %.6f vs %.6f", name, share, c.dead_share);
-    CHECK(share >= lo_share && share <= hi_share, "%s: dead share %.4f outside [%.2f, %.2f]", name, share, lo_share, hi_share);
+    CHECK(share >= lo_share && share <= hi_share, "%s: dead share %.4f outside [%.4f, %.4f]", name, share, lo_share, hi_share);
     std::vector<char> live_at_r0((size_t)M, 0);
     for (int mode = 0; mode < 2; ++mode) {
         const StripPack& sp = mode == 0 ? P.fwd : P.inv;
@@ -359,6 +381,11 @@ int main() {
         {180, 360, GRID_LEGENDRE_GAUSS, "180x360 legendre-gauss", 0.23, 0.26, 32, 0},
         {180, 360, GRID_EQUIANGULAR, "180x360 equiangular", 0.0, 1.0, 32, 0},
         {181, 360, GRID_LOBATTO, "181x360 lobatto", 0.0, 1.0, 32, 0},
+        // big form: first size past the small form; 12 k16-steps at half a degree; 18 steps with an odd nlat; equiangular, odd nlat
+        {194, 48, GRID_LEGENDRE_GAUSS, "194x48 legendre-gauss", 0.0, 1.0, 128, 0},
+        {360, 720, GRID_LEGENDRE_GAUSS, "360x720 legendre-gauss", 0.2750, 0.2950, 128, 0},
+        {385, 720, GRID_LEGENDRE_GAUSS, "385x720 legendre-gauss", 0.2486, 0.2686, 128, 0},
+        {361, 720, GRID_EQUIANGULAR, "361x720 equiangular", 0.2760, 0.2960, 128, 0},
     };
     for (auto& cs : cases) {
         Plan P;

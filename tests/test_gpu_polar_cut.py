@@ -7,7 +7,11 @@ dead entries unwritten, so a kernel that still read one would turn the output in
 
 Shapes: width 48 has the two-level FFT (both halves of either pair take the cut), 23 x 48 the self-mirrored middle row, width 92
 only the matrix DFT (pairing rule: Legendre window on, FFT cut off, the inverse Legendre kernel keeps writing its zeros), 180 x 360
-is the benchmark grid.  The reference of every comparison is the library itself without the cut, so equality is exact."""
+is the benchmark grid.  The reference of every comparison is the library itself without the cut, so equality is exact.  That the cut
+was on at all is asserted through ace_sht_plan_cut: a dead share above zero on the plan with the cut (with the forward table's dead
+k16-steps dropped at 180 x 360), none on the other."""
+
+import ctypes
 
 import pytest
 import torch
@@ -40,6 +44,13 @@ def make_pair(nlat, nlon):
     return fwd, inv
 
 
+def plan_cut(module):
+    from ace_amd import _lib
+    share, kdrop = ctypes.c_double(-1.0), ctypes.c_int(-9)
+    _lib.check(_lib.lib().ace_sht_plan_cut(module._get_plan().handle, ctypes.byref(share), ctypes.byref(kdrop)))
+    return share.value, kdrop.value
+
+
 def fields(n, nlat, nlon, dev, seed):
     return torch.randn(n, nlat, nlon, generator=torch.Generator().manual_seed(seed)).to(dev)
 
@@ -62,6 +73,11 @@ def test_public_transforms_equal_the_plan_without_the_cut(dev, monkeypatch, n, n
     set_cut(monkeypatch, True)
     f1, i1 = make_pair(nlat, nlon)
     got_c, got_x = f1(x).clone(), i1(c).clone()
+    assert plan_cut(f0) == (0.0, 0), plan_cut(f0)
+    share, kdrop = plan_cut(f1)
+    assert share > 0.0, "the plan has no polar cut: the comparison below would pass vacuously"
+    if (nlat, nlon) == (180, 360):
+        assert kdrop == 1, kdrop
     assert torch.isfinite(torch.view_as_real(want_c)).all() and torch.isfinite(want_x).all()
     assert torch.equal(torch.view_as_real(got_c), torch.view_as_real(want_c)), "forward differs"
     assert torch.equal(got_x, want_x), "inverse differs"
