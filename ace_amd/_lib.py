@@ -212,6 +212,8 @@ SIGNATURES = {
     "ace_diag_fill_scratch_doubles": (c_long, [c_int, c_int, c_int, c_int, c_int]),
     # srcs, strides, tab, layers, blurred, nmasks, scratch, dst, nnames, batch, steps, nlat, nlon, stream
     "ace_diag_fill_planes": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
+    # srcs, strides, rows, edges, sums, means, nrows, nseg, nplanes, batch, steps, hw, stream
+    "ace_diag_time_segments": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_long, c_void_p]),
 }
 
 _lib = None

@@ -13,6 +13,9 @@ Mirrors, on plain ``name -> tensor`` dicts:
 netCDF / xarray are not on the path (and not in this image): ``TensorFileWriter`` keeps the reference's writer interface and file
 stems but stores ``torch.save`` archives (``restart.pt`` holds exactly the prognostic names and shapes ``restart.nc`` would).
 Derived variables (``compute_derived_variables``) are torch ops on the window's output series (ace_amd/derived_variables.py).
+The writers that reduce in time - block means, monthly means, the ``DataWriterConfig`` fan-out - are ace_amd/data_writer.py; the
+drivers hand a writer that declares ``uses_time`` / ``needs_time`` the time axis of the batch's steps and one that declares
+``paired`` the target (``_append_batch``), and call every other writer as before.
 
 The feeder keeps one window ahead: while window i runs on the compute stream, window i + 1 is copied host -> HBM from pinned
 memory on a side stream (85 MB for a 40-step window of 8 forcing fields at 1 degree: ~2 ms at PCIe rates against ~330 ms of
@@ -134,6 +137,7 @@ class Looper:
         self._prognostic_state = data.initial_condition
         self._len = len(data.loader)
         self._loader = iter(data.loader)
+        self._time = None
 
     def __iter__(self):
         return self
@@ -141,8 +145,15 @@ class Looper:
     def __len__(self) -> int:
         return self._len
 
+    def get_time(self):
+        """The ``TimeAxis`` of the steps of the last batch (the window's time levels after the first), ``None`` for a loader built
+        without ``time=``."""
+        return self._time
+
     def __next__(self) -> TensorDict:
         forcing = next(self._loader)
+        time = getattr(forcing, "time", None)
+        self._time = None if time is None else time[:, 1:]
         if self._derived:
             output, self._prognostic_state = self._predict(self._prognostic_state, forcing, compute_derived_variables=True)
         else:
@@ -167,10 +178,11 @@ class NullDataWriter:
 class TensorFileWriter:
     """Writer with the reference's interface (fme/core/generics/writer.py): ``write(state, "restart.nc")`` stores
     ``<dir>/restart.pt``; ``append_batch`` collects the windows (optionally a subset of names) and ``flush`` stores them
-    concatenated along time as ``<dir>/autoregressive_predictions.pt``."""
+    concatenated along time as ``<dir>/<label>.pt`` (``autoregressive_predictions.pt``)."""
 
-    def __init__(self, directory: str, names: Optional[Sequence[str]] = None):
+    def __init__(self, directory: str, names: Optional[Sequence[str]] = None, label: str = "autoregressive_predictions"):
         self._dir = directory
+        self._label = label
         self._names = None if names is None else list(names)
         self._windows: List[TensorDict] = []
         os.makedirs(directory, exist_ok=True)
@@ -186,7 +198,21 @@ class TensorFileWriter:
     def flush(self):
         if self._windows:
             out = {k: torch.cat([w[k] for w in self._windows], dim=1) for k in self._windows[0]}
-            torch.save(out, os.path.join(self._dir, "autoregressive_predictions.pt"))
+            torch.save(out, os.path.join(self._dir, self._label + ".pt"))
+
+
+def _append_batch(writer, batch: TensorDict, time=None, target: Optional[TensorDict] = None):
+    """``writer.append_batch`` in the shape the writer declares (ace_amd/data_writer.py): ``append_batch(batch=)`` for a writer
+    without the attributes below, as ever; ``time=`` too for one with ``uses_time`` when the window has a time axis, which one with
+    ``needs_time`` insists on; ``target=`` too for one with ``paired``, from ``run_evaluator``."""
+    kwargs = {}
+    if getattr(writer, "needs_time", False) and time is None:
+        raise ValueError("this writer needs the windows' time axis: build the ForcingWindows with time=")
+    if time is not None and (getattr(writer, "uses_time", False) or getattr(writer, "needs_time", False)):
+        kwargs["time"] = time
+    if target is not None and getattr(writer, "paired", False):
+        kwargs["target"] = target
+    writer.append_batch(batch=batch, **kwargs)
 
 
 def run_inference(predict: Callable, data: InferenceData, aggregator=None, writer=None,
@@ -203,7 +229,7 @@ def run_inference(predict: Callable, data: InferenceData, aggregator=None, write
             record_logs(logs)
     writer.write(data.initial_condition, "initial_condition.nc")
     for batch in looper:
-        writer.append_batch(batch=batch)
+        _append_batch(writer, batch, time=looper.get_time())
         if aggregator is not None:
             logs = aggregator.record_batch(data=batch)
             if record_logs is not None:
@@ -238,8 +264,8 @@ def run_evaluator(predict: Callable, data: InferenceData, aggregator, writer=Non
         target = {k: win[k][:, 1:] for k in out if k in win}
         if derive_target is not None:
             target.update({k: v[:, 1:] for k, v in derive_target(win, list(target)).items() if k in out})
-        writer.append_batch(batch=out)
-        needs, has = getattr(aggregator, "needs_time", False), getattr(win, "time", None) is not None
+        _append_batch(writer, out, time=win.time[:, 1:] if getattr(win, "time", None) is not None else None, target=target)
+        needs, has =getattr(aggregator, "needs_time", False), getattr(win, "time", None) is not None
         if needs and not has:                             # the trend metric regresses against the times of the window's steps
             raise ValueError("this aggregator needs the windows' time axis: build the ForcingWindows with time=")
         if needs or (has and getattr(aggregator, "uses_time", False)):      # the calendar metrics take it when there is one

@@ -519,6 +519,33 @@ int ace_couple_atmosphere_to_ocean(const float* const* srcs, const long* src_str
  *                  tile and a halo of 6 in LDS: one read of the source, one write of dst, no intermediate in device memory.  Two
  *                  launches (the plane means, the tiles), one when nmasks is 0; each pixel is written by one thread: no atomics,
  *                  bitwise repeatable; no allocation, no host synchronisation.
+ *   diag_time_segments: the data writers' reductions over time (fme/ace/inference/data_writer/time_coarsen.py:187-196, the block
+ *                  means of coarsen_factor steps; monthly.py:339-382, the sums over the steps of each calendar month), ace_amd/
+ *                  data_writer.py: per-pixel sums and means over runs of consecutive steps, for all names of a window from one read
+ *                  of every plane.  srcs / strides / rows: as diag_window, planes of hw contiguous fp32 starting at any 4-byte
+ *                  boundary.  edges: DEVICE int [batch][nseg + 1]; segment s of sample b is the steps [lo, hi) with
+ *                  lo = min(max(edges[b][s], 0), steps) and hi = min(max(edges[b][s + 1], 0), steps): every edge is clamped on
+ *                  the device, so no content of this table can make the kernel read outside a plane.  hi <= lo (an edge below
+ *                  its predecessor) is an empty segment; nothing asks the edges to ascend, segments cut from a table that does
+ *                  not may overlap, and a step no segment covers is not read.
+ *                  For plane j, sample b, segment s and pixel p:  acc = 0.0;  for t ascending from lo to hi - 1:
+ *                  acc += (double)x[b][t][p];  then, both assignments, not +=:
+ *                    sums  (DEVICE fp64 [nrows][batch][nseg][hw], may be NULL)  [rows[j]][b][s][p] = acc
+ *                    means (DEVICE fp32 [nrows][batch][nseg][hw], may be NULL)  [rows[j]][b][s][p] = (float)(acc / (double)(hi - lo))
+ *                  The adds are plain fp64 adds in step order with no reassociation and the division is the IEEE fp64 one, so a
+ *                  host statement in fp64 arithmetic reproduces both outputs bit for bit.  An empty segment gives sums 0 and
+ *                  means NaN (0.0 / 0.0).  NaN and infinity propagate (masked ocean fields carry NaN).  The reference means in
+ *                  fp32 (torch's fp32 mean for the blocks; for the months a running fp32 update
+ *                  (old_mean * old_count + new_sum) / (old_count + n) once per window); here the sum is fp64 and is rounded
+ *                  once, the stance of the coupler: with u = 2^-24 and m = max |x| over the steps of one output pixel,
+ *                  |means - the reference's block mean| <= (f + 2) u m for blocks of f steps.
+ *                  At least one of sums and means must be given, or the call is refused (ACE_ERR_INVALID, nothing written).  A
+ *                  plane whose rows[j] is out of range [0, nrows) writes nothing.  rows must not name one row twice (two
+ *                  workgroups would assign the same slots); this is not checked.  nplanes == 0 or nseg == 0 is a no-op.
+ *                  1 <= batch <= 65535, nplanes <= 65535 (grid dimensions), steps >= 1.  A thread keeps the sums of its four
+ *                  pixels in registers and stores each segment's result as the segment closes: no scratch, each output slot
+ *                  written by one thread, no atomics, bitwise repeatable.  One launch however many planes; no allocation, no
+ *                  host synchronisation.
  * ------------------------------------------------------------------------------------------ */
 const char* ace_diag_last_error(void);
 long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
@@ -563,6 +590,8 @@ long ace_diag_fill_scratch_doubles(int nnames, int batch, int steps, int nlat, i
 int ace_diag_fill_planes(const float* const* srcs, const long* strides, const int* tab, const unsigned char* layers,
                          const float* blurred, int nmasks, double* scratch, float* dst, int nnames, int batch, int steps, int nlat,
                          int nlon, void* stream);
+int ace_diag_time_segments(const float* const* srcs, const long* strides, const int* rows, const int* edges, double* sums,
+                           float* means, int nrows, int nseg, int nplanes, int batch, int steps, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
