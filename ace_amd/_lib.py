@@ -78,6 +78,21 @@ class OceanFields(ctypes.Structure):
                 ("hfgeou", Plane)]
 
 
+class GemmRoute(ctypes.Structure):
+    """struct ace_gemm_route"""
+    _fields_ = [("family", c_int), ("tile", c_int)]
+
+
+class Conv1x1FusedDesc(ctypes.Structure):
+    """struct ace_conv1x1_fused_desc"""
+    _fields_ = [("x", c_void_p), ("x2", c_void_p), ("weight", c_void_p), ("bias", c_void_p), ("in_scale", c_void_p),
+                ("in_shift", c_void_p), ("res", c_void_p), ("res_scale", c_void_p), ("res_shift", c_void_p),
+                ("out_scale", c_void_p), ("out_shift", c_void_p), ("y", c_void_p), ("out_absmax", c_void_p),
+                ("n", c_int), ("cin", c_int), ("cin2", c_int), ("cout", c_int),
+                ("hw", c_long), ("in_pitch", c_long), ("out_pitch", c_long),
+                ("act", c_int), ("cap", c_float), ("engine", c_int)]
+
+
 # every symbol include/ace_sfno.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ace_last_error": (c_char_p, []),
@@ -93,6 +108,7 @@ SIGNATURES = {
     "ace_sht_tables_host": (c_int, [c_int, c_int, c_int, c_int, c_char_p, c_int, c_void_p]),
     "ace_conv1x1": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p]),
     "ace_conv1x1_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p]),
+    "ace_conv1x1_fused": (c_int, [POINTER(Conv1x1FusedDesc), POINTER(GemmRoute), c_void_p]),
     "ace_mlp_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_void_p]),
     "ace_dhconv_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ace_instance_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_long, c_void_p]),

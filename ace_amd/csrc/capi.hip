@@ -567,6 +567,118 @@ extern "C" int ace_conv1x1_f16x3(const float* x, const float* weight, const floa
     return ACE_OK;
 }
 
+// Bound of one source of ace_conv1x1_fused as its producer in the network would publish it, computed on the host from a copy of the
+// `planes` (sample, channel) rows of hw floats at `pitch`: max |x|, or with an affine (sc, sh per plane) the bound of x sc + sh over
+// each plane from its minimum and maximum, with the rounding slack of instnorm_stats_kernel.
+static int fused_source_bound(const float* x, long pitch, long hw, long planes, const float* sc, const float* sh, float* bound) {
+    std::vector<float> h((size_t)planes * hw);
+    HIP_TRY(hipMemcpy2D(h.data(), hw * sizeof(float), x, pitch * sizeof(float), hw * sizeof(float), planes, hipMemcpyDeviceToHost));
+    float b = 0.f;
+    for (long p = 0; p < planes; ++p) {
+        float lo = 3.0e38f, hi = -3.0e38f;
+        for (long j = 0; j < hw; ++j) { const float v = h[(size_t)p * hw + j]; lo = std::min(lo, v); hi = std::max(hi, v); }
+        if (sc) {
+            const float a = sc[p], c = sh[p];
+            const float bd = std::max(std::fabs(std::fmaf(lo, a, c)), std::fabs(std::fmaf(hi, a, c)));
+            b = std::max(b, bd + 1.1920929e-7f * std::fmaf(std::fabs(a), std::max(std::fabs(lo), std::fabs(hi)), std::fabs(c)));
+        } else {
+            b = std::max(b, std::max(std::fabs(lo), std::fabs(hi)));
+        }
+    }
+    *bound = b;
+    return ACE_OK;
+}
+
+extern "C" int ace_conv1x1_fused(const ace_conv1x1_fused_desc* d, ace_gemm_route* route, void* stream) {
+    if (!d || !d->x || !d->weight || !d->y || d->n <= 0 || d->cin <= 0 || d->cin2 < 0 || d->cout <= 0 || d->hw <= 0 ||
+        d->hw > 0x7fffffffL || d->in_pitch < d->hw || d->out_pitch < d->hw || (d->cin2 > 0) != (d->x2 != nullptr) ||
+        (d->in_scale != nullptr) != (d->in_shift != nullptr) || (d->res_scale != nullptr) != (d->res_shift != nullptr) ||
+        (d->res_scale && !d->res) || (d->out_scale != nullptr) != (d->out_shift != nullptr) || d->act < ACT_NONE || d->act > ACT_SILU ||
+        std::isnan(d->cap) || d->engine < 0 || d->engine > 2)
+        return fail(ACE_ERR_INVALID, "ace_conv1x1_fused: bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int K = d->cin + d->cin2, kp = (K + 31) & ~31;
+    const bool al_in = d->hw % 4 == 0 && d->in_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(d->x) & 15) == 0 &&
+                       (reinterpret_cast<uintptr_t>(d->x2) & 15) == 0;
+    if (d->engine == 1 && d->in_scale) return fail(ACE_ERR_INVALID, "ace_conv1x1_fused: the direct-to-LDS engine takes no input affine");
+    if (d->engine != 0 && !al_in)
+        return fail(ACE_ERR_INVALID, "ace_conv1x1_fused: engines 1 and 2 need hw % 4 == 0, in_pitch % 4 == 0 and 16-byte aligned x, x2");
+    if (d->engine == 2 && d->in_scale && kp > 1024)
+        return fail(ACE_ERR_INVALID, "ace_conv1x1_fused: the f16x3 engine keeps an input affine of at most 1024 (padded) channels");
+    GemmArgs g;
+    g.B = d->x; g.ldb = d->in_pitch; g.sB = (long)d->cin * d->in_pitch;
+    if (d->x2) { g.B2 = d->x2; g.ldb2 = d->in_pitch; g.sB2 = (long)d->cin2 * d->in_pitch; g.K1 = d->cin; }
+    g.bsc = d->in_scale; g.bsh = d->in_shift; g.sbs = d->in_scale ? K : 0;
+    g.C = d->y; g.ldc = d->out_pitch; g.sC = (long)d->cout * d->out_pitch;
+    g.bias = d->bias;
+    if (d->res) { g.R = d->res; g.ldr = d->in_pitch; g.sR = (long)d->cout * d->in_pitch; }
+    g.rsc = d->res_scale; g.rsh = d->res_shift; g.srs = d->res_scale ? d->cout : 0;
+    g.osc = d->out_scale; g.osh = d->out_shift;
+    g.M = d->cout; g.N = (int)d->hw; g.K = K; g.nbatch = d->n; g.act = d->act; g.cap = d->cap;
+    g.omax = d->out_absmax;
+    if (d->out_absmax) HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
+    DevBuf wpad, hi, lo, slots;
+    GemmRoute r;
+    if (d->engine == 0) {
+        g.A = d->weight; g.lda = K; g.a_kpad = 0;   // a caller's unpadded weight: never the direct-to-LDS kernel
+        r = gemm_route(g, false);
+        HIP_TRY(launch_gemm(g, s));
+    } else if (d->engine == 1) {
+        HIP_TRY(wpad.alloc((size_t)d->cout * kp, true));
+        HIP_TRY(hipMemcpy2DAsync(wpad.p, kp * sizeof(float), d->weight, K * sizeof(float), K * sizeof(float), d->cout,
+                                 hipMemcpyDeviceToDevice, s));
+        g.A = wpad.p; g.lda = kp; g.a_kpad = kp;
+        r = gemm_route(g, false);
+        if (r.family != 2) return fail(ACE_ERR_INVALID, "ace_conv1x1_fused: the launch does not qualify for the direct-to-LDS engine");
+        HIP_TRY(launch_gemm(g, s));
+    } else {
+        // weight: absmax -> power-of-two scale -> hi / lo planes at the padded pitch, as ace_conv1x1_f16x3 prepares it
+        std::vector<float> host((size_t)d->cout * K);
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpy(host.data(), d->weight, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+        float mx = 0.f;
+        for (float v : host) mx = std::max(mx, std::fabs(v));
+        int e = 0;
+        if (mx > 0.f && std::isfinite(mx)) { (void)std::frexp(mx, &e); e = 10 - e; }
+        const float ascale = std::ldexp(1.0f, e);
+        const size_t halves = (size_t)d->cout * kp;
+        HIP_TRY(hi.alloc((halves + 1) / 2, false));
+        HIP_TRY(lo.alloc((halves + 1) / 2, false));
+        HIP_TRY(launch_split_f16(d->weight, K, hi.p, lo.p, kp, d->cout, K, ascale, s));
+        g.lda = kp; g.sA = 0; g.a_kpad = kp;
+        if (!gemm_f16x3_eligible(g)) return fail(ACE_ERR_INVALID, "ace_conv1x1_fused: the launch does not qualify for the f16x3 engine");
+        // range slots of the two sources (word 0 of 64 carries the bound, the others stay zero)
+        std::vector<float> sc, sh;
+        if (d->in_scale) {
+            sc.resize((size_t)d->n * K); sh.resize(sc.size());
+            HIP_TRY(hipMemcpy(sc.data(), d->in_scale, sc.size() * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(sh.data(), d->in_shift, sh.size() * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        float bound[2] = {0.f, 0.f};
+        for (int b = 0; b < d->n; ++b) {   // per sample: the affine's rows of a source are not contiguous over samples
+            for (int src = 0; src < (d->x2 ? 2 : 1); ++src) {
+                const int c0 = src ? d->cin : 0, nc = src ? d->cin2 : d->cin;
+                const float* base = (src ? d->x2 : d->x) + (long)b * nc * d->in_pitch;
+                float bb = 0.f;
+                ACE_TRY(fused_source_bound(base, d->in_pitch, d->hw, nc, d->in_scale ? sc.data() + (size_t)b * K + c0 : nullptr,
+                                           d->in_scale ? sh.data() + (size_t)b * K + c0 : nullptr, &bb));
+                bound[src] = std::max(bound[src], bb);
+            }
+        }
+        HIP_TRY(slots.alloc(2 * AMAX_SHARDS, true));
+        unsigned* xslot = reinterpret_cast<unsigned*>(slots.p);
+        HIP_TRY(hipMemcpy(xslot, &bound[0], sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(xslot + AMAX_SHARDS, &bound[1], sizeof(float), hipMemcpyHostToDevice));
+        if (g.act == ACT_GELU) g.act = ACT_GELU_FAST;   // as the network runs this engine
+        r = gemm_route(g, true);
+        g.omax = nullptr;
+        HIP_TRY(launch_gemm_f16x3(g, hi.p, lo.p, ascale, 1.0f, s, xslot, d->out_absmax, d->x2 ? xslot + AMAX_SHARDS : nullptr));
+    }
+    if (route) { route->family = r.family; route->tile = r.tile; }
+    HIP_TRY(hipStreamSynchronize(s));  // temporaries are freed on return
+    return ACE_OK;
+}
+
 // one-off preparation of a 1x1-conv weight for the f16x3 engines (what ace_sfno_set_weight does once per parameter)
 struct PreparedWeight { DevBuf hi, lo; int pitch = 0; float ascale = 1.f, winf = 0.f; };
 static int prepare_weight(const float* weight, int rows, int cols, hipStream_t s, PreparedWeight& out, bool tiled) {

@@ -74,6 +74,13 @@ struct GemmArgs {
 };
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 
+// Which kernel a GemmArgs launch takes: the ONE place that decides it (launch_gemm and launch_gemm_f16x3 both ask here).
+//   family 0 gemm_f32_kernel, scalar loads;  1 gemm_f32_kernel, 16-byte loads;  2 gemm2_f32_kernel (direct to LDS);
+//          3 gemm3_f16x3_kernel (f16x3 = true: the caller has checked gemm_f16x3_eligible)
+//   tile   1 = 128 x 128 iff M >= 128 and the rows wasted at 128 are no more than at 64, else 0 = 64 x 256
+struct GemmRoute { int family = 0; int tile = 0; };
+GemmRoute gemm_route(const GemmArgs& a, bool f16x3);
+
 // Compensated-fp16 engine (f16x3): same contract as launch_gemm, but the A operand is given pre-split into two
 // fp16 planes (hi, lo; pitch g.lda HALVES, rows zero-padded to a multiple of 32 columns: g.a_kpad), scaled by the
 // power of two `ascale`; B is scaled by the power of two `bscale` on the fly.  g.A is ignored.

@@ -755,9 +755,14 @@ __global__ __launch_bounds__(128 * WM * WN, 4) void gemm3_f16x3_kernel(Gemm3Args
     if (AFF) {  // per-row affine of B (fused instance norm), pre-multiplied by the power-of-two scale
         const float* bsc = p.bsc + (long)batch * p.sbs;
         const float* bsh = p.bsh + (long)batch * p.sbs;
-        for (int k = tid; k < K; k += NT) {
-            Aff[k] = bsc[k] * bscale_k;
-            Aff[G3_KAFF + k] = bsh[k] * bscale_k;
+        // The B stager reads the table in groups of 8 up to roundup(K, 32) and applies the entries past K to the clamped row K - 1.
+        // Those products meet zero A columns, but only a FINITE one vanishes there: the tail is written as the zero affine (0 x + 0),
+        // not left as whatever the LDS held (gemm_f16x3_eligible: roundup(K, 32) <= G3_KAFF with an affine)
+        const int kpad = (K + BKT - 1) / BKT * BKT;
+        for (int k = tid; k < kpad; k += NT) {
+            const bool in = k < K;
+            Aff[k] = in ? bsc[k] * bscale_k : 0.f;
+            Aff[G3_KAFF + k] = in ? bsh[k] * bscale_k : 0.f;
         }
         __syncthreads();
     }
@@ -1307,41 +1312,51 @@ static hipError_t launch_gemm2_cfg(const GemmArgs& a, hipStream_t s, int tilesM,
 #ifndef ACE_GEMM2_BK
 #define ACE_GEMM2_BK 32
 #endif
+#ifndef ACE_G3_W128_PCT
+#define ACE_G3_W128_PCT 0   // f16x3 engine: take the 128 x 128 tile when it wastes at most this share of its rows (else 64 x 256)
+#endif
 
-template <int WM, int WN>
-static hipError_t launch_gemm_cfg(const GemmArgs& a, hipStream_t s) {
-    constexpr int BM = 64 * WM, BN = 64 * WN, NT = 64 * WM * WN;
-    constexpr int BK2 = ACE_GEMM2_BK;
-    const int tilesM = (a.M + BM - 1) / BM, tilesN = (a.N + BN - 1) / BN;
-    const long nblk = (long)tilesM * tilesN * a.nbatch;
-    if (nblk <= 0) return hipSuccess;
+// The route of a launch (kernels.h): tile shape and kernel family, decided here and nowhere else.
+GemmRoute gemm_route(const GemmArgs& a, bool f16x3) {
+    GemmRoute r;
+    // 128x128 when the row count tiles well by 128, else 64x256 (M = 180/181-row spectral problems, M = 50)
+    const int waste128 = ((a.M + 127) / 128) * 128 - a.M;
+    const int waste64 = ((a.M + 63) / 64) * 64 - a.M;
+    r.tile = (a.M >= 128 && (waste128 <= waste64 || (f16x3 && waste128 * 100 <= ACE_G3_W128_PCT * (a.M + waste128)))) ? 1 : 0;
+    if (f16x3) { r.family = 3; return r; }
     bool vec = al16(a.A) && (a.lda % 4 == 0) && (a.sA % 4 == 0) && (a.K % 4 == 0) && al16(a.B) && (a.ldb % 4 == 0) &&
                (a.sB % 4 == 0) && (a.N % 4 == 0);
     if (a.B2) vec = vec && al16(a.B2) && (a.ldb2 % 4 == 0) && (a.sB2 % 4 == 0);
-    dim3 grid((unsigned)nblk), block(NT);
     // direct-to-LDS engine: needs zero-padded (or exact) A rows up to the stage depth and no per-k affine
+    constexpr int BK2 = ACE_GEMM2_BK;
     const int kround = ((a.K + BK2 - 1) / BK2) * BK2;
     const bool v2 = !g_force_v1 && al16(a.A) && (a.lda % 4 == 0) && (a.sA % 4 == 0) && al16(a.B) && (a.ldb % 4 == 0) &&
                     (a.sB % 4 == 0) && (a.N % 4 == 0) && (a.N >= 4) && (a.bsc == nullptr) && (a.a_kpad >= kround) &&
                     (!a.B2 || (al16(a.B2) && (a.ldb2 % 4 == 0) && (a.sB2 % 4 == 0))) && a.M >= 1 && a.K >= 1;
-    if (v2) return launch_gemm2_cfg<WM, WN, BK2>(a, s, tilesM, tilesN, grid, block);
-    if (vec) return launch_gemm_vec<WM, WN, true>(a, s, tilesM, tilesN, grid, block);
+    r.family = v2 ? 2 : (vec ? 1 : 0);
+    return r;
+}
+
+template <int WM, int WN>
+static hipError_t launch_gemm_cfg(const GemmArgs& a, hipStream_t s, int family) {
+    constexpr int BM = 64 * WM, BN = 64 * WN, NT = 64 * WM * WN;
+    const int tilesM = (a.M + BM - 1) / BM, tilesN = (a.N + BN - 1) / BN;
+    const long nblk = (long)tilesM * tilesN * a.nbatch;
+    if (nblk <= 0) return hipSuccess;
+    dim3 grid((unsigned)nblk), block(NT);
+    if (family == 2) return launch_gemm2_cfg<WM, WN, ACE_GEMM2_BK>(a, s, tilesM, tilesN, grid, block);
+    if (family == 1) return launch_gemm_vec<WM, WN, true>(a, s, tilesM, tilesN, grid, block);
     return launch_gemm_vec<WM, WN, false>(a, s, tilesM, tilesN, grid, block);
 }
 
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s) {
     if (a.brow) return hipErrorInvalidValue;   // row tables: f16x3 engine only
-    // 128x128 when the row count tiles well by 128, else 64x256 (M = 180/181-row spectral problems, M = 50)
-    const int waste128 = ((a.M + 127) / 128) * 128 - a.M;
-    const int waste64 = ((a.M + 63) / 64) * 64 - a.M;
-    if (a.M >= 128 && waste128 <= waste64) return launch_gemm_cfg<2, 2>(a, s);
-    return launch_gemm_cfg<1, 4>(a, s);
+    const GemmRoute r = gemm_route(a, false);
+    if (r.tile == 1) return launch_gemm_cfg<2, 2>(a, s, r.family);
+    return launch_gemm_cfg<1, 4>(a, s, r.family);
 }
 
 
-#ifndef ACE_G3_W128_PCT
-#define ACE_G3_W128_PCT 0   // f16x3 engine: take the 128 x 128 tile when it wastes at most this share of its rows (else 64 x 256)
-#endif
 template <int WM, int WN>
 static hipError_t launch_gemm3_cfg(const Gemm3Args& a, hipStream_t s) {
     constexpr int BM = 64 * WM, BN = 64 * WN, NT = 128 * WM * WN;  // MMA waves + loader waves
@@ -1387,9 +1402,7 @@ hipError_t launch_gemm_f16x3(const GemmArgs& g, const void* Ahi, const void* Alo
     a.oscale = bmax ? 1.0f / ascale : 1.0f / (ascale * bscale);
     a.bmax = bmax;
     a.omax = omax;
-    const int waste128 = ((g.M + 127) / 128) * 128 - g.M;
-    const int waste64 = ((g.M + 63) / 64) * 64 - g.M;
-    if (g.M >= 128 && (waste128 <= waste64 || waste128 * 100 <= ACE_G3_W128_PCT * (g.M + waste128))) return launch_gemm3_cfg<2, 2>(a, s);
+    if (gemm_route(g, true).tile == 1) return launch_gemm3_cfg<2, 2>(a, s);
     return launch_gemm3_cfg<1, 4>(a, s);
 }
 

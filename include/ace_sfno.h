@@ -86,6 +86,50 @@ int ace_conv1x1(const float* x, const float* weight, const float* bias, float* y
 int ace_conv1x1_f16x3(const float* x, const float* weight, const float* bias, float* y, int n, int cin, int cout,
                       long hw, int act, void* stream);
 
+/* The whole fused contract of the tile GEMM engines (every 1x1 convolution that is not on one of the packed / weight-stationary
+ * kernels), one launch, on the engine the caller names:
+ *
+ *   y = min(act(W . affine(x || x2) + bias + (res * res_scale + res_shift)), cap) * out_scale + out_shift
+ *
+ *   x (n, cin, hw) and the optional second source x2 (n, cin2, hw) are contracted as ONE (cin + cin2)-channel input without a
+ *   concatenated copy; weight (cout, cin + cin2) row-major, contiguous; bias (cout) or NULL;
+ *   in_scale / in_shift (n, cin + cin2), both or neither: the affine applied to the inputs as they are loaded (a fused instance norm);
+ *   res (n, cout, hw) or NULL, with res_scale / res_shift (n, cout), both or neither;
+ *   out_scale / out_shift (cout), both or neither: the affine applied last (a fused de-normalisation);
+ *   act as above, the activated value clamped from above by cap (INFINITY: no clamp);
+ *   in_pitch / out_pitch >= hw: floats between two channels of x, x2, res / of y; a sample's channels follow each other at the
+ *   same pitch (sample stride = channels x pitch).  The floats between hw and the pitch are neither read into a result nor written;
+ *   out_absmax: NULL, or 64 words that receive the bit pattern of max |y| over the stored values (the maximum over the 64 words
+ *   is the maximum; the entry zeroes them first).
+ *   engine 0: exact fp32, register-staged operands - 16-byte loads when every base, pitch, hw and cin + cin2 allow them, 4-byte
+ *             loads otherwise; any shape;
+ *          1: exact fp32, operands brought to LDS directly (the weight is copied to a pitch of roundup(cin + cin2, 32), zero
+ *             padded); takes no input affine and needs hw % 4 == 0, in_pitch % 4 == 0 and 16-byte aligned x, x2;
+ *          2: f16x3 (weight split as above; the dynamic-range slots of the two sources are derived as the network's producers
+ *             derive them: max |x| of a source, or the bound of its affine's output when one is given; GELU runs as the network
+ *             runs it on this engine, erf to 1.1e-7); needs hw % 4 == 0, in_pitch % 4 == 0, 16-byte aligned x, x2 and, with an
+ *             input affine, roundup(cin + cin2, 32) <= 1024.
+ * What an engine does not take is ACE_ERR_INVALID with a message, never another engine.  route (optional) receives what ran:
+ * family 0 register-staged with 4-byte loads, 1 register-staged with 16-byte loads, 2 direct to LDS, 3 f16x3; tile 0 = 64 x 256
+ * outputs per workgroup, 1 = 128 x 128 (taken iff cout >= 128 and it wastes no more rows than 64-row tiles would).
+ * Test / micro-benchmark entry: prepares its operands on every call and synchronises. */
+typedef struct ace_gemm_route { int family, tile; } ace_gemm_route;
+typedef struct ace_conv1x1_fused_desc {
+    const float* x; const float* x2;
+    const float* weight; const float* bias;
+    const float* in_scale; const float* in_shift;
+    const float* res; const float* res_scale; const float* res_shift;
+    const float* out_scale; const float* out_shift;
+    float* y;
+    unsigned* out_absmax;
+    int n, cin, cin2, cout;
+    long hw, in_pitch, out_pitch;
+    int act;
+    float cap;
+    int engine;
+} ace_conv1x1_fused_desc;
+int ace_conv1x1_fused(const ace_conv1x1_fused_desc* desc, ace_gemm_route* route, void* stream);
+
 /* MLP.forward (fme/ace/models/modulus/layers.py:97-137): y = W2 act(W1 x + b1) + b2 on (n, cin, hw) -> (n, cout, hw),
  * on the packed-operand f16x3 engine (the hidden activation is produced and consumed as pre-split fp16 planes and
  * never exists in fp32).  Needs cin % 8 == 0, hid % 8 == 0, hw % 4 == 0.  Test / micro-benchmark entry: prepares the
