@@ -93,6 +93,21 @@ class Conv1x1FusedDesc(ctypes.Structure):
                 ("act", c_int), ("cap", c_float), ("engine", c_int)]
 
 
+class DftRoute(ctypes.Structure):
+    """struct ace_dft_route"""
+    _fields_ = [("form", c_int), ("rows", c_int), ("units", c_int), ("rode", c_int)]
+
+
+class DftStageDesc(ctypes.Structure):
+    """struct ace_dft_stage_desc"""
+    _fields_ = [("inverse", c_int), ("engine", c_int), ("bt", c_int), ("c", c_int),
+                ("x", c_void_p), ("xhi", c_void_p), ("xlo", c_void_p), ("sxp", c_long), ("xslot", c_void_p),
+                ("in_scale", c_void_p), ("in_shift", c_void_p), ("spec_out", c_void_p),
+                ("spec", c_void_p), ("bias", c_void_p), ("y", c_void_p), ("mcut", c_void_p), ("out_absmax", c_void_p),
+                ("ride_weight", c_void_p), ("ride_o", c_int), ("ride_i", c_int), ("ride_order", c_int), ("ride_scale", c_float),
+                ("ride_dst", c_void_p), ("ride_dst_alone", c_void_p)]
+
+
 # every symbol include/ace_sfno.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ace_last_error": (c_char_p, []),
@@ -109,6 +124,7 @@ SIGNATURES = {
     "ace_conv1x1": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p]),
     "ace_conv1x1_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p]),
     "ace_conv1x1_fused": (c_int, [POINTER(Conv1x1FusedDesc), POINTER(GemmRoute), c_void_p]),
+    "ace_dft_stage": (c_int, [c_void_p, POINTER(DftStageDesc), POINTER(DftRoute), c_void_p]),
     "ace_mlp_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_void_p]),
     "ace_dhconv_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ace_instance_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_long, c_void_p]),

@@ -679,6 +679,82 @@ extern "C" int ace_conv1x1_fused(const ace_conv1x1_fused_desc* d, ace_gemm_route
     return ACE_OK;
 }
 
+// The longitude DFT stage as an operator: fills a DftArgs from the descriptor and the plan and calls launch_dft_forward /
+// launch_dft_inverse - with no_fft set for engine 0, and only after dft_*_fft_takes has said yes for engine 1, so that the launch
+// takes the form the caller named or none.
+extern "C" int ace_dft_stage(ace_sht_plan* plan, const ace_dft_stage_desc* d, ace_dft_route* route, void* stream) {
+    if (!plan || !d) return fail(ACE_ERR_INVALID, "ace_dft_stage: null plan or descriptor");
+    if (d->engine < 0 || d->engine > 1 || d->bt <= 0 || d->c <= 0 || (d->inverse != 0 && d->inverse != 1))
+        return fail(ACE_ERR_INVALID, "ace_dft_stage: bad argument");
+    const bool planes = d->xhi || d->xlo || d->xslot;
+    if (d->inverse) {
+        if (!d->spec || !d->y) return fail(ACE_ERR_INVALID, "ace_dft_stage: the inverse transform needs spec and y");
+        if (d->x || planes || d->in_scale || d->in_shift || d->spec_out || d->ride_weight)
+            return fail(ACE_ERR_INVALID, "ace_dft_stage: a forward operand given to the inverse transform");
+    } else {
+        if (!d->spec_out || (!d->x && !planes)) return fail(ACE_ERR_INVALID, "ace_dft_stage: the forward transform needs x (or the planes) and spec_out");
+        if (d->spec || d->y || d->bias) return fail(ACE_ERR_INVALID, "ace_dft_stage: an inverse operand given to the forward transform");
+        if ((d->in_scale != nullptr) != (d->in_shift != nullptr)) return fail(ACE_ERR_INVALID, "ace_dft_stage: in_scale and in_shift come together");
+        if (planes) {
+            if (d->x) return fail(ACE_ERR_INVALID, "ace_dft_stage: x and the planes are alternatives");
+            if (d->engine != 1) return fail(ACE_ERR_INVALID, "ace_dft_stage: the matrix form takes no planes input");
+            if (!d->xhi || !d->xlo || !d->xslot || d->c % 8 != 0 || d->sxp < (long)d->c * plan->nlat * plan->nlon)
+                return fail(ACE_ERR_INVALID, "ace_dft_stage: the planes input needs xhi, xlo, xslot, c % 8 == 0 and sxp >= c H W");
+        }
+    }
+    if (d->engine == 0 && d->mcut) return fail(ACE_ERR_INVALID, "ace_dft_stage: the matrix form does not look at mcut");
+    if (d->ride_weight) {
+        if (d->engine != 1) return fail(ACE_ERR_INVALID, "ace_dft_stage: the matrix form takes no rider job");
+        if (!d->ride_dst || !d->ride_dst_alone) return fail(ACE_ERR_INVALID, "ace_dft_stage: a rider job needs ride_dst and ride_dst_alone");
+    }
+    if ((double)plan->nlat * d->bt * d->c * 2.0 * std::max(plan->mmax, plan->nlon) >= 2147483647.0)
+        return fail(ACE_ERR_INVALID, "ace_dft_stage: a test entry for operands below 2^31 elements");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DftArgs a;
+    a.Bt = d->bt; a.C = d->c; a.H = plan->nlat; a.W = plan->nlon; a.Mm = plan->mmax; a.ldt = plan->Kfp;
+    a.no_fft = d->engine == 0;
+    a.mcut = d->mcut;
+    a.omax = d->out_absmax;
+    bool rode = false;
+    if (d->inverse) {
+        a.spec = d->spec; a.y = d->y; a.bias = d->bias; a.tc = plan->gc.p; a.ts = plan->gs.p;
+        if (d->engine == 1 && !dft_inverse_fft_takes(a))
+            return fail(ACE_ERR_INVALID, "ace_dft_stage: the FFT form takes W in {16, 24, 48, 360, 720, 1440} and a 16-byte aligned y");
+    } else {
+        a.x = d->x; a.xhi = static_cast<const _Float16*>(d->xhi); a.xlo = static_cast<const _Float16*>(d->xlo); a.sxp = d->sxp; a.xslot = d->xslot;
+        a.sc = d->in_scale; a.sh = d->in_shift; a.spec_out = d->spec_out; a.tc = plan->fc.p; a.ts = plan->fs.p;
+        if (d->engine == 1 && !dft_forward_fft_takes(a))
+            return fail(ACE_ERR_INVALID, "ace_dft_stage: the FFT form takes W in {16, 24, 48, 360, 720, 1440} and a 16-byte aligned x");
+        if (d->ride_weight) {
+            PackFragArgs q;
+            q.W = d->ride_weight; q.ldw = d->ride_i; q.O = d->ride_o; q.I = d->ride_i; q.order = d->ride_order;
+            q.scale_static = d->ride_scale; q.dst = static_cast<_Float16*>(d->ride_dst); q.nsamples = 1;
+            if (d->ride_o <= 0 || d->ride_i <= 0 || !pack_frag_args_ok(q)) return fail(ACE_ERR_INVALID, "ace_dft_stage: the rider job needs ride_o % 32 == 0 and ride_i % 16 == 0 (order 1: % 32)");
+            a.ride = q; a.nride = pack_frag_blocks(q); a.rode = &rode;
+            HIP_TRY(launch_pack_conv_frag(q.W, q.ldw, q.O, q.I, q.order, nullptr, 0.f, q.scale_static, nullptr, d->ride_dst_alone, 0, 1, s));
+        }
+    }
+    if (d->out_absmax) HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
+    HIP_TRY(d->inverse ? launch_dft_inverse(a, s) : launch_dft_forward(a, s));
+    if (route) {
+        const long cols = (long)a.H * a.Bt * a.C;
+        if (d->engine == 1) {
+            const int R = dft_fft_rows(a.W, d->inverse != 0), gx = (a.C + R - 1) / R;
+            route->form = 2; route->rows = R;
+            route->units = gx * (a.H + (rode ? (a.nride + gx - 1) / gx : 0));
+        } else if (d->inverse) {
+            route->form = dft_inverse_matrix_vs(a) ? 1 : 0; route->rows = 0;
+            route->units = (int)((cols + 127) / 128) * ((a.W / 2 + 1 + 63) / 64);
+        } else {
+            route->form = dft_forward_matrix_vx(a) ? 1 : 0; route->rows = 0;
+            route->units = ((a.Mm + 63) / 64) * (int)((cols + 127) / 128);
+        }
+        route->rode = rode ? 1 : 0;
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return ACE_OK;
+}
+
 // one-off preparation of a 1x1-conv weight for the f16x3 engines (what ace_sfno_set_weight does once per parameter)
 struct PreparedWeight { DevBuf hi, lo; int pitch = 0; float ascale = 1.f, winf = 0.f; };
 static int prepare_weight(const float* weight, int rows, int cols, hipStream_t s, PreparedWeight& out, bool tiled) {
@@ -1510,7 +1586,7 @@ static FwdRoute plan_route(const ace_sfno* n, int B, bool has_noise) {
     // Residual stream as planes only: once a block's fc2 (conv_ws mode 4) has written h' as P-format planes, the next block reads
     // them everywhere - longitude FFT, inner skip, outer-skip residual - and no fp32 copy of h' exists (fc2: 520 -> 420 MB)
     r.stream_ok = sw.planes_stream && f16 && !n->taps_on && n->plan_data == n->plan_lg.get() && C % 16 == 0 &&
-                  !n->plan_lg->sw.no_fft && dft_fft_has_width(n->W);
+                  !n->plan_lg->sw.no_fft && dft_fft_has_width(n->W) && dft_fft_planes_fit(n->H, n->W, B, C);
     r.blk.resize(nl);
 
     // ---- engines of each block (sfnonet.py:217-252): functions of the block's grids and of what was uploaded

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "fft_units.h"
 #include "kernels.h"
 #include "pack_frag.h"
 #include "small_fft.h"
@@ -90,47 +91,13 @@ struct ZPitch {
 };
 
 
-// Workgroup -> (channel block, latitude).  Workgroups go round-robin over the 8 XCDs by linear id, and every XCD has its own L2:
-// in launch order the R-row (64- or 128-byte) spectral runs of neighbouring channel blocks would be written from eight different
-// L2s as partial lines.  With a unit count divisible by 8, XCD x takes the contiguous unit range [x T/8, (x+1) T/8) instead, so
-// the channel blocks of one latitude share an L2 and leave it as whole lines.
-// (r03 same-box A/B at 1 degree: forward 71.7 -> 68.0 us; the inverse kernel, whose spectral side is READ in 128-byte runs,
-// got slower, 54.6 -> 59.1 us, and keeps launch order.)
+// Workgroup -> (channel block, latitude): fft_unit / fft_unit_ride of fft_units.h (shared with the CPU test of the mappings)
 #ifndef ACE_FFT_XCD
 #define ACE_FFT_XCD 1
 #endif
 #ifndef ACE_FFT_XCD_INV
 #define ACE_FFT_XCD_INV 0
 #endif
-template <bool XCD>
-FDEV void fft_unit(int& cblk, int& lat) {
-    const int gx = (int)gridDim.x, id = (int)blockIdx.x + gx * (int)blockIdx.y, total = gx * (int)gridDim.y;
-    int u = id;
-    if (XCD && (total & 7) == 0) u = (id & 7) * (total >> 3) + (id >> 3);
-    cblk = u % gx;
-    lat = u / gx;
-}
-// The forward kernel's form with RIDER workgroups (DftArgs::nride, pack_frag.h): the grid's y extent carries ceil(nride / gx) extra
-// rows; the riders are the FIRST units of every XCD's range - dispatched first, their slots go back to the transform's own
-// workgroups (at the end they would sit in the launch's tail; all on one XCD they cost its range 2 us).  Returns true for a rider
-// (index rid, idle when rid >= nride).
-template <bool XCD>
-FDEV bool fft_unit_ride(int nride, int& cblk, int& lat, int& rid) {
-    const int gx = (int)gridDim.x, id = (int)blockIdx.x + gx * (int)blockIdx.y, total = gx * (int)gridDim.y;
-    const int nextra = nride > 0 ? (nride + gx - 1) / gx * gx : 0;
-    int u;
-    if (XCD && (total & 7) == 0 && (nextra & 7) == 0) {
-        const int xcd = id & 7, pos = id >> 3, nr8 = nextra >> 3;
-        if (pos < nr8) { rid = pos * 8 + xcd; return true; }
-        u = xcd * ((total >> 3) - nr8) + (pos - nr8);
-    } else {
-        if (id < nextra) { rid = id; return true; }
-        u = id - nextra;
-    }
-    cblk = u % gx;
-    lat = u / gx;
-    return false;
-}
 
 // ---- forward ----------------------------------------------------------------------------------------------------------
 // grid = (ceil(C / R), H, Bt); block = R * N2.  LDS: the rows, then - aliased - Z.
@@ -174,7 +141,7 @@ __global__ __launch_bounds__(R * N2, N1 * N2 == 360 ? (PLN ? ACE_FFT_FWD_PLN_WAV
 
     const int tid = threadIdx.x;
     int cblk = 0, k = 0, rid = 0;
-    if (fft_unit_ride<ACE_FFT_XCD != 0>(p.nride, cblk, k, rid)) {
+    if (fft_unit_ride<ACE_FFT_XCD != 0>((int)blockIdx.x + (int)gridDim.x * (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y, p.nride, cblk, k, rid)) {
         // rider workgroup: one block of a weight-packing job (pack_frag.h), for every sample, from plane z = 0
         if (rid >= p.nride || blockIdx.z != 0) return;
         float* red = smem;
@@ -354,7 +321,7 @@ __global__ __launch_bounds__(R * N2, N1 * N2 == 360 ? (PLN ? ACE_FFT_FWD_PLN_WAV
     }
 }
 
-template <int N1, int N2, int R = FFT_ROWS>
+template <int N1, int N2, int R>
 hipError_t launch_fwd(const DftArgs& a0, hipStream_t s) {
     DftArgs a = a0;
     const int gx = (a.C + R - 1) / R;
@@ -400,7 +367,7 @@ __global__ __launch_bounds__(R * N2, N1 * N2 == 360 ? ACE_FFT_INV_WAVES : (N1 * 
 
     const int tid = threadIdx.x;
     int cblk, k;
-    fft_unit<XCD>(cblk, k);
+    fft_unit<XCD>((int)blockIdx.x + (int)gridDim.x * (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y, cblk, k);
     const int c0 = cblk * R, b = blockIdx.z;
     const int kb = k * p.Bt + b;
     const long HW = (long)p.H * W;
@@ -520,7 +487,7 @@ __global__ __launch_bounds__(R * N2, N1 * N2 == 360 ? ACE_FFT_INV_WAVES : (N1 * 
     }
 }
 
-template <int N1, int N2, int R = FFT_ROWS>
+template <int N1, int N2, int R>
 hipError_t launch_inv(const DftArgs& a, hipStream_t s) {
     dim3 grid((unsigned)((a.C + R - 1) / R), (unsigned)a.H, (unsigned)a.Bt), block(R * N2);
     // The spectral side is read in runs of R floats per wavenumber.  With R = 32 a run is a whole 128-byte line and launch order is
@@ -532,25 +499,36 @@ hipError_t launch_inv(const DftArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the kernels address with 32-bit lane offsets: at most (N1 + 1) spectral planes, and 32 grid rows, from a workgroup's base
-bool lane_offsets_fit(const DftArgs& a) {
-    const double plane = (double)a.H * a.Bt * 2.0 * a.C * 4.0, rows = 33.0 * (double)a.H * a.W * 4.0;
-    return 42.0 * plane < 2147483647.0 && rows < 2147483647.0;
-}
+// the kernels address with 32-bit lane offsets (fft_units.h: spectral planes, grid rows and - planes input - the sample's k-groups)
+bool lane_offsets_fit(const DftArgs& a) { return fft_lane_offsets_fit(a.H, a.W, a.Bt, a.C, a.xhi != nullptr); }
 
 }  // namespace
 
 // true when the FFT form handled the launch (sizes with an instantiated factorisation, 16-byte aligned rows)
+bool dft_forward_fft_takes(const DftArgs& a) {
+    return !(a.no_fft || (!a.xhi && (reinterpret_cast<uintptr_t>(a.x) & 15) != 0) || a.Mm > a.W / 2 + 1 || a.H > 65535 || a.Bt > 65535 || !lane_offsets_fit(a)) &&
+           dft_fft_has_width(a.W);
+}
+
+bool dft_fft_planes_fit(int H, int W, int Bt, int C) { return H <= 65535 && Bt <= 65535 && fft_lane_offsets_fit(H, W, Bt, C, true); }
+
+// channel rows per workgroup of the FFT form at width W - the R the launch_fwd / launch_inv instantiations below are given; 0: no such
+// form.  360 inverse: 32 rows, 128-byte runs on the spectral side (r02: 81.7 -> 75.6 us; the forward kernel is faster with 16);
+// 1440 (0.25-degree grid): 8 rows (46 KiB of LDS)
+constexpr int fft_rows(int W, bool inverse) {
+    return W == 360 ? (inverse ? ACE_FFT_INV_ROWS : FFT_ROWS) : W == 1440 ? ACE_FFT_QROWS : W == 720 ? 8 : (W == 48 || W == 24 || W == 16) ? FFT_ROWS : 0;
+}
+int dft_fft_rows(int W, bool inverse) { return fft_rows(W, inverse); }
+
 bool launch_dft_forward_fft(const DftArgs& a, hipStream_t s, hipError_t* err) {
-    if (a.no_fft || (!a.xhi && (reinterpret_cast<uintptr_t>(a.x) & 15) != 0) || a.Mm > a.W / 2 + 1 || a.H > 65535 || a.Bt > 65535 || !lane_offsets_fit(a))
-        return false;
+    if (!dft_forward_fft_takes(a)) return false;
     switch (a.W) {
-        case 360: *err = launch_fwd<20, 18>(a, s); return true;
-        case 1440: *err = launch_fwd<40, 36, ACE_FFT_QROWS>(a, s); return true;    // 0.25-degree grid: 8 channel rows per workgroup (46 KiB)
-        case 720: *err = launch_fwd<30, 24, 8>(a, s); return true;
-        case 48: *err = launch_fwd<8, 6>(a, s); return true;
-        case 24: *err = launch_fwd<6, 4>(a, s); return true;
-        case 16: *err = launch_fwd<4, 4>(a, s); return true;
+        case 360: *err = launch_fwd<20, 18, fft_rows(360, false)>(a, s); return true;
+        case 1440: *err = launch_fwd<40, 36, fft_rows(1440, false)>(a, s); return true;
+        case 720: *err = launch_fwd<30, 24, fft_rows(720, false)>(a, s); return true;
+        case 48: *err = launch_fwd<8, 6, fft_rows(48, false)>(a, s); return true;
+        case 24: *err = launch_fwd<6, 4, fft_rows(24, false)>(a, s); return true;
+        case 16: *err = launch_fwd<4, 4, fft_rows(16, false)>(a, s); return true;
         default: return false;
     }
 }
@@ -565,12 +543,12 @@ bool dft_inverse_fft_takes(const DftArgs& a) {
 bool launch_dft_inverse_fft(const DftArgs& a, hipStream_t s, hipError_t* err) {
     if (!dft_inverse_fft_takes(a)) return false;
     switch (a.W) {
-        case 360: *err = launch_inv<20, 18, ACE_FFT_INV_ROWS>(a, s); return true;   // 32 channel rows per workgroup: 128-byte runs on the spectral side (r02: 81.7 -> 75.6 us; the forward kernel is faster with 16)
-        case 1440: *err = launch_inv<40, 36, ACE_FFT_QROWS>(a, s); return true;
-        case 720: *err = launch_inv<30, 24, 8>(a, s); return true;
-        case 48: *err = launch_inv<8, 6>(a, s); return true;
-        case 24: *err = launch_inv<6, 4>(a, s); return true;
-        case 16: *err = launch_inv<4, 4>(a, s); return true;
+        case 360: *err = launch_inv<20, 18, fft_rows(360, true)>(a, s); return true;
+        case 1440: *err = launch_inv<40, 36, fft_rows(1440, true)>(a, s); return true;
+        case 720: *err = launch_inv<30, 24, fft_rows(720, true)>(a, s); return true;
+        case 48: *err = launch_inv<8, 6, fft_rows(48, true)>(a, s); return true;
+        case 24: *err = launch_inv<6, 4, fft_rows(24, true)>(a, s); return true;
+        case 16: *err = launch_inv<4, 4, fft_rows(16, true)>(a, s); return true;
         default: return false;
     }
 }

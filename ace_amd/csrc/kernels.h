@@ -311,11 +311,17 @@ struct DftArgs {
 };
 hipError_t launch_dft_forward(const DftArgs& a, hipStream_t s);
 hipError_t launch_dft_inverse(const DftArgs& a, hipStream_t s);
+// matrix form: does the launch take the 16-byte loads of x (forward: VX) / of spec (inverse: VS)?
+bool dft_forward_matrix_vx(const DftArgs& a);
+bool dft_inverse_matrix_vs(const DftArgs& a);
 // two-level FFT forms on the vector ALUs (fft.hip); return false when the size / alignment is not covered
 bool launch_dft_forward_fft(const DftArgs& a, hipStream_t s, hipError_t* err);
 bool launch_dft_inverse_fft(const DftArgs& a, hipStream_t s, hipError_t* err);
 bool dft_fft_has_width(int W);   // widths with an instantiated two-level FFT
 bool dft_inverse_fft_takes(const DftArgs& a);   // would launch_dft_inverse_fft handle this launch?
+bool dft_forward_fft_takes(const DftArgs& a);   // would launch_dft_forward_fft handle this launch?
+bool dft_fft_planes_fit(int H, int W, int Bt, int C);   // do the planes-input forward kernel's 32-bit lane offsets reach every k-group of a sample?
+int dft_fft_rows(int W, bool inverse);          // channel rows per workgroup of the FFT form at width W (0: no such form)
 
 // Conditional layer norm in one pass (cln_mfma.hip): statistics + the two conditioning 1x1 convolutions on MFMA + apply, for
 // C % 256 == 0 and H W % 32 == 0.  As / Ab: W_scale / W_bias as packed MFMA A fragments [C / 32][ceil(J / 16)][hi 512 | lo 512] halves

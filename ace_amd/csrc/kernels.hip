@@ -2500,6 +2500,9 @@ __global__ __launch_bounds__(256) void dft_forward_kernel(DftArgs p, int tilesM,
     }
 }
 
+bool dft_forward_matrix_vx(const DftArgs& a) { return al16(a.x) && (a.W % 4 == 0) && (a.W >= 8); }
+bool dft_inverse_matrix_vs(const DftArgs& a) { return al16(a.spec) && (a.C % 4 == 0); }
+
 hipError_t launch_dft_forward(const DftArgs& a, hipStream_t s) {
     hipError_t ferr = hipSuccess;
     if (launch_dft_forward_fft(a, s, &ferr)) return ferr;
@@ -2507,7 +2510,7 @@ hipError_t launch_dft_forward(const DftArgs& a, hipStream_t s) {
     constexpr int BM = 64, BN = 128;
     const int ncols = a.H * a.Bt * a.C;
     const int tilesM = (a.Mm + BM - 1) / BM, tilesN = (ncols + BN - 1) / BN;
-    const bool vx = al16(a.x) && (a.W % 4 == 0) && (a.W >= 8);
+    const bool vx = dft_forward_matrix_vx(a);
     dim3 grid((unsigned)(tilesM * tilesN)), block(256);
     if (vx)
         hipLaunchKernelGGL((dft_forward_kernel<true>), grid, block, 0, s, a, tilesM, tilesN);
@@ -2702,7 +2705,7 @@ hipError_t launch_dft_inverse(const DftArgs& a, hipStream_t s) {
     const int nrows = a.H * a.Bt * a.C;
     const int Kf = a.W / 2 + 1;
     const int tilesM = (nrows + BM - 1) / BM, tilesN = (Kf + BN - 1) / BN;
-    const bool vs = al16(a.spec) && (a.C % 4 == 0);
+    const bool vs = dft_inverse_matrix_vs(a);
     dim3 grid((unsigned)(tilesM * tilesN)), block(256);
     if (vs)
         hipLaunchKernelGGL((dft_inverse_kernel<true>), grid, block, 0, s, a, tilesM, tilesN);

@@ -130,6 +130,48 @@ typedef struct ace_conv1x1_fused_desc {
 } ace_conv1x1_fused_desc;
 int ace_conv1x1_fused(const ace_conv1x1_fused_desc* desc, ace_gemm_route* route, void* stream);
 
+/* The longitude DFT stage of the spectral blocks - the first and the last kernel of every transform - as an operator, one launch, on
+ * the engine the caller names, over an existing plan (which supplies H = nlat, W = nlon, Mm = mmax and the matrix form's tables; the
+ * plan's own polar cut is not used).  The spectral side is the library's internal layout X[m][lat][b][re | im][c], element
+ * ((m * H + lat) * bt + b) * 2 * c + ri * c + ch, Mm * H * bt * 2 * c floats.
+ *
+ *   inverse = 0:  spec_out[m] = (2 pi / W) sum_w (x[w] * in_scale + in_shift) e^(-2 pi i m w / W),  m < Mm
+ *                 (2 pi * rfft(norm = "forward"): fme/fft.py:61-77 under the 2 pi of fme/sht_fix.py).
+ *     x (bt, c, H, W), or - engine 1 only, c % 8 == 0 - the field as P-format fp16 planes xhi / xlo ([c / 8][H W][8] halves per sample,
+ *     sxp halves between samples; value = (hi + lo) / 2^e with e from the bound in the 64-word range slot xslot, as a producer
+ *     kernel writes them); x is then NULL.  in_scale / in_shift (bt, c), both or neither (a fused instance norm).
+ *   inverse = 1:  y = irfft(spec, n = W, norm = "forward") + bias with the imaginary parts of m = 0 and of a stored m = W / 2
+ *                 ignored and the wavenumbers from Mm on zero (fme/fft.py:78-96); spec as above, bias (c) or NULL, y (bt, c, H, W).
+ *   mcut: NULL, or H ints on the device (engine 1 only - the matrix kernels do not look at it, so engine 0 with mcut is refused):
+ *     at latitude lat the wavenumbers m >= mcut[lat] are NOT STORED by the forward transform (spec_out keeps what it held) and read
+ *     as zeros, without a load, by the inverse one.
+ *   out_absmax: NULL, or 64 words that receive the bit pattern of max |stored value| (the maximum over the 64 words is the maximum;
+ *     the entry zeroes them first).  The forward transform's maximum deliberately covers the entries mcut drops: the published bound
+ *     is what it is without the cut.
+ *   ride_weight (forward, engine 1): NULL, or a 1x1-convolution weight (ride_o, ride_i) row-major whose packing into MFMA A
+ *     fragments (order ride_order, the static power-of-two scale ride_scale, one sample, no fold) rides in the launch as extra
+ *     workgroups, into ride_dst ((ride_o / 32) (ride_i / 16) 1024 halves).  ride_dst_alone, of the same size, always receives the
+ *     same job from the stand-alone packing launch; when the riders did not ride (route: rode = 0) ride_dst is not written.
+ *   engine 0: the matrix form (fp32 MFMA against the plan's cos / sin tables): any width, 16-byte loads of x when x is 16-byte
+ *             aligned, W % 4 == 0 and W >= 8, of spec when it is 16-byte aligned and c % 4 == 0; takes no planes, no mcut, no rider;
+ *          1: the two-level FFT form: W in {16, 24, 48, 360, 720, 1440} and a 16-byte aligned x (forward) / y (inverse).
+ * What an engine does not take is ACE_ERR_INVALID with a message, never the other engine.  route (optional) receives what ran:
+ * form 0 matrix with 4-byte loads, 1 matrix with 16-byte loads, 2 FFT; rows = channel rows per workgroup (0 for the matrix form);
+ * units = workgroups in x * y of the grid; rode = 1 when the rider job rode in the launch.
+ * Test / micro-benchmark entry: synchronises. */
+typedef struct ace_dft_route { int form, rows, units, rode; } ace_dft_route;
+typedef struct ace_dft_stage_desc {
+    int inverse, engine, bt, c;
+    const float* x; const void* xhi; const void* xlo; long sxp; const unsigned* xslot;
+    const float* in_scale; const float* in_shift;
+    float* spec_out;
+    const float* spec; const float* bias; float* y;
+    const int* mcut;
+    unsigned* out_absmax;
+    const float* ride_weight; int ride_o, ride_i, ride_order; float ride_scale; void* ride_dst; void* ride_dst_alone;
+} ace_dft_stage_desc;
+int ace_dft_stage(ace_sht_plan* plan, const ace_dft_stage_desc* desc, ace_dft_route* route, void* stream);
+
 /* MLP.forward (fme/ace/models/modulus/layers.py:97-137): y = W2 act(W1 x + b1) + b2 on (n, cin, hw) -> (n, cout, hw),
  * on the packed-operand f16x3 engine (the hidden activation is produced and consumed as pre-split fp16 planes and
  * never exists in fp32).  Needs cin % 8 == 0, hid % 8 == 0, hw % 4 == 0.  Test / micro-benchmark entry: prepares the

@@ -74,3 +74,15 @@ def test_dhconv_work_list(tmp_path):
     res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout + res.stderr
     assert "worst" in res.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_fft_unit_mappings_and_offset_bound(tmp_path):
+    """ace_amd/csrc/fft_units.h (the workgroup -> (channel block, latitude) mappings of fft.hip, with and without rider workgroups,
+    and the bound on the kernels' 32-bit lane offsets): every unit exactly once, every rider exactly once and first in its XCD's
+    range, XCD ranges contiguous, over gx 1 .. 40 x H 1 .. 70 x eight rider counts; the bound at its boundaries, on the host only."""
+    exe = str(tmp_path / "fft_units_emul")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "emul", "fft_units_emul.cpp")], check=True)
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "combinations ok" in res.stdout
