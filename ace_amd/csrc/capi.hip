@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "strip_pack.h"
 #include "tables.h"
+#include "weight_prep.h"
 
 using namespace ace;
 
@@ -118,6 +119,35 @@ struct DevBuf {
     }
 };
 
+// `count` floats of a device array on the host, once the stream's pending writes to it have finished
+static int host_copy(const float* dev, size_t count, hipStream_t s, std::vector<float>& host) {
+    host.resize(count);
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(host.data(), dev, count * sizeof(float), hipMemcpyDeviceToHost));
+    return ACE_OK;
+}
+static float host_absmax(const std::vector<float>& v) {
+    float mx = 0.f;
+    for (float x : v) mx = std::max(mx, std::fabs(x));
+    return mx;
+}
+// a dynamic-range slot (AMAX_SHARDS words, each the bit pattern of a non-negative float) read back as the maximum it holds
+static int read_range_slot(const unsigned* slot, hipStream_t s, float* mx) {
+    unsigned bits[AMAX_SHARDS];
+    HIP_TRY(hipMemcpyAsync(bits, slot, sizeof(bits), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *mx = 0.f;
+    for (unsigned b : bits) { float f; std::memcpy(&f, &b, 4); *mx = std::max(*mx, f); }
+    return ACE_OK;
+}
+// max |x| of a device array, reduced on the device (a maximum rounds nothing: the value a host loop over a copy gives)
+static int device_absmax(const float* x, long count, hipStream_t s, float* mx) {
+    DevBuf slot;
+    HIP_TRY(slot.alloc(AMAX_SHARDS));
+    HIP_TRY(launch_absmax(x, count, reinterpret_cast<unsigned*>(slot.p), s));
+    return read_range_slot(reinterpret_cast<const unsigned*>(slot.p), s, mx);
+}
+
 // ---------------------------------------------------------------------------------------------
 // SHT plan
 // ---------------------------------------------------------------------------------------------
@@ -150,13 +180,7 @@ struct ace_sht_plan {
 };
 static int fold_route(const LegStripArgs& f) { return legendre_fold_is_big(f) ? 3 : 2; }
 
-static float pow2_scale_for(const std::vector<float>& v) {  // puts max|v| in [2^9, 2^10)
-    float mx = 0.f;
-    for (float x : v) mx = std::max(mx, std::fabs(x));
-    int e = 0;
-    if (mx > 0.f && std::isfinite(mx)) { (void)std::frexp(mx, &e); e = 10 - e; }
-    return std::ldexp(1.0f, e);
-}
+static float pow2_scale_for(const std::vector<float>& v) { return pow2_scale(host_absmax(v), 10); }  // puts max|v| in [2^9, 2^10)
 
 static int plan_build(int nlat, int nlon, int lmax, int mmax, Grid g, std::unique_ptr<ace_sht_plan>& out,
                       bool f16 = false) {
@@ -515,6 +539,56 @@ extern "C" int ace_sht_tables_host(int nlat, int nlon, int lmax, int mmax, const
 }
 
 // ---------------------------------------------------------------------------------------------
+// weight preparation for the f16x3 engines: what ace_sfno_set_weight stores once per parameter and the operator-level entries
+// below build on every call
+// ---------------------------------------------------------------------------------------------
+// A 1x1-conv weight (rows x cols): fp16 hi / lo planes of w * ascale at `pitch` = cols rounded up to 32 halves (rows rounded up to
+// 16, padding zero), row-major and / or in the packed engine's A-tile order, with the norms the output bounds are made of
+struct ConvOperand {
+    int pitch = 0;
+    DevBuf hi, lo;      // row-major planes (the on-the-fly-split engine)
+    DevBuf thi, tlo;    // the same planes in the v4 engine's A-tile order
+    float ascale = 1.f; // power of two that puts max|w| in [2^9, 2^10): hi and lo parts stay in fp16's normal range
+    float wabs = 0.f;   // max |w|
+    float winf = 0.f;   // max row sum of |w| (bounds |W x| by winf * max|x|)
+};
+enum { PLANES_ROWS = 1, PLANES_TILED = 2 };
+// w: device weight at pitch ld (the padded library copy or a caller's dense tensor).  Buffers `o` already owns are reused.
+static int prepare_conv_operand(const float* w, int rows, int cols, long ld, int forms, hipStream_t s, ConvOperand& o) {
+    std::vector<float> host;
+    ACE_TRY(host_copy(w, (size_t)rows * ld, s, host));
+    const WeightNorms nm = weight_norms(host.data(), rows, cols, ld);
+    o.wabs = nm.absmax; o.winf = nm.winf;
+    o.ascale = pow2_scale(nm.absmax, 10);
+    o.pitch = (cols + 31) & ~31;
+    const size_t halves = (size_t)((rows + 15) / 16 * 16) * o.pitch;
+    if (forms & PLANES_ROWS) {
+        if (!o.hi.p) HIP_TRY(o.hi.alloc((halves + 1) / 2, false));
+        if (!o.lo.p) HIP_TRY(o.lo.alloc((halves + 1) / 2, false));
+        HIP_TRY(launch_split_f16(w, ld, o.hi.p, o.lo.p, o.pitch, rows, cols, o.ascale, s));
+    }
+    if (forms & PLANES_TILED) {
+        if (!o.thi.p) HIP_TRY(o.thi.alloc((halves + 1) / 2, false));
+        if (!o.tlo.p) HIP_TRY(o.tlo.alloc((halves + 1) / 2, false));
+        HIP_TRY(launch_split_f16_tiled(w, ld, o.thi.p, o.tlo.p, o.pitch, rows, cols, o.ascale, s));
+    }
+    return ACE_OK;
+}
+// The conditioning convolution (C x J, dense) of a conditional layer norm as the MFMA A fragments of cln_mfma.hip, packed on the host
+// (strip_pack.h) at the scale returned in *ascale
+static int prepare_cln_frags(const float* w, int C, int J, hipStream_t s, DevBuf& frag, float* ascale, WeightNorms* norms) {
+    std::vector<float> host;
+    ACE_TRY(host_copy(w, (size_t)C * J, s, host));
+    *norms = weight_norms(host.data(), C, J, J);
+    *ascale = cln_frag_scale(norms->absmax);
+    std::vector<uint16_t> frags(cln_frag_halves(C, J));
+    pack_cln_frags(host.data(), C, J, *ascale, frags.data());
+    if (!frag.p) HIP_TRY(frag.alloc((frags.size() + 1) / 2, false));
+    HIP_TRY(hipMemcpy(frag.p, frags.data(), frags.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return ACE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // building blocks
 // ---------------------------------------------------------------------------------------------
 extern "C" int ace_conv1x1(const float* x, const float* weight, const float* bias, float* y, int n, int cin, int cout,
@@ -536,23 +610,10 @@ extern "C" int ace_conv1x1_f16x3(const float* x, const float* weight, const floa
     if (!x || !weight || !y || n <= 0 || cin <= 0 || cout <= 0 || hw <= 0)
         return fail(ACE_ERR_INVALID, "ace_conv1x1_f16x3: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int pitch = (cin + 31) & ~31;
-    // one-off weight preparation (what ace_sfno_set_weight does once per parameter): absmax -> power-of-two scale -> split
-    std::vector<float> host((size_t)cout * cin);
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(host.data(), weight, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-    float mx = 0.f;
-    for (float v : host) mx = std::max(mx, std::fabs(v));
-    int e = 0;
-    if (mx > 0.f && std::isfinite(mx)) { (void)std::frexp(mx, &e); e = 10 - e; }
-    const float ascale = std::ldexp(1.0f, e);
-    DevBuf hi, lo;
-    const size_t halves = (size_t)cout * pitch;
-    HIP_TRY(hi.alloc((halves + 1) / 2, false));
-    HIP_TRY(lo.alloc((halves + 1) / 2, false));
-    HIP_TRY(launch_split_f16(weight, cin, hi.p, lo.p, pitch, cout, cin, ascale, s));
+    ConvOperand w;
+    ACE_TRY(prepare_conv_operand(weight, cout, cin, cin, PLANES_ROWS, s, w));
     GemmArgs g;
-    g.lda = pitch; g.sA = 0; g.a_kpad = pitch;
+    g.lda = w.pitch; g.sA = 0; g.a_kpad = w.pitch;
     g.B = x; g.ldb = hw; g.sB = (long)cin * hw;
     g.C = y; g.ldc = hw; g.sC = (long)cout * hw;
     g.bias = bias; g.M = cout; g.N = (int)hw; g.K = cin; g.nbatch = n; g.act = act;
@@ -562,7 +623,7 @@ extern "C" int ace_conv1x1_f16x3(const float* x, const float* weight, const floa
     HIP_TRY(slotbuf.alloc(AMAX_SHARDS));
     unsigned* xslot = reinterpret_cast<unsigned*>(slotbuf.p);
     HIP_TRY(launch_absmax(x, (long)n * cin * hw, xslot, s));
-    HIP_TRY(launch_gemm_f16x3(g, hi.p, lo.p, ascale, 1.0f, s, xslot, nullptr));
+    HIP_TRY(launch_gemm_f16x3(g, w.hi.p, w.lo.p, w.ascale, 1.0f, s, xslot, nullptr));
     HIP_TRY(hipStreamSynchronize(s));  // temporaries are freed on return
     return ACE_OK;
 }
@@ -617,7 +678,8 @@ extern "C" int ace_conv1x1_fused(const ace_conv1x1_fused_desc* d, ace_gemm_route
     g.M = d->cout; g.N = (int)d->hw; g.K = K; g.nbatch = d->n; g.act = d->act; g.cap = d->cap;
     g.omax = d->out_absmax;
     if (d->out_absmax) HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
-    DevBuf wpad, hi, lo, slots;
+    DevBuf wpad, slots;
+    ConvOperand w;
     GemmRoute r;
     if (d->engine == 0) {
         g.A = d->weight; g.lda = K; g.a_kpad = 0;   // a caller's unpadded weight: never the direct-to-LDS kernel
@@ -632,19 +694,7 @@ extern "C" int ace_conv1x1_fused(const ace_conv1x1_fused_desc* d, ace_gemm_route
         if (r.family != 2) return fail(ACE_ERR_INVALID, "ace_conv1x1_fused: the launch does not qualify for the direct-to-LDS engine");
         HIP_TRY(launch_gemm(g, s));
     } else {
-        // weight: absmax -> power-of-two scale -> hi / lo planes at the padded pitch, as ace_conv1x1_f16x3 prepares it
-        std::vector<float> host((size_t)d->cout * K);
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(host.data(), d->weight, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-        float mx = 0.f;
-        for (float v : host) mx = std::max(mx, std::fabs(v));
-        int e = 0;
-        if (mx > 0.f && std::isfinite(mx)) { (void)std::frexp(mx, &e); e = 10 - e; }
-        const float ascale = std::ldexp(1.0f, e);
-        const size_t halves = (size_t)d->cout * kp;
-        HIP_TRY(hi.alloc((halves + 1) / 2, false));
-        HIP_TRY(lo.alloc((halves + 1) / 2, false));
-        HIP_TRY(launch_split_f16(d->weight, K, hi.p, lo.p, kp, d->cout, K, ascale, s));
+        ACE_TRY(prepare_conv_operand(d->weight, d->cout, K, K, PLANES_ROWS, s, w));
         g.lda = kp; g.sA = 0; g.a_kpad = kp;
         if (!gemm_f16x3_eligible(g)) return fail(ACE_ERR_INVALID, "ace_conv1x1_fused: the launch does not qualify for the f16x3 engine");
         // range slots of the two sources (word 0 of 64 carries the bound, the others stay zero)
@@ -672,7 +722,7 @@ extern "C" int ace_conv1x1_fused(const ace_conv1x1_fused_desc* d, ace_gemm_route
         if (g.act == ACT_GELU) g.act = ACT_GELU_FAST;   // as the network runs this engine
         r = gemm_route(g, true);
         g.omax = nullptr;
-        HIP_TRY(launch_gemm_f16x3(g, hi.p, lo.p, ascale, 1.0f, s, xslot, d->out_absmax, d->x2 ? xslot + AMAX_SHARDS : nullptr));
+        HIP_TRY(launch_gemm_f16x3(g, w.hi.p, w.lo.p, w.ascale, 1.0f, s, xslot, d->out_absmax, d->x2 ? xslot + AMAX_SHARDS : nullptr));
     }
     if (route) { route->family = r.family; route->tile = r.tile; }
     HIP_TRY(hipStreamSynchronize(s));  // temporaries are freed on return
@@ -755,30 +805,6 @@ extern "C" int ace_dft_stage(ace_sht_plan* plan, const ace_dft_stage_desc* d, ac
     return ACE_OK;
 }
 
-// one-off preparation of a 1x1-conv weight for the f16x3 engines (what ace_sfno_set_weight does once per parameter)
-struct PreparedWeight { DevBuf hi, lo; int pitch = 0; float ascale = 1.f, winf = 0.f; };
-static int prepare_weight(const float* weight, int rows, int cols, hipStream_t s, PreparedWeight& out, bool tiled) {
-    std::vector<float> host((size_t)rows * cols);
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(host.data(), weight, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-    float mx = 0.f;
-    for (int r = 0; r < rows; ++r) {
-        double rs = 0.0;
-        for (int c = 0; c < cols; ++c) { const float v = std::fabs(host[(size_t)r * cols + c]); mx = std::max(mx, v); rs += v; }
-        out.winf = std::max(out.winf, (float)(rs * (1.0 + 1e-6)));
-    }
-    int e = 0;
-    if (mx > 0.f && std::isfinite(mx)) { (void)std::frexp(mx, &e); e = 10 - e; }
-    out.ascale = std::ldexp(1.0f, e);
-    out.pitch = (cols + 31) & ~31;
-    const size_t halves = (size_t)((rows + 15) / 16 * 16) * out.pitch;
-    HIP_TRY(out.hi.alloc((halves + 1) / 2, false));
-    HIP_TRY(out.lo.alloc((halves + 1) / 2, false));
-    if (tiled) HIP_TRY(launch_split_f16_tiled(weight, cols, out.hi.p, out.lo.p, out.pitch, rows, cols, out.ascale, s));
-    else HIP_TRY(launch_split_f16(weight, cols, out.hi.p, out.lo.p, out.pitch, rows, cols, out.ascale, s));
-    return ACE_OK;
-}
-
 // The reference's MLP (fme/ace/models/modulus/layers.py:97-137: 1x1 conv -> activation -> 1x1 conv, drop_rate 0) on
 // the packed-operand f16x3 engine: x is split once into P format, fc1 writes the hidden activation straight in
 // P format (bound-scaled), fc2 consumes it by DMA.  Operator-level entry for tests / benchmarks.
@@ -789,14 +815,14 @@ extern "C" int ace_mlp_f16x3(const float* x, const float* w1, const float* b1, c
     if (cin % 8 != 0 || hid % 8 != 0 || hw % 4 != 0)
         return fail(ACE_ERR_INVALID, "ace_mlp_f16x3: needs cin % 8 == 0, hid % 8 == 0, hw % 4 == 0");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PreparedWeight p1, p2;
-    ACE_TRY(prepare_weight(w1, hid, cin, s, p1, true));
-    ACE_TRY(prepare_weight(w2, cout, hid, s, p2, true));
+    ConvOperand p1, p2;
+    ACE_TRY(prepare_conv_operand(w1, hid, cin, cin, PLANES_TILED, s, p1));
+    ACE_TRY(prepare_conv_operand(w2, cout, hid, hid, PLANES_TILED, s, p2));
     float b1max = 0.f;
     if (b1) {
-        std::vector<float> hb((size_t)hid);
-        HIP_TRY(hipMemcpy(hb.data(), b1, hb.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (float v : hb) b1max = std::max(b1max, std::fabs(v));
+        std::vector<float> hb;
+        ACE_TRY(host_copy(b1, (size_t)hid, s, hb));
+        b1max = host_absmax(hb);
     }
     DevBuf slots, xp, up;
     HIP_TRY(slots.alloc(2 * AMAX_SHARDS, true));
@@ -812,7 +838,7 @@ extern "C" int ace_mlp_f16x3(const float* x, const float* w1, const float* b1, c
     HIP_TRY(launch_pack_pformat(x, hw, (long)cin * hw, cin, (int)hw, n, nullptr, nullptr, 0, xslot, xh, xl, hw,
                                 (long)cin * hw, s));
     Gemm4Args a;
-    a.Ahi = reinterpret_cast<const _Float16*>(p1.hi.p); a.Alo = reinterpret_cast<const _Float16*>(p1.lo.p);
+    a.Ahi = reinterpret_cast<const _Float16*>(p1.thi.p); a.Alo = reinterpret_cast<const _Float16*>(p1.tlo.p);
     a.lda = p1.pitch; a.ascale = p1.ascale; a.a_tiled = 1;
     a.Bhi = xh; a.Blo = xl; a.ldn = hw; a.sB = (long)cin * hw; a.bmax = xslot;
     a.Chi = uh; a.Clo = ul; a.ldnc = hw; a.sCp = (long)hid * hw; a.cw = p1.winf; a.cb = b1max; a.cslot = uslot;
@@ -820,7 +846,7 @@ extern "C" int ace_mlp_f16x3(const float* x, const float* w1, const float* b1, c
     a.act = act == ACT_GELU ? ACT_GELU_FAST : act;
     HIP_TRY(launch_gemm_f16x3_packed(a, s));
     Gemm4Args b;
-    b.Ahi = reinterpret_cast<const _Float16*>(p2.hi.p); b.Alo = reinterpret_cast<const _Float16*>(p2.lo.p);
+    b.Ahi = reinterpret_cast<const _Float16*>(p2.thi.p); b.Alo = reinterpret_cast<const _Float16*>(p2.tlo.p);
     b.lda = p2.pitch; b.ascale = p2.ascale; b.a_tiled = 1;
     b.Bhi = uh; b.Blo = ul; b.ldn = hw; b.sB = (long)hid * hw; b.bmax = uslot;
     b.C = y; b.ldc = hw; b.sC = (long)cout * hw;
@@ -861,16 +887,10 @@ extern "C" int ace_dhconv_f16x3(const float* coeffs, const float* weight, float*
     HIP_TRY(launch_ref_to_spec(coeffs, D.p, n, c, L, Mm, s));
     HIP_TRY(launch_absmax(D.p, (long)spec, dslot, s));
     HIP_TRY(launch_absmax(weight, (long)c * c * L * 2, wslot, s));
-    unsigned bits[2 * AMAX_SHARDS];
-    HIP_TRY(hipMemcpyAsync(bits, slots.p, sizeof(bits), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
     float dmx = 0.f, wmx = 0.f;
-    for (int k = 0; k < AMAX_SHARDS; ++k) {
-        float f; std::memcpy(&f, &bits[k], 4); dmx = std::max(dmx, f);
-        std::memcpy(&f, &bits[AMAX_SHARDS + k], 4); wmx = std::max(wmx, f);
-    }
-    auto pow2 = [](float mx, int top) { int e = 0; if (mx > 0.f && std::isfinite(mx)) { (void)std::frexp(mx, &e); e = top - e; } return std::ldexp(1.0f, e); };
-    const float dscale = pow2(dmx, 12), wscale = pow2(wmx, 10);   // the kernel derives 2^(12 - exponent) from the slot itself
+    ACE_TRY(read_range_slot(dslot, s, &dmx));
+    ACE_TRY(read_range_slot(wslot, s, &wmx));
+    const float dscale = pow2_scale(dmx, 12), wscale = pow2_scale(wmx, 10);   // the kernel derives 2^(12 - exponent) from the slot itself
     HIP_TRY(launch_split_f16(D.p, N2, Dp.p, reinterpret_cast<_Float16*>(Dp.p) + spec, N2, (long)L * Mm, (int)N2, dscale, s));
     HIP_TRY(launch_pack_dhconv_f16c(weight, Wh.p, Wl.p, c, c, L, wscale, s));
     DhconvStripArgs ds;
@@ -936,23 +956,10 @@ extern "C" int ace_conditional_layer_norm_f16x3(const float* x, const float* noi
         if (!cln_mfma_eligible(probe))
             return fail(ACE_ERR_INVALID, "ace_conditional_layer_norm_f16x3: needs c % 256 == 0 (c <= 1024), hw % 4 == 0 (c > 512: hw % 32 == 0), noise_dim <= 128");
     }
-    if (w_scale) {   // one-off weight preparation (what ace_sfno_set_weight does once per parameter) + the conditioning field's bound
-        const size_t halves = cln_frag_halves(c, noise_dim);
-        std::vector<float> host((size_t)c * noise_dim);
-        std::vector<uint16_t> frags(halves);
-        int k = 0;
-        for (const float* wsrc : {w_scale, w_bias}) {
-            HIP_TRY(hipMemcpy(host.data(), wsrc, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-            float mx = 0.f;
-            for (float v : host) mx = std::max(mx, std::fabs(v));
-            const float sc = cln_frag_scale(mx);
-            pack_cln_frags(host.data(), c, noise_dim, sc, frags.data());
-            DevBuf& dst = k == 0 ? fs : fb;
-            HIP_TRY(dst.alloc((halves + 1) / 2, false));
-            HIP_TRY(hipMemcpy(dst.p, frags.data(), halves * sizeof(uint16_t), hipMemcpyHostToDevice));
-            (k == 0 ? a.ascale_s : a.ascale_b) = sc;
-            ++k;
-        }
+    if (w_scale) {   // the two conditioning convolutions as fragments + the conditioning field's bound
+        WeightNorms nm;
+        ACE_TRY(prepare_cln_frags(w_scale, c, noise_dim, s, fs, &a.ascale_s, &nm));
+        ACE_TRY(prepare_cln_frags(w_bias, c, noise_dim, s, fb, &a.ascale_b, &nm));
         HIP_TRY(cslot.alloc(AMAX_SHARDS));
         HIP_TRY(launch_absmax(noise, (long)n * noise_dim * hw, reinterpret_cast<unsigned*>(cslot.p), s));
         a.cond = noise; a.scond = (long)noise_dim * hw; a.J = noise_dim; a.cslot = reinterpret_cast<const unsigned*>(cslot.p);
@@ -982,22 +989,27 @@ extern "C" int ace_unpack_denormalize(const float* src, const float* mean, const
 // ---------------------------------------------------------------------------------------------
 // the network
 // ---------------------------------------------------------------------------------------------
-struct Weight {
+// What a parameter is to the forward: decides which derived operands ace_sfno_set_weight stores with the library copy
+enum ParamRole {
+    ROLE_PLAIN,      // library copy only (the (H, W) affine fields of "layer_norm")
+    ROLE_VECTOR,     // biases and per-channel norm affines: + max |value|, the bound term of the P-format producers
+    ROLE_POS_EMBED,  // + its bound as a range slot (the residual of the last encoder convolution)
+    ROLE_ENC_CONV, ROLE_ENC_LAST, ROLE_DEC_CONV, ROLE_SKIP, ROLE_FC1, ROLE_FC2,   // 1x1 convolutions: + planes and norms, some + fragments
+    ROLE_FILTER,     // spectral filter: + the contraction's operand (native, compact or expanded)
+    ROLE_CLN_COND    // conditioning convolution of a conditional layer norm: + cln_mfma.hip's fragments
+};
+struct Weight : ConvOperand {   // (the ConvOperand part: conv roles of an f16x3 net; ascale / wabs / winf also of ROLE_CLN_COND)
     std::string name;
+    ParamRole role = ROLE_PLAIN;
     long numel = 0;
     DevBuf buf;    // library copy (reference layout; conv weights: rows zero-padded to `pitch`)
     bool set = false;
     int block = -1;
-    bool is_filter = false;
-    long ext_numel = 0;  // numel of the caller's tensor when it differs from the library copy (grouped csfno filter)
-    int rows = 0, cols = 0, pitch = 0;  // conv weights (rows x cols), pitch = cols rounded up to 32
-    DevBuf hi, lo;      // f16x3 mode: fp16 planes of the conv weight scaled by `ascale` (pitch halves)
-    float ascale = 1.f;
-    DevBuf thi, tlo;    // the same planes in the v4 engine's A-tile order (rows padded to 16)
-    DevBuf frag0;       // inner_skip / mlp.fwd.2 / last encoder convolution: packed MFMA A fragments (conv_ws.hip, static weights)
-    float wabs = 0.f;   // conv weights: max |w|
-    float winf = 0.f;   // conv weights: max row sum of |w| (bounds |W x| by winf * max|x|)
-    float absmax = 0.f; // small parameters (biases): max |value|
+    long hw = 0;         // pixels of the grid the role's consumer runs on (block i: block_out_pixels; encoder / decoder: the data grid)
+    long ext_numel = 0;  // grouped csfno filter: numel of the caller's tensor, which differs from the (dense) library copy's
+    int rows = 0, cols = 0;  // conv weights (rows x cols)
+    DevBuf frag0;       // packed MFMA A fragments: static weights of conv_ws.hip / conv_wl.hip, or of cln_mfma.hip (ROLE_CLN_COND)
+    float absmax = 0.f; // ROLE_VECTOR: max |value|
 };
 
 struct GraphKey {
@@ -1064,31 +1076,32 @@ struct ace_sfno {
     }
 };
 
-static void add_weight(ace_sfno* n, const std::string& name, long numel, int block = -1, bool is_filter = false) {
+static Weight& add_weight(ace_sfno* n, const std::string& name, ParamRole role, long numel, int block = -1) {
     auto w = std::make_unique<Weight>();
-    w->name = name; w->numel = numel; w->block = block; w->is_filter = is_filter;
+    w->name = name; w->role = role; w->numel = numel; w->block = block;
     n->index[name] = (int)n->weights.size();
     n->weights.push_back(std::move(w));
+    return *n->weights.back();
 }
-// 1x1-conv weight (rows x cols): kept zero-padded to a multiple of 32 columns so the direct-to-LDS GEMM can
-// read whole k-stages
-static void add_conv_weight(ace_sfno* n, const std::string& name, int rows, int cols) {
-    add_weight(n, name, (long)rows * cols);
-    Weight& w = *n->weights.back();
-    w.rows = rows; w.cols = cols; w.pitch = (cols + 31) & ~31;
+// 1x1-conv weight (rows x cols) consumed on a grid of hw pixels: kept zero-padded to a multiple of 32 columns so the direct-to-LDS
+// GEMM can read whole k-stages
+static void add_conv_weight(ace_sfno* n, const std::string& name, ParamRole role, int rows, int cols, long hw, int block = -1) {
+    Weight& w = add_weight(n, name, role, (long)rows * cols, block);
+    w.rows = rows; w.cols = cols; w.pitch = (cols + 31) & ~31; w.hw = hw;
 }
 
-// Does role R of a K -> M 1x1 convolution at resolution HW leave the tile engines for conv_ws.hip / conv_wl.hip?  One function per
-// question, asked by ace_sfno_create (which buffers exist), ace_sfno_set_weight (which fragments are packed) and plan_route (which
-// kernel runs).  The last encoder convolution counts as an fc2 (static weights, fp32 residual, planes + statistics out).
-static bool skip_on_conv_ws(const Switches& sw, int K, int M, long HW) { return conv_ws_eligible(K, M, HW, 0, sw.conv_ws_roles); }
-static bool fc1_on_conv_ws(const Switches& sw, int K, int M, long HW) { return conv_ws_eligible(K, M, HW, 1, sw.conv_ws_roles); }
-static bool fc2_on_conv_ws(const Switches& sw, int K, int M, long HW) { return conv_ws_eligible(K, M, HW, 2, sw.conv_ws_roles); }
-static bool fc1_on_conv_wl(const Switches& sw, int K, int M, long HW) { return sw.conv_wl && conv_wl_eligible(K, M, HW); }
-// the inner skip of a noise-conditioned net (conv_ws.hip mode 6: no per-step weight fold, any K of that file): the "skip" bit of
-// ACE_CONV_WS switches it
-static bool cln_skip_on_conv_ws(const Switches& sw, int K, int M, long HW) {
-    return (sw.conv_ws_roles & 1) && conv_ws_eligible(K, M, HW, -1, sw.conv_ws_roles);
+// Does this convolution keep static fragments (frag0) for conv_ws.hip / conv_wl.hip?  Asked by ace_sfno_set_weight with the
+// weight's own consumer grid - the per-role questions of conv_roles.h that plan_route asks again per block.
+static bool keeps_static_frags(const ace_sfno* n, const Weight& w) {
+    const Switches& sw = n->sw;
+    const int nrm = n->cfg.normalization_layer;
+    switch (w.role) {
+        case ROLE_SKIP: return nrm == 2 ? cln_skip_on_conv_ws(sw.conv_ws_roles, w.cols, w.rows, w.hw) : skip_on_conv_ws(sw.conv_ws_roles, w.cols, w.rows, w.hw);
+        case ROLE_FC2: case ROLE_ENC_LAST: return fc2_on_conv_ws(sw.conv_ws_roles, w.cols, w.rows, w.hw);
+        // fc1 without an instance norm in front of it (nothing to fold per step): static fragments for conv_wl.hip
+        case ROLE_FC1: return nrm != 1 && fc1_on_conv_wl(sw.conv_wl, w.cols, w.rows, w.hw);
+        default: return false;
+    }
 }
 
 extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
@@ -1154,58 +1167,60 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
 
     // parameters in the reference's state_dict order
     const long C = n->C, HW = n->HW;
-    if (c.pos_embed) add_weight(n.get(), "pos_embed", C * HW);
+    if (c.pos_embed) add_weight(n.get(), "pos_embed", ROLE_POS_EMBED, C * HW);
     long cur = c.in_chans;
     for (int j = 0; j < c.encoder_layers; ++j) {
-        add_conv_weight(n.get(), "encoder." + std::to_string(2 * j) + ".weight", (int)C, (int)cur);
-        add_weight(n.get(), "encoder." + std::to_string(2 * j) + ".bias", C);
+        add_conv_weight(n.get(), "encoder." + std::to_string(2 * j) + ".weight", ROLE_ENC_CONV, (int)C, (int)cur, HW);
+        add_weight(n.get(), "encoder." + std::to_string(2 * j) + ".bias", ROLE_VECTOR, C);
         cur = C;
     }
-    add_conv_weight(n.get(), "encoder." + std::to_string(2 * c.encoder_layers) + ".weight", (int)C, (int)cur);
+    add_conv_weight(n.get(), "encoder." + std::to_string(2 * c.encoder_layers) + ".weight", ROLE_ENC_LAST, (int)C, (int)cur, HW);
     for (int i = 0; i < c.num_layers; ++i) {
         const std::string p = "blocks." + std::to_string(i) + ".";
-        if (c.normalization_layer == 1) { add_weight(n.get(), p + "norm0.weight", C); add_weight(n.get(), p + "norm0.bias", C); }
+        auto add_pair = [&](const std::string& q, ParamRole role, long len) { add_weight(n.get(), q + "weight", role, len); add_weight(n.get(), q + "bias", role, len); };
         // "layer_norm" (sfnonet.py:584-592): nn.LayerNorm over (H, W), its affine is a pair of (H, W) fields
         const long hw_n0 = i == 0 ? HW : n->HWs;                                  // sfnonet.py:616-623: norm0 sees the block's input grid,
         const long hw_n1 = (i == 0 || i + 1 < c.num_layers) ? n->HWs : HW;        // norm1 its output grid (a first block's: the inner one)
-        if (c.normalization_layer == 3) { add_weight(n.get(), p + "norm0.weight", hw_n0); add_weight(n.get(), p + "norm0.bias", hw_n0); }
+        const long hw_out = block_out_pixels(i, c.num_layers, HW, n->HWs);         // the skips and the MLP likewise (plan_route: BlockRoute::hw_out)
         auto add_cln = [&](const std::string& q, long ch) {   // ConditionalLayerNorm parameters in state_dict order
             if (c.noise_embed_dim > 0) {
-                add_weight(n.get(), q + "W_scale_2d.weight", ch * c.noise_embed_dim);
-                add_weight(n.get(), q + "W_bias_2d.weight", ch * c.noise_embed_dim);
+                add_weight(n.get(), q + "W_scale_2d.weight", ROLE_CLN_COND, ch * c.noise_embed_dim);
+                add_weight(n.get(), q + "W_bias_2d.weight", ROLE_CLN_COND, ch * c.noise_embed_dim);
             }
-            if (c.affine_norms) { add_weight(n.get(), q + "norm.weight", ch); add_weight(n.get(), q + "norm.bias", ch); }
+            if (c.affine_norms) add_pair(q + "norm.", ROLE_VECTOR, ch);
         };
+        if (c.normalization_layer == 1) add_pair(p + "norm0.", ROLE_VECTOR, C);
+        if (c.normalization_layer == 3) add_pair(p + "norm0.", ROLE_PLAIN, hw_n0);
         if (cln) add_cln(p + "norm0.", C);
         const long fw = c.operator_type == 1 ? C * C * n->L * 2 : C * C * (long)n->L * n->Mm * 2;
-        add_weight(n.get(), p + "filter.filter.weight", fw, i, true);
-        if (cln) n->weights.back()->ext_numel = fw / c.filter_num_groups;   // (G, L, C/G, C/G, 2)
-        add_weight(n.get(), p + "filter.filter.bias", C);
-        add_conv_weight(n.get(), p + "inner_skip.weight", (int)C, (int)C);
-        add_weight(n.get(), p + "inner_skip.bias", C);
-        if (c.normalization_layer == 1) { add_weight(n.get(), p + "norm1.weight", C); add_weight(n.get(), p + "norm1.bias", C); }
-        if (c.normalization_layer == 3) { add_weight(n.get(), p + "norm1.weight", hw_n1); add_weight(n.get(), p + "norm1.bias", hw_n1); }
+        Weight& flt = add_weight(n.get(), p + "filter.filter.weight", ROLE_FILTER, fw, i);
+        if (cln) flt.ext_numel = fw / c.filter_num_groups;   // grouped: (G, L, C/G, C/G, 2)
+        add_weight(n.get(), p + "filter.filter.bias", ROLE_VECTOR, C);
+        add_conv_weight(n.get(), p + "inner_skip.weight", ROLE_SKIP, (int)C, (int)C, hw_out, i);
+        add_weight(n.get(), p + "inner_skip.bias", ROLE_VECTOR, C);
+        if (c.normalization_layer == 1) add_pair(p + "norm1.", ROLE_VECTOR, C);
+        if (c.normalization_layer == 3) add_pair(p + "norm1.", ROLE_PLAIN, hw_n1);
         if (cln) add_cln(p + "norm1.", C);
         if (c.use_mlp) {
-            add_conv_weight(n.get(), p + "mlp.fwd.0.weight", n->hid, (int)C);
-            add_weight(n.get(), p + "mlp.fwd.0.bias", n->hid);
-            add_conv_weight(n.get(), p + "mlp.fwd.2.weight", (int)C, n->hid);
-            add_weight(n.get(), p + "mlp.fwd.2.bias", C);
+            add_conv_weight(n.get(), p + "mlp.fwd.0.weight", ROLE_FC1, n->hid, (int)C, hw_out, i);
+            add_weight(n.get(), p + "mlp.fwd.0.bias", ROLE_VECTOR, n->hid);
+            add_conv_weight(n.get(), p + "mlp.fwd.2.weight", ROLE_FC2, (int)C, n->hid, hw_out, i);
+            add_weight(n.get(), p + "mlp.fwd.2.bias", ROLE_VECTOR, C);
         }
     }
     cur = C + (c.big_skip ? c.in_chans : 0);
     for (int j = 0; j < c.encoder_layers; ++j) {
-        add_conv_weight(n.get(), "decoder." + std::to_string(2 * j) + ".weight", (int)C, (int)cur);
-        add_weight(n.get(), "decoder." + std::to_string(2 * j) + ".bias", C);
+        add_conv_weight(n.get(), "decoder." + std::to_string(2 * j) + ".weight", ROLE_DEC_CONV, (int)C, (int)cur, HW);
+        add_weight(n.get(), "decoder." + std::to_string(2 * j) + ".bias", ROLE_VECTOR, C);
         cur = C;
     }
-    add_conv_weight(n.get(), "decoder." + std::to_string(2 * c.encoder_layers) + ".weight", c.out_chans, (int)cur);
+    add_conv_weight(n.get(), "decoder." + std::to_string(2 * c.encoder_layers) + ".weight", ROLE_DEC_CONV, c.out_chans, (int)cur, HW);
     if (cln && c.normalize_big_skip && c.big_skip) {
         if (c.noise_embed_dim > 0) {
-            add_weight(n.get(), "norm_big_skip.W_scale_2d.weight", (long)c.in_chans * c.noise_embed_dim);
-            add_weight(n.get(), "norm_big_skip.W_bias_2d.weight", (long)c.in_chans * c.noise_embed_dim);
+            add_weight(n.get(), "norm_big_skip.W_scale_2d.weight", ROLE_CLN_COND, (long)c.in_chans * c.noise_embed_dim);
+            add_weight(n.get(), "norm_big_skip.W_bias_2d.weight", ROLE_CLN_COND, (long)c.in_chans * c.noise_embed_dim);
         }
-        if (c.affine_norms) { add_weight(n.get(), "norm_big_skip.norm.weight", c.in_chans); add_weight(n.get(), "norm_big_skip.norm.bias", c.in_chans); }
+        if (c.affine_norms) { add_weight(n.get(), "norm_big_skip.norm.weight", ROLE_VECTOR, c.in_chans); add_weight(n.get(), "norm_big_skip.norm.bias", ROLE_VECTOR, c.in_chans); }
     }
 
     n->wx.resize(c.num_layers);
@@ -1221,12 +1236,10 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
         n->wx_compact[i] = (!n->sw.no_pk_sht && c.precision == 1 && c.operator_type == 1 && n->C % 128 == 0 && !mixed &&
                             ((long)n->Bmax * 2 * n->C) % 4 == 0) ? 1 : 0;
         // grouped filter of the NoiseConditionedSFNO kept as the reference keeps it: the strip kernel is then the ONLY reader
-        // (every runtime precondition of that kernel is decided HERE, from the shape and max_batch: plan arithmetic = c.precision,
-        // column alignment = wx_compact, and its row-chunk grid limit for the largest batch - a handle that stores the native form
-        // can always run it)
-        const bool strip_rows_ok = ((long)n->Mm * n->Bmax + 191) / 192 <= 65535;
+        // (every runtime precondition of that kernel is decided HERE, from the shape: plan arithmetic = c.precision, column
+        // alignment = wx_compact - a handle that stores the native form can always run it)
         n->wx_native[i] = (n->wx_compact[i] && cln && c.filter_num_groups > 1 && !n->sw.dense_grouped_filter && !n->sw.no_dhconv_strip &&
-                           strip_rows_ok && dhconv_native_groups_ok(n->C, c.filter_num_groups)) ? 1 : 0;
+                           dhconv_native_groups_ok(n->C, c.filter_num_groups)) ? 1 : 0;
     }
     if (c.operator_type == 1 && c.precision == 1 && n->C % 128 == 0) {   // dhconv_strip.hip's work lists (depend on the batch size)
         n->dh_units.resize(n->Bmax);
@@ -1249,11 +1262,11 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
         if (c.normalization_layer == 1 && c.use_mlp) {
             HIP_TRY(n->P2.alloc(act, true));
             n->nstrips = (int)((HW + 31) / 32) + 8;     // >= tilesN * WN of either tile shape and conv_ws's 32-pixel tiles
-            // Asked with the DATA grid, while plan_route asks with each block's own: a known gap for scale_factor != 1, whose inner
-            // blocks may then find no buffer and stay on the tile engine
-            if (fc1_on_conv_ws(n->sw, (int)C, n->hid, HW) || fc1_on_conv_wl(n->sw, (int)C, n->hid, HW))
+            // the per-sample fold buffers: needed when ANY block of this net runs that role on conv_ws.hip / conv_wl.hip
+            auto any = [&](auto q) { return any_block(c.num_layers, HW, n->HWs, q); };
+            if (any([&](long hw) { return fc1_on_conv_ws(n->sw.conv_ws_roles, (int)C, n->hid, hw) || fc1_on_conv_wl(n->sw.conv_wl, (int)C, n->hid, hw); }))
                 HIP_TRY(n->Wq1.alloc((size_t)n->Bmax * n->hid * C, true));   // hi + lo halves = one float per element
-            if (skip_on_conv_ws(n->sw, (int)C, (int)C, HW)) HIP_TRY(n->Wq0.alloc((size_t)n->Bmax * C * C, true));
+            if (any([&](long hw) { return skip_on_conv_ws(n->sw.conv_ws_roles, (int)C, (int)C, hw); })) HIP_TRY(n->Wq0.alloc((size_t)n->Bmax * C * C, true));
             HIP_TRY(n->zero_c.alloc((size_t)C, true));
             HIP_TRY(n->inP.alloc((size_t)n->Bmax * ((c.in_chans + 7) / 8 * 8) * n->HW, true));   // two planes of halves = one float per element
             HIP_TRY(n->pe_slot.alloc(64, true));
@@ -1333,6 +1346,83 @@ extern "C" long ace_sfno_weight_numel(const ace_sfno* n, int i) {
     return n->weights[i]->ext_numel ? n->weights[i]->ext_numel : n->weights[i]->numel;
 }
 
+// ---- ace_sfno_set_weight: the library copy, then the derived operands of the parameter's role - one function per stored form
+// library copy: the caller's tensor in the reference layout; conv weights zero-padded to `pitch`, a grouped filter kept as it comes
+// (wx_native) or expanded to the dense form
+static int store_library_copy(ace_sfno* n, Weight& w, const float* src, hipStream_t s) {
+    if (w.rows > 0) {
+        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)w.rows * w.pitch, true));  // zero padding columns
+        HIP_TRY(hipMemcpy2DAsync(w.buf.p, sizeof(float) * w.pitch, src, sizeof(float) * w.cols, sizeof(float) * w.cols,
+                                 w.rows, hipMemcpyDeviceToDevice, s));
+    } else if (w.ext_numel && !n->wx_native[w.block]) {   // (G, L, C/G, C/G, 2) -> dense (Cin, Cout, L, 2), then as any dhconv weight
+        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)w.numel, false));
+        HIP_TRY(launch_csfno_weight_to_dense(src, w.buf.p, n->C, n->cfg.filter_num_groups, n->L, s));
+    } else {
+        const long numel = w.ext_numel ? w.ext_numel : w.numel;
+        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)numel, false));
+        HIP_TRY(hipMemcpyAsync(w.buf.p, src, sizeof(float) * numel, hipMemcpyDeviceToDevice, s));
+    }
+    return ACE_OK;
+}
+// dhconv filter operand.  f16x3: k-packed fp16 hi/lo planes scaled so that max|w| lands in [2^9, 2^10) - the diagonal blocks of a
+// grouped filter only (native), the compact (Wr | Wi) form, or the expanded real form; fp32: the expanded real [L][2C][2C] matrix
+static int store_filter_operand(ace_sfno* n, Weight& w, hipStream_t s) {
+    if (n->cfg.operator_type != 1) return ACE_OK;
+    const int b = w.block, C = n->C, G = n->cfg.filter_num_groups;
+    const size_t cnt = (size_t)n->L * 2 * C * 2 * C;
+    if (n->cfg.precision != 1 || (2 * C) % 32 != 0) {
+        if (!n->wx[b].p) HIP_TRY(n->wx[b].alloc(cnt, false));
+        HIP_TRY(launch_expand_dhconv_weight(w.buf.p, n->wx[b].p, C, C, n->L, s));
+        return ACE_OK;
+    }
+    const bool native = n->wx_native[b] != 0, compact = n->wx_compact[b] != 0;
+    float mx = 0.f;
+    ACE_TRY(device_absmax(w.buf.p, native ? w.ext_numel : w.numel, s, &mx));
+    const float sc = n->wx_scale[b] = pow2_scale(mx, 10);
+    const size_t halves = native ? cnt / 2 / G : (compact ? cnt / 2 : cnt);
+    if (!n->wx_hi[b].p) HIP_TRY(n->wx_hi[b].alloc((halves + 1) / 2, false));
+    if (!n->wx_lo[b].p) HIP_TRY(n->wx_lo[b].alloc((halves + 1) / 2, false));
+    if (native) HIP_TRY(launch_pack_dhconv_f16g(w.buf.p, n->wx_hi[b].p, n->wx_lo[b].p, C, G, n->L, sc, s));
+    else if (compact) HIP_TRY(launch_pack_dhconv_f16c(w.buf.p, n->wx_hi[b].p, n->wx_lo[b].p, C, C, n->L, sc, s));
+    else HIP_TRY(launch_pack_dhconv_f16(w.buf.p, n->wx_hi[b].p, n->wx_lo[b].p, C, C, n->L, sc, s));
+    return ACE_OK;
+}
+// f16x3 conv weights: planes + norms in both orders, and the static fragments of the roles conv_ws.hip / conv_wl.hip serve
+static int store_conv_operand(ace_sfno* n, Weight& w, hipStream_t s) {
+    if (n->cfg.precision != 1) return ACE_OK;
+    ACE_TRY(prepare_conv_operand(w.buf.p, w.rows, w.cols, w.pitch, PLANES_ROWS | PLANES_TILED, s, w));
+    if (keeps_static_frags(n, w)) {
+        if (!w.frag0.p) HIP_TRY(w.frag0.alloc((size_t)w.rows * w.cols, false));
+        HIP_TRY(launch_pack_conv_frag(w.buf.p, w.pitch, w.rows, w.cols, 0, nullptr, 0.f, w.ascale, nullptr, w.frag0.p, 0, 1, s));
+    }
+    return ACE_OK;
+}
+// conditioning convolutions of a conditional layer norm: MFMA A fragments for cln_mfma.hip (f16x3 networks, C % 256 == 0)
+static int store_cln_frags(ace_sfno* n, Weight& w, hipStream_t s) {
+    const int J = n->cfg.noise_embed_dim;
+    if (n->cfg.precision != 1 || J < 1 || J > 128 || w.numel != (long)n->C * J || n->C % 256 != 0 || n->C > 1024) return ACE_OK;
+    WeightNorms nm;
+    ACE_TRY(prepare_cln_frags(w.buf.p, n->C, J, s, w.frag0, &w.ascale, &nm));
+    w.wabs = nm.absmax; w.winf = nm.winf;   // winf bounds the convolution's output by winf * max |cond|
+    return ACE_OK;
+}
+// max |pos_embed| as a dynamic-range slot (the residual of the last encoder convolution)
+static int store_pos_embed_slot(ace_sfno* n, Weight& w, hipStream_t s) {
+    if (!n->pe_slot.p) return ACE_OK;
+    float mx = 0.f;
+    ACE_TRY(device_absmax(w.buf.p, w.numel, s, &mx));   // (C x H x W values: reduced where they are, not through a host copy)
+    const std::vector<float> rep(64, mx);
+    HIP_TRY(hipMemcpy(n->pe_slot.p, rep.data(), rep.size() * sizeof(float), hipMemcpyHostToDevice));
+    return ACE_OK;
+}
+// biases and norm affines: the bound used by the P-format producers
+static int store_vector_bound(Weight& w, hipStream_t s) {
+    std::vector<float> host;
+    ACE_TRY(host_copy(w.buf.p, (size_t)w.numel, s, host));
+    w.absmax = host_absmax(host);
+    return ACE_OK;
+}
+
 extern "C" int ace_sfno_set_weight(ace_sfno* n, const char* name, const float* src, long numel, void* stream) {
     if (!n || !name || !src) return fail(ACE_ERR_INVALID, "null argument");
     auto it = n->index.find(name);
@@ -1343,146 +1433,16 @@ extern "C" int ace_sfno_set_weight(ace_sfno* n, const char* name, const float* s
         return fail(ACE_ERR_INVALID, std::string("size mismatch for ") + name + ": expected " +
                                          std::to_string(expect) + " elements, got " + std::to_string(numel));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool native_groups = w.ext_numel && w.is_filter && w.block >= 0 && n->wx_native[w.block];
-    if (native_groups) {   // grouped csfno filter kept AS IT IS, (G, L, C/G, C/G, 2): fp32 copy and packed planes hold the diagonal blocks only
-        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)w.ext_numel, false));
-        HIP_TRY(hipMemcpyAsync(w.buf.p, src, sizeof(float) * w.ext_numel, hipMemcpyDeviceToDevice, s));
-        src = nullptr;
-        numel = w.ext_numel;
-    } else if (w.ext_numel) {   // ... or (shapes the strip kernel does not read that way) -> dense (Cin, Cout, L, 2), then as any dhconv weight
-        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)w.numel, false));
-        HIP_TRY(launch_csfno_weight_to_dense(src, w.buf.p, n->C, n->cfg.filter_num_groups, n->L, s));
-        src = nullptr;
-        numel = w.numel;
-    }
-    if (w.pitch > 0) {
-        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)w.rows * w.pitch, true));  // zero padding columns
-        HIP_TRY(hipMemcpy2DAsync(w.buf.p, sizeof(float) * w.pitch, src, sizeof(float) * w.cols, sizeof(float) * w.cols,
-                                 w.rows, hipMemcpyDeviceToDevice, s));
-    } else if (src) {
-        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)numel, false));
-        HIP_TRY(hipMemcpyAsync(w.buf.p, src, sizeof(float) * numel, hipMemcpyDeviceToDevice, s));
-    }
-    if (w.is_filter && n->cfg.operator_type == 1) {
-        const size_t cnt = (size_t)n->L * 2 * n->C * 2 * n->C;
-        const bool packed = n->cfg.precision == 1 && (2 * n->C) % 32 == 0;
-        if (packed) {  // f16x3: k-packed fp16 hi/lo planes scaled so that max|w| lands in [2^9, 2^10)
-            DevBuf slotbuf;
-            HIP_TRY(slotbuf.alloc(AMAX_SHARDS));
-            HIP_TRY(launch_absmax(w.buf.p, numel, reinterpret_cast<unsigned*>(slotbuf.p), s));
-            unsigned bits[AMAX_SHARDS];
-            HIP_TRY(hipMemcpyAsync(bits, slotbuf.p, sizeof(bits), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            float mx = 0.f;
-            for (unsigned b : bits) { float f; std::memcpy(&f, &b, 4); mx = std::max(mx, f); }
-            int e = 0;
-            if (mx > 0.f && std::isfinite(mx)) { (void)std::frexp(mx, &e); e = 10 - e; }
-            n->wx_scale[w.block] = std::ldexp(1.0f, e);
-            const bool compact = n->wx_compact[w.block] != 0;
-            const size_t halves = native_groups ? cnt / 2 / n->cfg.filter_num_groups : (compact ? cnt / 2 : cnt);
-            if (!n->wx_hi[w.block].p) HIP_TRY(n->wx_hi[w.block].alloc((halves + 1) / 2, false));
-            if (!n->wx_lo[w.block].p) HIP_TRY(n->wx_lo[w.block].alloc((halves + 1) / 2, false));
-            if (native_groups)
-                HIP_TRY(launch_pack_dhconv_f16g(w.buf.p, n->wx_hi[w.block].p, n->wx_lo[w.block].p, n->C, n->cfg.filter_num_groups, n->L,
-                                                n->wx_scale[w.block], s));
-            else if (compact)
-                HIP_TRY(launch_pack_dhconv_f16c(w.buf.p, n->wx_hi[w.block].p, n->wx_lo[w.block].p, n->C, n->C, n->L,
-                                                n->wx_scale[w.block], s));
-            else
-                HIP_TRY(launch_pack_dhconv_f16(w.buf.p, n->wx_hi[w.block].p, n->wx_lo[w.block].p, n->C, n->C, n->L,
-                                               n->wx_scale[w.block], s));
-        } else {
-            DevBuf& wx = n->wx[w.block];
-            if (!wx.p) HIP_TRY(wx.alloc(cnt, false));
-            HIP_TRY(launch_expand_dhconv_weight(w.buf.p, wx.p, n->C, n->C, n->L, s));
-        }
+    ACE_TRY(store_library_copy(n, w, src, s));
+    switch (w.role) {
+        case ROLE_PLAIN: break;
+        case ROLE_VECTOR: ACE_TRY(store_vector_bound(w, s)); break;
+        case ROLE_POS_EMBED: ACE_TRY(store_pos_embed_slot(n, w, s)); break;
+        case ROLE_FILTER: ACE_TRY(store_filter_operand(n, w, s)); break;
+        case ROLE_CLN_COND: ACE_TRY(store_cln_frags(n, w, s)); break;
+        default: ACE_TRY(store_conv_operand(n, w, s)); break;   // the convolutions
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (w.pitch > 0 && n->cfg.precision == 1) {
-        // power-of-two scale that puts max|w| in [2^9, 2^10): hi and lo parts stay in fp16's normal range
-        std::vector<float> host((size_t)w.rows * w.pitch);
-        HIP_TRY(hipMemcpy(host.data(), w.buf.p, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-        float mx = 0.f;
-        for (float v : host) mx = std::max(mx, std::fabs(v));
-        w.wabs = mx;
-        w.winf = 0.f;
-        for (int r = 0; r < w.rows; ++r) {
-            double rs = 0.0;
-            for (int cidx = 0; cidx < w.cols; ++cidx) rs += std::fabs((double)host[(size_t)r * w.pitch + cidx]);
-            w.winf = std::max(w.winf, (float)(rs * (1.0 + 1e-6)));
-        }
-        int e = 0;
-        if (mx > 0.f && std::isfinite(mx)) { (void)std::frexp(mx, &e); e = 10 - e; }
-        w.ascale = std::ldexp(1.0f, e);
-        const size_t halves = (size_t)w.rows * w.pitch;
-        if (!w.hi.p) HIP_TRY(w.hi.alloc((halves + 1) / 2, false));
-        if (!w.lo.p) HIP_TRY(w.lo.alloc((halves + 1) / 2, false));
-        HIP_TRY(launch_split_f16(w.buf.p, w.pitch, w.hi.p, w.lo.p, w.pitch, w.rows, w.pitch, w.ascale, s));
-        const size_t thalves = (size_t)((w.rows + 15) / 16 * 16) * w.pitch;
-        if (!w.thi.p) HIP_TRY(w.thi.alloc((thalves + 1) / 2, false));
-        if (!w.tlo.p) HIP_TRY(w.tlo.alloc((thalves + 1) / 2, false));
-        HIP_TRY(launch_split_f16_tiled(w.buf.p, w.pitch, w.thi.p, w.tlo.p, w.pitch, w.rows, w.cols, w.ascale, s));
-        const std::string& wn = w.name;
-        const bool is_enc2 = wn == "encoder." + std::to_string(2 * n->cfg.encoder_layers) + ".weight";
-        const bool is_skip = wn.size() > 17 && wn.compare(wn.size() - 17, 17, "inner_skip.weight") == 0;
-        const bool is_fc2 = wn.size() > 16 && wn.compare(wn.size() - 16, 16, "mlp.fwd.2.weight") == 0;
-        // fc1 without an instance norm in front of it (nothing to fold per step): static fragments for conv_wl.hip
-        const bool is_fc1 = wn.size() > 16 && wn.compare(wn.size() - 16, 16, "mlp.fwd.0.weight") == 0;
-        // (every question below is asked with the DATA grid, plan_route asks with the block's own: the known gap noted in ace_sfno_create)
-        if (is_fc1 && n->cfg.normalization_layer != 1 && fc1_on_conv_wl(n->sw, w.cols, w.rows, n->HW)) {
-            if (!w.frag0.p) HIP_TRY(w.frag0.alloc((size_t)w.rows * w.cols, false));
-            HIP_TRY(launch_pack_conv_frag(w.buf.p, w.pitch, w.rows, w.cols, 0, nullptr, 0.f, w.ascale, nullptr, w.frag0.p,
-                                          0, 1, s));
-        }
-        const bool cln_skip = is_skip && n->cfg.normalization_layer == 2;
-        const bool ws_ok = cln_skip ? cln_skip_on_conv_ws(n->sw, w.cols, w.rows, n->HW)
-                           : is_skip ? skip_on_conv_ws(n->sw, w.cols, w.rows, n->HW)
-                                     : fc2_on_conv_ws(n->sw, w.cols, w.rows, n->HW);
-        if ((is_skip || is_fc2 || is_enc2) && ws_ok) {
-            if (!w.frag0.p) HIP_TRY(w.frag0.alloc((size_t)w.rows * w.cols, false));
-            HIP_TRY(launch_pack_conv_frag(w.buf.p, w.pitch, w.rows, w.cols, 0, nullptr, 0.f, w.ascale, nullptr, w.frag0.p,
-                                          0, 1, s));
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    if (w.name == "pos_embed" && n->pe_slot.p) {   // its bound, as a dynamic-range slot (the residual of the last encoder convolution)
-        std::vector<float> host((size_t)numel);
-        HIP_TRY(hipMemcpy(host.data(), w.buf.p, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-        float mx = 0.f;
-        for (float v : host) mx = std::max(mx, std::fabs(v));
-        std::vector<float> rep(64, mx);
-        HIP_TRY(hipMemcpy(n->pe_slot.p, rep.data(), rep.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    {   // conditioning convolutions of a conditional layer norm: MFMA A fragments for cln_mfma.hip (f16x3 networks, C % 256 == 0)
-        const std::string& wn = w.name;
-        const bool is_cln_w = (wn.size() > 17 && wn.compare(wn.size() - 17, 17, "W_scale_2d.weight") == 0) ||
-                              (wn.size() > 16 && wn.compare(wn.size() - 16, 16, "W_bias_2d.weight") == 0);
-        const int J = n->cfg.noise_embed_dim;
-        if (is_cln_w && n->cfg.precision == 1 && J >= 1 && J <= 128 && numel == (long)n->C * J && n->C % 256 == 0 && n->C <= 1024) {
-            std::vector<float> host((size_t)numel);
-            HIP_TRY(hipMemcpy(host.data(), w.buf.p, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-            float mx = 0.f;
-            for (float v : host) mx = std::max(mx, std::fabs(v));
-            w.wabs = mx;
-            w.winf = 0.f;   // max row sum of |w|: bounds the convolution's output by winf * max |cond|
-            for (int r = 0; r < n->C; ++r) {
-                double rs = 0.0;
-                for (int j = 0; j < J; ++j) rs += std::fabs((double)host[(size_t)r * J + j]);
-                w.winf = std::max(w.winf, (float)(rs * (1.0 + 1e-6)));
-            }
-            w.ascale = cln_frag_scale(mx);
-            std::vector<uint16_t> frags(cln_frag_halves(n->C, J));
-            pack_cln_frags(host.data(), n->C, J, w.ascale, frags.data());
-            if (!w.frag0.p) HIP_TRY(w.frag0.alloc((frags.size() + 1) / 2, false));
-            HIP_TRY(hipMemcpy(w.frag0.p, frags.data(), frags.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
-    }
-    if (w.pitch == 0 && !w.is_filter && numel <= (1 << 16)) {  // biases: bound used by the P-format producers
-        std::vector<float> host((size_t)numel);
-        HIP_TRY(hipMemcpy(host.data(), w.buf.p, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-        w.absmax = 0.f;
-        for (float v : host) w.absmax = std::max(w.absmax, std::fabs(v));
-    }
     w.set = true;
     // Captured graphs keep pointing at the same library buffers, but the host-side scalars derived from the weights
     // (ascale, winf, wabs, bias bounds, filter scale) are baked into their kernel arguments by value: drop the graphs so
@@ -1600,7 +1560,7 @@ static FwdRoute plan_route(const ace_sfno* n, int B, bool has_noise) {
         b.hw_in = (long)b.fwd->nlat * b.fwd->nlon;
         // everything behind the filter works on ITS output grid (the skips, norm1 and the MLP see what the inverse transform
         // produced) - the inner grid after the first block of a scale_factor != 1 net, the data grid after the last
-        const long hw = b.hw_out = (long)b.inv->nlat * b.inv->nlon;
+        const long hw = b.hw_out = block_out_pixels(i, nl, n->HW, n->HWs);
 
         // spectral filter (s2convolutions.py:162-197)
         b.dplanes = f16 && !sw.no_pk_sht && c.operator_type == 1 && n->wx_hi[i].p && !b.scale_residual && b.fwd->f16 &&
@@ -1637,18 +1597,18 @@ static FwdRoute plan_route(const ace_sfno* n, int B, bool has_noise) {
             // Instance norms fused away: every conv input is P-format planes written by its producer's epilogue, the norm affine is
             // folded into the consumer's weights.  Which of the three convolutions run on the weight-stationary kernels:
             const Weight& w1 = wt(p + "mlp.fwd.0.weight");
-            if (gelu && n->Wq0.p && wt(p + "inner_skip.weight").frag0.p && skip_on_conv_ws(sw, C, C, hw)) b.skip = CONV_WS;
-            if (gelu && n->Wq1.p && fc1_on_conv_wl(sw, C, hid, hw)) b.fc1 = CONV_WL;
-            else if (gelu && n->Wq1.p && fc1_on_conv_ws(sw, C, hid, hw)) b.fc1 = CONV_WS;
+            if (gelu && n->Wq0.p && wt(p + "inner_skip.weight").frag0.p && skip_on_conv_ws(sw.conv_ws_roles, C, C, hw)) b.skip = CONV_WS;
+            if (gelu && n->Wq1.p && fc1_on_conv_wl(sw.conv_wl, C, hid, hw)) b.fc1 = CONV_WL;
+            else if (gelu && n->Wq1.p && fc1_on_conv_ws(sw.conv_ws_roles, C, hid, hw)) b.fc1 = CONV_WS;
             b.pfold = sw.fused_pack && b.fc1 == CONV_WL && C == 384 && w1.pitch % 4 == 0;
             // (C <= 1024: the fp32 output of conv_ws.hip)
-            if (wt(p + "mlp.fwd.2.weight").frag0.p && C <= 1024 && fc2_on_conv_ws(sw, hid, C, hw)) b.fc2 = CONV_WS;
+            if (wt(p + "mlp.fwd.2.weight").frag0.p && C <= 1024 && fc2_on_conv_ws(sw.conv_ws_roles, hid, C, hw)) b.fc2 = CONV_WS;
             b.t_nparts = b.skip == CONV_WS ? ws_stat_parts(C, C, hw) : gemm4_strips(C, (int)hw);
         } else if (pk) {
             // conv_ws.hip mode 6: GELU(W . planes + bias + Y) -> fp32 T (the conditional norm that follows reads fp32)
-            if (cln && gelu && wt(p + "inner_skip.weight").frag0.p && cln_skip_on_conv_ws(sw, C, C, hw)) b.skip = CONV_WS;
+            if (cln && gelu && wt(p + "inner_skip.weight").frag0.p && cln_skip_on_conv_ws(sw.conv_ws_roles, C, C, hw)) b.skip = CONV_WS;
             // conv_wl.hip: the noise-conditioned nets' fc1 (no norm affine to fold, static fragments)
-            if (c.use_mlp && !norm && gelu && wt(p + "mlp.fwd.0.weight").frag0.p && fc1_on_conv_wl(sw, C, hid, hw)) b.fc1 = CONV_WL;
+            if (c.use_mlp && !norm && gelu && wt(p + "mlp.fwd.0.weight").frag0.p && fc1_on_conv_wl(sw.conv_wl, C, hid, hw)) b.fc1 = CONV_WL;
             b.n0_to_planes = cln;
             b.n1_to_planes = cln && c.use_mlp && !n->taps_on;   // followed by the packed MLP, norm1's output exists as planes only
         } else {
@@ -1660,7 +1620,7 @@ static FwdRoute plan_route(const ace_sfno* n, int B, bool has_noise) {
     // starts like every other block (no pack pass, no statistics pass over h0).
     const Weight& we = wt("encoder." + std::to_string(2 * c.encoder_layers) + ".weight");
     r.enc_planes = !sw.no_enc_ws && r.blk[0].body == BODY_FUSED && c.encoder_layers >= 1 && c.pos_embed && we.frag0.p && n->zero_c.p &&
-                   n->pe_slot.p && n->part.p && fc2_on_conv_ws(sw, C, C, n->HW);
+                   n->pe_slot.p && n->part.p && fc2_on_conv_ws(sw.conv_ws_roles, C, C, n->HW);
     if (r.enc_planes) r.enc_nparts = ws_stat_parts(C, C, n->HW);
     // Then a ONE-hidden-layer encoder (the ACE2 shape) never materialises its hidden activation as fp32: the network input is packed
     // to P-format planes (in_chans rounded up to a k-group, 11 MB) and the first convolution runs on the packed-operand engine, whose

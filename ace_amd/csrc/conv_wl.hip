@@ -321,13 +321,6 @@ extern "C" int ace_debug_trace(void* dst) { return (int)hipMemcpyFromSymbol(dst,
 extern "C" int ace_debug_wg_spans(void* dst) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(wl_wg_span), sizeof(wl_wg_span)); }
 #endif
 
-// K: input channels, M: output channels.  GELU + P-format output, no residual, no statistics (the first MLP convolution)
-bool conv_wl_eligible(int K, int M, long HW) {
-    if (K == 384) return M % 96 == 0 && M / 96 <= 32 && (long)M * HW * 2 < 0x7fffff00L;
-    if (K == 512 || K == 256 || K == 128) return M % 64 == 0 && M / 64 <= 32 && (long)M * HW * 2 < 0x7fffff00L;   // two row tiles per workgroup (K = 512: 128 KiB of weights)
-    return false;
-}
-
 hipError_t launch_conv_wl(const ConvStripArgs& a, hipStream_t s) {
     if (!conv_wl_eligible(a.C, a.M, a.HW) || !a.bias || !a.xslot || !(a.A || a.Wraw) || !a.Chi || !a.Clo || !a.cslot || a.R || a.part || a.Cf ||
         !(a.act == ACT_GELU || a.act == ACT_GELU_FAST))

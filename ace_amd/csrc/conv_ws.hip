@@ -676,15 +676,6 @@ int conv_ws_stat_parts(const ConvStripArgs& a) {
     return ws_stat_slots(pl);
 }
 
-// K: input channels (contraction), M: output channels; role 0 inner skip, 1 fc1, 2 fc2 (-1: any)
-bool conv_ws_eligible(int K, int M, long HW, int role, int roles_on) {
-    if (role >= 0 && role < 3 && !(roles_on >> role & 1)) return false;
-    if (role == -1 && roles_on == 0) return false;
-    if (!(K == 128 || K == 256 || K == 384 || K == 512 || K == 768)) return false;
-    if (role >= 0 && role <= 1 && K > 384) return false;
-    return M % 128 == 0 && M >= 128 && M <= 2048 && (long)M * HW * 4 < 0x7fffff00L && ((HW + 31) / 32 + 8) * (long)M * 16 < 0x7fffff00L;
-}
-
 hipError_t launch_conv_ws(const ConvStripArgs& a, hipStream_t s) {
     if (!conv_ws_eligible(a.C, a.M, a.HW, -2) || !a.bias || !a.xslot || !a.A) return hipErrorInvalidValue;
     const bool f32 = a.Cf != nullptr, pk = a.Chi != nullptr, stats = a.part != nullptr, res = a.R != nullptr;

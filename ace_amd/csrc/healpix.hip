@@ -29,6 +29,7 @@
 #include "../../include/ace_sfno.h"
 #include "kernels.h"
 #include "strip_common.h"
+#include "weight_prep.h"
 
 using namespace ace;
 
@@ -482,21 +483,13 @@ extern "C" int ace_hpx_weight_create(const float* w_dev, int rows, int cols, voi
     std::vector<float> host((size_t)rows * cols);
     HPX_TRY(hipStreamSynchronize(s));
     HPX_TRY(hipMemcpy(host.data(), w_dev, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-    float mx = 0.f;
-    for (float v : host) {
+    for (float v : host)
         if (!std::isfinite(v)) return hfail(ACE_ERR_INVALID, "ace_hpx_weight_create: non-finite weight");
-        mx = std::max(mx, std::fabs(v));
-    }
-    int e = 0;
-    if (mx > 0.f) { (void)std::frexp(mx, &e); e = 10 - e; }
+    const WeightNorms nm = weight_norms(host.data(), rows, cols, cols);
     ace_hpx_weight* w = new ace_hpx_weight;
     w->rows = rows; w->cols = cols; w->pitch = (cols + 31) & ~31;
-    w->ascale = std::ldexp(1.0f, e);
-    for (int r = 0; r < rows; ++r) {
-        double rs = 0.0;
-        for (int c = 0; c < cols; ++c) rs += std::fabs((double)host[(size_t)r * cols + c]);
-        w->winf = std::max(w->winf, (float)(rs * (1.0 + 1e-6)));
-    }
+    w->ascale = pow2_scale(nm.absmax, 10);
+    w->winf = nm.winf;
     const size_t halves = (size_t)((rows + 15) / 16 * 16) * w->pitch;
     if (hipMalloc(reinterpret_cast<void**>(&w->hi), halves * 2) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&w->lo), halves * 2) != hipSuccess) {
         ace_hpx_weight_destroy(w);

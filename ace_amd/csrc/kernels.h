@@ -1,6 +1,7 @@
 // Launch interface of the gfx950 kernels (kernels.hip).  Internal to the library;
 // the public boundary is include/ace_sfno.h.
 #pragma once
+#include "conv_roles.h"
 #include "tuning_guard.h"
 
 #include <hip/hip_runtime.h>
@@ -236,13 +237,11 @@ struct ConvStripArgs {
     unsigned* omax = nullptr;
 };
 // weights resident in registers, persistent grid over pixel tiles; K in {128, 256, 384, 512, 768}, M % 128 == 0;
-// statistics per 32-pixel tile (fc2) or per pixel group (inner skip): nstrips32 >= conv_ws_stat_parts()
-bool conv_ws_eligible(int K, int M, long HW, int role, int roles_on = 7);   // role 0 inner skip, 1 fc1, 2 fc2 (-1: any); roles_on: Switches::conv_ws_roles
+// statistics per 32-pixel tile (fc2) or per pixel group (inner skip): nstrips32 >= conv_ws_stat_parts().  conv_ws_eligible(): conv_roles.h
 hipError_t launch_conv_ws(const ConvStripArgs& a, hipStream_t s);
 int conv_ws_stat_parts(const ConvStripArgs& a);
 // the first MLP convolution (GELU, planes in / planes out, no residual, no statistics) with the weights in LDS and unsynchronised
-// waves (conv_wl.hip); K in {128, 256, 384}
-bool conv_wl_eligible(int K, int M, long HW);
+// waves (conv_wl.hip); K in {128, 256, 384}.  conv_wl_eligible(): conv_roles.h
 hipError_t launch_conv_wl(const ConvStripArgs& a, hipStream_t s);   // statistics partials per row that launch writes (nstrips32 >= this)
 
 // dhconv with the filter streamed once into MFMA B fragments (dhconv_strip.hip).  Rows (m, b), m <= l; K = N = 2 C.

@@ -17,6 +17,8 @@
 #include <cstring>
 #include <vector>
 
+#include "weight_prep.h"
+
 namespace ace {
 
 struct StripGeom {   // per-m geometry shared by the packer, the kernel and the emulator
@@ -336,11 +338,7 @@ inline PolarCut derive_polar_cut(const StripPack& fwd, const StripPack& inv, int
 // ---- conditional layer norm on MFMA (cln_mfma.hip): a (C x J) 1x1-convolution weight as error-compensated A fragments of
 // v_mfma_f32_32x32x16_f16, [C / 32 row tiles][ceil(J / 16) k-steps][hi 512 | lo 512] halves; lane (i, g) element e of a block is
 // W[32 rt + i][16 ks + 8 g + e] * scale (zero beyond J).  `scale` = cln_frag_scale(max |W|): max |W| scale in [2^9, 2^10).
-inline float cln_frag_scale(float wabs) {
-    int e = 0;
-    if (wabs > 0.f && std::isfinite(wabs)) { (void)std::frexp(wabs, &e); e = 10 - e; }
-    return std::ldexp(1.0f, e);
-}
+inline float cln_frag_scale(float wabs) { return pow2_scale(wabs, 10); }
 inline size_t cln_frag_halves(int C, int J) { return (size_t)(C / 32) * (size_t)((J + 15) / 16) * 1024; }
 inline void pack_cln_frags(const float* W, int C, int J, float scale, uint16_t* out) {
     const int nk = (J + 15) / 16;

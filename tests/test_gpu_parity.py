@@ -937,6 +937,97 @@ def test_graph_replay_matches_eager(dev, precision):
             assert torch.equal(out, ref2)
 
 
+def _rescaled_state(state):
+    """every tensor times a factor that is no power of two, one per kind of parameter: every stored scale, bound and fragment changes"""
+    out = {}
+    for k, v in state.items():
+        f = 0.11 if k.endswith("filter.filter.weight") else 5.0 if (v.ndim <= 1 or k.endswith("pos_embed")) else 3.7
+        out[k] = v * f
+    return out
+
+
+REUPLOAD_NETS = {   # the smallest nets at which each stored operand form of ace_sfno_set_weight exists
+    # fused body, static fragments of skip / fc2 / last encoder convolution, pos_embed slot, compact filter planes
+    "dhconv_f16x3": (dict(img_shape=(24, 48), embed_dim=128, num_layers=3, operator_type="dhconv"), "f16x3"),
+    # library copies only + the expanded fp32 filter
+    "dhconv_fp32": (dict(img_shape=(24, 48), embed_dim=128, num_layers=3, operator_type="dhconv"), "fp32"),
+    # mixed-grid first and last blocks (expanded f16 operand there), inner blocks on the inner grid
+    "scale_factor_2": (dict(img_shape=(48, 96), embed_dim=128, num_layers=4, operator_type="dhconv", scale_factor=2), "f16x3"),
+    "diagonal": (dict(img_shape=(24, 48), embed_dim=32, num_layers=3, operator_type="diagonal"), "f16x3"),
+    # conditional-norm fragments, the inner skip's and fc1's static fragments; 2 groups: the native grouped filter
+    "csfno_groups_1": (1, "f16x3"),
+    "csfno_groups_2": (2, "f16x3"),
+}
+
+
+@pytest.mark.parametrize("name", list(REUPLOAD_NETS))
+def test_second_upload_into_a_live_handle_equals_a_fresh_handle(dev, name):
+    """ace_sfno_set_weight into a handle that already holds values and captured graphs: every derived buffer is reused in place and
+    the graphs are marked stale.  A handle loaded with A, run, then loaded with B must give - eager and replayed - bit for bit what a
+    fresh handle loaded with B gives, and every upload must advance ace_sfno_weights_generation.  (The conditioned forward has no
+    graph entry: the cSFNO cases run eager only.)"""
+    import ace_amd
+    from ace_amd import _lib
+    from oracle.sfno import SFNOConfig, init_state
+    spec, precision = REUPLOAD_NETS[name]
+    g = torch.Generator().manual_seed(31)
+    csfno = isinstance(spec, int)
+    if csfno:   # the net of test_conditional_norm_routing_switches_against_the_oracle
+        kwargs = dict(embed_dim=256, noise_embed_dim=8, noise_type="gaussian", num_layers=2, use_mlp=True, mlp_ratio=2.0, affine_norms=True,
+                      normalize_big_skip=True, filter_num_groups=spec)
+        hw = (16, 32)
+
+        def make(state=None):
+            net = ace_amd.ModuleSelector(type="NoiseConditionedSFNO", config=dict(kwargs)).build(5, 4, ace_amd.DatasetInfo(hw)).torch_module
+            if state is not None:
+                net.load_state_dict(state, strict=True)
+            return net.to(dev).set_precision(precision)
+        torch.manual_seed(11)
+        state_a = {k: v.detach().clone() for k, v in make().state_dict().items()}
+        noise = torch.randn(2, 8, *hw, generator=g).to(dev)
+    else:
+        cfg = SFNOConfig(in_chans=5, out_chans=4, **spec)
+        hw = cfg.img_shape
+        state_a = init_state(cfg, seed=41)
+        noise = None
+
+        def make(state):
+            return build_native_net(cfg, state, dev, precision)
+    for k, v in state_a.items():   # biases and norm affines away from their 0 / 1 initialisation
+        if v.ndim <= 1:
+            state_a[k] = v.cpu() + 0.1 * torch.randn(v.shape, generator=g)
+    state_b = _rescaled_state(state_a)
+    x = torch.randn(2, 5, *hw, generator=g).to(dev)
+
+    def run(net):
+        with torch.no_grad():
+            if csfno:
+                return net(x, noise=noise).clone(), None
+            y = net(x).clone()
+            out = torch.empty_like(y)
+            net.forward_graph(x, out)
+            torch.cuda.synchronize()
+            return y, out
+
+    def generation(net):
+        return int(_lib.lib().ace_sfno_weights_generation(net._native))
+
+    live = make(state_a)
+    ya, ga = run(live)
+    nparams = int(_lib.lib().ace_sfno_num_weights(live._native))
+    assert generation(live) == nparams
+    live.load_state_dict({k: v.to(dev) for k, v in state_b.items()}, strict=True)
+    yb, gb = run(live)
+    assert generation(live) == 2 * nparams          # every parameter went up again, each upload counted
+    fresh = make(state_b)
+    yf, gf = run(fresh)
+    assert generation(fresh) == nparams
+    assert torch.isfinite(yb).all() and not torch.equal(ya, yb)
+    assert torch.equal(yb, yf)
+    if not csfno:
+        assert torch.equal(ga, ya) and torch.equal(gb, yb) and torch.equal(gf, yf)
+
+
 @pytest.mark.parametrize("scale", [1e-4, 1.0, 3e3])
 def test_f16x3_dynamic_range(dev, scale):
     """the compensated engine derives its power-of-two operand scales from the data: inputs and weights far from

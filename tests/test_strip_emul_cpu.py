@@ -86,3 +86,15 @@ def test_fft_unit_mappings_and_offset_bound(tmp_path):
     res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout + res.stderr
     assert "combinations ok" in res.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_weight_preparation_arithmetic_and_storage_question(tmp_path):
+    """ace_amd/csrc/weight_prep.h and conv_roles.h (host arithmetic of weight upload): pow2_scale against the rule written out at zero,
+    denormal, power-of-two neighbours, FLT_MAX, inf and NaN; weight_norms exact in max |w| and within (1 + 2e-6) above the long-double
+    row sums, padding columns never read; the conv_ws / conv_wl storage question on the data grid against a block's own grid."""
+    exe = str(tmp_path / "weight_prep_emul")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "emul", "weight_prep_emul.cpp")], check=True)
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "weight prep ok" in res.stdout
