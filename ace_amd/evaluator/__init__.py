@@ -16,13 +16,16 @@ labels (config.py holds the configurations and the build rules; each family's do
     that gets none is dropped with a warning and listed in ``skipped`` (``uses_time``), a strict one raises (``needs_time``);
   * stepped.py, ``_StepMeans``: ``step_means`` (one_step/reduced.py:24-249) from ``StepMeanMetricConfig`` entries, and
     ``_Ensembles``: ``ensembles`` (one_step/ensemble.py:74-505) from ``EnsembleMetricConfig`` entries, recorded only when
-    ``build(..., n_ensemble_per_ic=E)`` has ``E > 1``.
+    ``build(..., n_ensemble_per_ic=E)`` has ``E > 1``;
+  * video.py, ``_Video``: ``video`` (video.py:33-541), off by default and from a ``VideoMetricConfig`` only, with its own
+    ``variables`` filter (its accumulators hold every time index of every kept name; ``build(..., video_max_bytes=)`` bounds them);
+    fused: one ``ace_diag_video_window`` per window.  ``video_frames`` states the reference's ``_make_video`` up to its logger call.
 
 Not built (``config._FIELDS`` and ``build`` state the rules): skipped at build time with one warning and listed in ``skipped``, as the
 reference's non-strict path does (main.py:143-153; ``strict=True`` raises), are the bare ``MetricConfig`` defaults of ``step_means``,
 ``ensembles``, ``annual``, ``enso_index`` and ``ipo_index``, an entry whose ``step`` exceeds ``n_forward_steps``, a calendar metric or
 ENSO coefficient whose record is too short, an ``enso_coefficient`` without an index, a ``trend`` over fewer than two forward steps.
-``video``, a bare enabled ``seasonal``, ``histogram``, ``trend`` or ``near_zero_fraction``, the reference-data paths, a ``variables``
+A bare enabled ``video``, ``seasonal``, ``histogram``, ``trend`` or ``near_zero_fraction``, the reference-data paths, a ``variables``
 filter on a paired metric and HEALPix grids raise ``NotImplementedError``.  As in ace_amd/aggregator.py, tensors and floats stand
 where the reference logs images and figures, and a name whose mask has zeros is left out of the spectrum and listed in ``omitted`` - unless ``power_spectrum.fill_masked`` is on
 (the reference's behaviour; off by default): then its masked pixels are flood-filled before the SHT (ace_amd/fill.py, fused:
@@ -44,14 +47,18 @@ The one deliberate difference from the reference: the zonal mean adds each step 
 scaled by 1 / factor, which equals the reference's buffer-carry form (zonal_mean.py:192-266) whenever every window has at least
 ``factor`` steps; a shorter window raises ``ValueError`` where the reference silently drops it (zonal_mean.py:181-190).  Zonal
 accumulator memory: names x 2 x slots x H x 8 bytes (40 names, 4096 slots, 180 latitudes: 472 MB; the default
-``zonal_mean_max_size`` only coarsens past 4096 steps)."""
+``zonal_mean_max_size`` only coarsens past 4096 steps).
+
+One numerical difference, as for the time means and the coupler: the fused video sums over the samples in fp64 and rounds once,
+where the reference (and the torch path) takes fp32 means; with u = 2^-24 the two differ by at most B u max|x| per visit."""
 from .aggregator import InferenceEvaluatorAggregator  # noqa: F401
 from .calendar import (SEASONS, _Calendar, anomalies_from_monthly_climo, fair_crps, latlon_region_weights, low_pass_filter,  # noqa: F401
                        nan_aware_regional_mean, psd_band_power, running_monthly_mean, sample_average_power_spectrum, sample_mean_std)
 from .config import (AnnualMetricConfig, EnsembleMetricConfig, EnsoCoefficientMetricConfig, EnsoIndexMetricConfig,  # noqa: F401
                      HistogramMetricConfig, InferenceEvaluatorAggregatorConfig, InferenceSummary, IpoIndexMetricConfig, MetricConfig,
                      NearZeroFractionMetricConfig, PowerSpectrumMetricConfig, SeasonalMetricConfig, StepMeanMetricConfig,
-                     TrendMetricConfig, ZonalMeanMetricConfig)
+                     TrendMetricConfig, VideoMetricConfig, ZonalMeanMetricConfig)
 from .histogram import HIST_BINS, HIST_PERCENTILES, histogram_quantile, trim_zero_bins  # noqa: F401
 from .paired import NORM_SERIES, SERIES, spectrum_bias_scores, zonal_coarsening  # noqa: F401
 from .stepped import ENSEMBLE_METRICS, ssr_bias  # noqa: F401
+from .video import video_frames  # noqa: F401

@@ -9,11 +9,12 @@ from ..aggregator import InferenceAggregator, TensorMapping, _flat
 from .calendar import _Calendar
 from .common import Window
 from .config import (EnsembleMetricConfig, EnsoCoefficientMetricConfig, HistogramMetricConfig, InferenceSummary, MetricConfig,
-                     NearZeroFractionMetricConfig, StepMeanMetricConfig, TrendMetricConfig)
+                     NearZeroFractionMetricConfig, StepMeanMetricConfig, TrendMetricConfig, VideoMetricConfig)
 from .histogram import _Histograms
 from .paired import LABELS, _Paired, _Spectrum, zonal_coarsening
 from .regress import _Regress
 from .stepped import _Ensembles, _StepMeans
+from .video import _Video
 
 
 class InferenceEvaluatorAggregator(InferenceAggregator):
@@ -26,7 +27,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
                  trend: Optional[TrendMetricConfig] = None, enso_coefficient: Optional[EnsoCoefficientMetricConfig] = None,
                  near_zero_fraction: Optional[NearZeroFractionMetricConfig] = None,
                  calendar: Optional[Mapping[str, MetricConfig]] = None, step_means: Sequence[StepMeanMetricConfig] = (),
-                 ensembles: Sequence[EnsembleMetricConfig] = (), n_ensemble_per_ic: int = 1, fill_masked: bool = False):
+                 ensembles: Sequence[EnsembleMetricConfig] = (), n_ensemble_per_ic: int = 1, fill_masked: bool = False,
+                 video: Optional[VideoMetricConfig] = None, video_max_bytes: int = 32 << 30):
         super().__init__(dataset_info, n_ic_steps + n_forward_steps, True, output_dir, save_diagnostics, sht_factory,
                          spectrum_chunk_bytes, fill_masked_spectrum=fill_masked)
         self.n_ensemble_per_ic = int(n_ensemble_per_ic)
@@ -45,6 +47,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         # the metric families, in the order a window goes through them; a step mean is a column of the paired pass's series
         self._paired = _Paired(self, self._labels, {c.target for c in step_means})
         self._families: List[Any] = [self._paired]
+        if video is not None and video.enabled:
+            self._families.append(_Video(self, video, video_max_bytes))
         if histogram is not None and histogram.enabled:
             self._families.append(_Histograms(histogram))
         on = [None if m is None or not m.enabled else m for m in (trend, enso_coefficient, near_zero_fraction)]
@@ -66,6 +70,7 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
 
     _regress = property(lambda self: self._family(_Regress))             # what the tests and the benchmarks reach for
     _calendar = property(lambda self: self._family(_Calendar))
+    _video = property(lambda self: self._family(_Video))
     _ensembles = property(lambda self: self._family(_Ensembles))
 
     # ---- routing ------------------------------------------------------------------------------------------------------
@@ -76,8 +81,9 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         return super().route({**{f"p:{k}": v for k, v in prediction.items()}, **{f"t:{k}": v for k, v in (target or {}).items()}})
 
     def launches(self) -> int:
-        """Native launches made so far: one ``ace_diag_paired_window`` per window, one ``ace_diag_hist_window`` per window of
-        ``record_batch`` when the histogram is on, one ``ace_diag_regress_window`` per window of ``record_batch`` when any of
+        """Native launches made so far: one ``ace_diag_paired_window`` per window, one ``ace_diag_video_window`` per window of
+        ``record_batch`` when the video is on, one ``ace_diag_hist_window`` per window of ``record_batch`` when the histogram is
+        on, one ``ace_diag_regress_window`` per window of ``record_batch`` when any of
         trend, enso_coefficient and near_zero_fraction is on (a second one for the ENSO term of a window at time index 0), and
         one ``ace_diag_ensemble_step`` per ensemble entry and window that holds its step, and per spectrum chunk of either side
         one forward SHT and one ``ace_diag_spectrum`` - three with ``power_spectrum.fill_masked``: one ``ace_diag_fill_planes``

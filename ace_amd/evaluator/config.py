@@ -48,6 +48,17 @@ class HistogramMetricConfig(MetricConfig):
 
 
 @dataclasses.dataclass
+class VideoMetricConfig(MetricConfig):
+    """video.py:522-541.  ``variables``: videos of these names only (the accumulators hold every time index of every kept name:
+    ace_amd/evaluator/video.py states the memory); ``enable_extended_videos``: also the bias, RMSE, error extrema and variance
+    ratio videos."""
+    enabled: bool = False
+    strict: bool = True
+    name: Optional[str] = "video"
+    enable_extended_videos: bool = False
+
+
+@dataclasses.dataclass
 class TrendMetricConfig(MetricConfig):
     """trend.py:279-314.  ``variables``: compute trends for these names only."""
     enabled: bool = False
@@ -176,7 +187,7 @@ _FIELDS = (
     ("zonal_mean", MetricConfig, "built", "paired"),
     ("step_means", StepMeanMetricConfig, "skipped", "stepped"),           # lists: an entry of the typed class is built
     ("ensembles", EnsembleMetricConfig, "skipped", "stepped"),
-    ("video", (), "raises", None),
+    ("video", VideoMetricConfig, "raises", "video"),
     ("seasonal", SeasonalMetricConfig, "raises", "calendar"),
     ("histogram", HistogramMetricConfig, "raises", "histogram"),
     ("annual", AnnualMetricConfig, "skipped", "calendar"),
@@ -238,12 +249,13 @@ class InferenceEvaluatorAggregatorConfig:
     def build(self, dataset_info, n_ic_steps: int, n_forward_steps: int, normalize, output_dir: Optional[str] = None,
               channel_mean_names: Optional[Sequence[str]] = None, save_diagnostics: bool = False,
               sht_factory: Optional[Callable[[int, int], Callable]] = None,
-              n_ensemble_per_ic: int = 1) -> "InferenceEvaluatorAggregator":
+              n_ensemble_per_ic: int = 1, video_max_bytes: int = 32 << 30) -> "InferenceEvaluatorAggregator":
         """``normalize``: a ``StandardNormalizer``, its bound ``normalize``, or anything exposing per-name ``means`` and ``stds``
         (the fused path reads the statistics, the torch path calls it); a bare callable serves the torch path only.
         ``n_ensemble_per_ic``: the samples of a window are ``n_ic x n_ensemble_per_ic`` members, sample ``b = i * n_ensemble_per_ic +
         e`` (``inference.repeat_members``); with 1 the ensemble entries are accepted but neither recorded nor reported
-        (main.py:560-562, 604-621)."""
+        (main.py:560-562, 604-621).  ``video_max_bytes``: the most the video metric's accumulators may take (names x n_timesteps
+        x H x W x 16 bytes, x 48 with extended videos); a window that would pass it raises ``ValueError``."""
         if int(n_ensemble_per_ic) < 1:
             raise ValueError(f"n_ensemble_per_ic must be >= 1, got {n_ensemble_per_ic}")
         if self.monthly_reference_data is not None or self.time_mean_reference_data is not None:
@@ -254,9 +266,9 @@ class InferenceEvaluatorAggregatorConfig:
                                       "aggregator is built)")
         for field, typed, bare, _ in _FIELDS:
             if bare == "raises" and getattr(self, field).enabled and not isinstance(getattr(self, field), typed):
-                if field == "histogram":
-                    raise NotImplementedError("the histogram metric is built from its typed configuration only: pass a "
-                                              "HistogramMetricConfig, not a bare MetricConfig")
+                if field in ("histogram", "video"):
+                    raise NotImplementedError(f"the {field} metric is built from its typed configuration only: pass a "
+                                              f"{typed.__name__}, not a bare MetricConfig")
                 raise NotImplementedError(f"the {field} metric is not built")
         skipped = []
         regress = {"trend": self.trend, "enso_coefficient": self.enso_coefficient, "near_zero_fraction": self.near_zero_fraction}
@@ -330,7 +342,8 @@ class InferenceEvaluatorAggregatorConfig:
             if m.enabled:
                 labels[field.replace("_denorm", "")] = m.name or field.replace("_denorm", "")
         taken = list(labels.values())                                     # every label that heads a block of the logs and the dataset
-        taken += [m.name or field for field, m in (("histogram", self.histogram), *regress.items()) if m is not None and m.enabled]
+        taken += [m.name or field for field, m in (("video", self.video), ("histogram", self.histogram), *regress.items())
+                  if m is not None and m.enabled]
         taken += [m.name or field for field, m in calendar.items()]
         for m in stepped["step_means"] + stepped["ensembles"]:
             if m.name in taken:
@@ -347,5 +360,6 @@ class InferenceEvaluatorAggregatorConfig:
             zonal_mean_max_size=getattr(self.zonal_mean, "zonal_mean_max_size", 4096), channel_mean_names=channel_mean_names,
             report_directional_bias=getattr(self.power_spectrum, "report_directional_bias", True), output_dir=output_dir,
             save_diagnostics=save_diagnostics, sht_factory=sht_factory,
-            histogram=self.histogram if self.histogram.enabled else None, calendar=calendar, **regress, **stepped,
+            histogram=self.histogram if self.histogram.enabled else None, video=self.video if self.video.enabled else None,
+            video_max_bytes=int(video_max_bytes), calendar=calendar, **regress, **stepped,
             n_ensemble_per_ic=int(n_ensemble_per_ic), fill_masked=bool(getattr(self.power_spectrum, "fill_masked", False)))

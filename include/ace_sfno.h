@@ -632,6 +632,39 @@ int ace_couple_atmosphere_to_ocean(const float* const* srcs, const long* src_str
  *                  pixels in registers and stores each segment's result as the segment closes: no scratch, each output slot
  *                  written by one thread, no atomics, bitwise repeatable.  One launch however many planes; no allocation, no
  *                  host synchronisation.
+ *   diag_video_window: the evaluator's video metric (fme/ace/aggregator/inference/video.py:33-255), ace_amd/evaluator/video.py:
+ *                  per time slot of the whole inference and per pixel, the means over the samples of both sides and, for the
+ *                  extended videos, of their squares and of the squared error, with the smallest and largest error - for all
+ *                  names and both sides of a window from one read of every plane, the accumulators staying on the device.
+ *                  gen / target / strides / rows: as diag_regress_window, planes of hw contiguous fp32 starting at any 4-byte
+ *                  boundary; target[j] may be NULL.  A plane whose rows[j] is out of range [0, nrows) contributes to nothing.
+ *                  rows must not name one row twice (two workgroups would update the same slots); this is not checked.
+ *                  mean: DEVICE fp64 [2][nrows][n_time][hw], the generated side then the target side.  sq: DEVICE fp64
+ *                  [3][nrows][n_time][hw], channel 0 gen^2, 1 target^2, 2 d^2.  err: DEVICE fp32 [2][nrows][n_time][hw], min
+ *                  then max.  sq and err are both NULL (the basic videos) or both given.
+ *                  For plane j, step t, slot u = t0 + t and pixel p, with g_b, y_b the fp32 values of sample b:
+ *                  d_b = g_b - y_b is formed in fp32, as the reference forms its error tensor; everything else is widened to
+ *                  fp64; every sum runs over b ascending from 0.0 and is NOT contracted (products are rounded, then added):
+ *                    sg = sum g_b   st = sum y_b   sgg = sum g_b g_b   stt = sum y_b y_b   sdd = sum (double)d_b (double)d_b
+ *                    mn = min_b d_b   mx = max_b d_b
+ *                  each sum is divided by (double)batch with the IEEE fp64 division, then
+ *                    mean[0][row][u][p] += sg / B    mean[1][row][u][p] += st / B
+ *                    sq[0][row][u][p] += sgg / B     sq[1][row][u][p] += stt / B     sq[2][row][u][p] += sdd / B
+ *                    err[0][row][u][p] = min(err[0][row][u][p], mn)    err[1][row][u][p] = max(err[1][row][u][p], mx)
+ *                  so a host statement in plain fp64 arithmetic reproduces the five sums bit for bit.  With assign != 0 every
+ *                  one of these is a plain assignment of the window's value and the old contents are not read (the host passes
+ *                  it for a window none of whose slots has been visited: up to 48 bytes per pixel and step less to read).  A
+ *                  plane with a NULL target updates mean[0] and sq[0] only.  NaN and infinity propagate through the sums.  For
+ *                  min and max, if any d_b is NaN or the stored value is NaN the result is NaN (payload not specified), which is
+ *                  what torch.min(dim=0) and torch.minimum do; the sign of a zero result is not specified.  Every accumulator
+ *                  index is formed in 64-bit (nrows * n_time * hw passes 2^31 in real use).
+ *                  Refused (ACE_ERR_INVALID, a message behind ace_diag_last_error, nothing written): t0 < 0 or
+ *                  t0 + steps > n_time; batch < 1 or steps < 1; steps > 65535 or nplanes > 65535 (grid dimensions; batch is a
+ *                  loop and has no upper limit); mean NULL; exactly one of sq and err given.  nplanes == 0 is a no-op.
+ *                  A thread owns four pixels of one (plane, step), loops over the samples with the loads of four samples of
+ *                  both sides in flight ahead of the adds (which stay in sample order), and keeps its 5 fp64 sums and 2 fp32
+ *                  extrema per pixel in registers: no scratch, no LDS, each slot owned by one thread, no atomics, bitwise
+ *                  repeatable.  One launch however many planes; no allocation, no host synchronisation.
  * ------------------------------------------------------------------------------------------ */
 const char* ace_diag_last_error(void);
 long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
@@ -678,6 +711,9 @@ int ace_diag_fill_planes(const float* const* srcs, const long* strides, const in
                          int nlon, void* stream);
 int ace_diag_time_segments(const float* const* srcs, const long* strides, const int* rows, const int* edges, double* sums,
                            float* means, int nrows, int nseg, int nplanes, int batch, int steps, long hw, void* stream);
+int ace_diag_video_window(const float* const* gen, const long* gen_strides, const float* const* target, const long* target_strides,
+                          const int* rows, double* mean, double* sq, float* err, int nrows, int n_time, int t0, int assign,
+                          int nplanes, int batch, int steps, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
