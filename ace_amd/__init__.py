@@ -34,8 +34,9 @@ from .coupled import (ComponentConfig, ComponentStepPrediction, CoupledDatasetIn
 from .coupled_rollout import CoupledEnginePredict, CoupledRolloutEngine, plan_coupled_window  # noqa: F401
 from .inference import EnginePredict, ForcingWindows, InferenceData, Looper, TensorFileWriter, repeat_members, run_evaluator, run_inference  # noqa: F401
 from .evaluator import InferenceEvaluatorAggregator, InferenceEvaluatorAggregatorConfig  # noqa: F401
-from .data_writer import (DataWriter, DataWriterConfig, MonthlyCoarsenConfig, MonthlyDataWriter, PairedDataWriter,  # noqa: F401
-                          PairedMonthlyDataWriter, PairedTensorFileWriter, PairedTimeCoarsen, SegmentReducer, TimeCoarsen,
-                          TimeCoarsenConfig, segment_sums)
+from .data_writer import (DataWriter, DataWriterConfig, FileWriter, FileWriterConfig, MonthlyCoarsenConfig,  # noqa: F401
+                          MonthlyDataWriter, MonthSelector, NetCDFWriterConfig, PairedDataWriter, PairedFileWriter,
+                          PairedMonthlyDataWriter, PairedTensorFileWriter, PairedTimeCoarsen, SegmentReducer, Slice, TimeCoarsen,
+                          TimeCoarsenConfig, TimeSlice, ZarrWriterConfig, extent_indices, segment_sums)
 
 __version__ = "0.1.0"

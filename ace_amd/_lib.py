@@ -246,6 +246,8 @@ SIGNATURES = {
     "ace_diag_fill_planes": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
     # srcs, strides, rows, edges, sums, means, nrows, nseg, nplanes, batch, steps, hw, stream
     "ace_diag_time_segments": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_long, c_void_p]),
+    # srcs, strides, rows, bounds, sums, means, nrows, nseg, nplanes, batch, steps, nlat, nlon, lat0, nlat_r, lon0, nlon_r, stream
+    "ace_diag_region_segments": (c_int, [c_void_p] * 6 + [c_int] * 11 + [c_void_p]),
     # gen, gen_strides, target, target_strides, rows, mean, sq, err, nrows, n_time, t0, assign, nplanes, batch, steps, hw, stream
     "ace_diag_video_window": (c_int, [c_void_p] * 8 + [c_int] * 7 + [c_long, c_void_p]),
 }

@@ -1,4 +1,4 @@
-// What the diagnostics kernels (diag.hip, hist.hip, regress.hip, calendar.hip, ensemble.hip, video.hip) share: the pixel partition of a plane, the guarded 4-pixel load,
+// What the diagnostics kernels (diag.hip, hist.hip, regress.hip, calendar.hip, ensemble.hip, timeseg.hip, region.hip, video.hip) share: the pixel partition of a plane, the guarded 4-pixel load,
 // the wave reductions and the error report behind ace_diag_last_error.  A new diag kernel starts from here.
 #pragma once
 #include <hip/hip_runtime.h>

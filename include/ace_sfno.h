@@ -632,6 +632,40 @@ int ace_couple_atmosphere_to_ocean(const float* const* srcs, const long* src_str
  *                  pixels in registers and stores each segment's result as the segment closes: no scratch, each output slot
  *                  written by one thread, no atomics, bitwise repeatable.  One launch however many planes; no allocation, no
  *                  host synchronisation.
+ *   diag_region_segments: the regional file writers' reduction (fme/ace/inference/data_writer/file_writer.py:505-551: a latitude /
+ *                  longitude box and a selection of steps, optionally after block means over time), ace_amd/data_writer.py: the
+ *                  rectangular-region counterpart of diag_time_segments, for all names of a window in one launch, written as a
+ *                  compact record.  srcs / strides / rows: as diag_time_segments, planes of nlat * nlon contiguous fp32 starting
+ *                  at any 4-byte boundary, sample and step strides in floats; a NULL srcs[j] or a rows[j] out of range
+ *                  [0, nrows) writes nothing.  bounds: DEVICE int [batch][nseg][2]; segment s of sample b is the steps [lo, hi)
+ *                  with lo = min(max(bounds[b][s][0], 0), steps) and hi = min(max(bounds[b][s][1], 0), steps): both ends are
+ *                  clamped on the device, so no content of this table can make the kernel read outside a plane.  hi <= lo is an
+ *                  empty segment.  Unlike edges, segments need not touch: the steps between two segments are never read, which
+ *                  is what a time selection needs; segments may overlap.  The region is the rows [lat0, lat0 + nlat_r) and the
+ *                  columns [lon0, lon0 + nlon_r) of the plane; there is no wrap across the date line (the reference has none,
+ *                  file_writer.py:531).
+ *                  For plane j, sample b, segment s and region pixel (i, k):  acc = 0.0;  for t ascending from lo to hi - 1:
+ *                  acc += (double)x[b][t][lat0 + i][lon0 + k];  then, both assignments, not +=:
+ *                    sums  (DEVICE fp64 [nrows][batch][nseg][nlat_r][nlon_r], may be NULL)  [rows[j]][b][s][i][k] = acc
+ *                    means (DEVICE fp32 [nrows][batch][nseg][nlat_r][nlon_r], may be NULL)  [rows[j]][b][s][i][k] =
+ *                                                                                          (float)(acc / (double)(hi - lo))
+ *                  The adds are plain fp64 adds in step order with no reassociation or contraction and the division is the IEEE
+ *                  fp64 one, so a host statement in fp64 arithmetic reproduces both outputs bit for bit.  An empty segment gives
+ *                  sums 0 and means NaN (0.0 / 0.0).  NaN and infinity propagate.  A segment of one step returns the input
+ *                  value, with one exception in the sign bit: 0.0 + -0.0 is +0.0, so a -0.0 input comes back as +0.0.
+ *                  Nothing outside the region, or outside the steps of some segment, is read into a result; nothing outside the
+ *                  nrows * batch * nseg * nlat_r * nlon_r slots of each output is written.
+ *                  Refused (ACE_ERR_INVALID, a message behind ace_diag_last_error, nothing written): lat0 < 0, nlat_r < 1 or
+ *                  lat0 + nlat_r > nlat, and the same for longitude; nlat < 1 or nlon < 1; neither sums nor means given; and
+ *                  diag_time_segments' limits: nrows >= 1, 1 <= batch <= 65535, 0 <= nplanes <= 65535 (grid dimensions),
+ *                  steps >= 1, 0 <= nseg < 2^31 - 1.  nplanes == 0 or nseg == 0 is a no-op.  rows must not name one row twice;
+ *                  this is not checked.
+ *                  A thread owns four consecutive pixels of the compact record and keeps their sums in registers across a
+ *                  segment.  The four are one 16-byte load only when nlon_r, lon0, nlon, the base and both strides are all
+ *                  multiples of 4 floats; otherwise they may lie in two region rows and are loaded one by one.  The choice is
+ *                  made once per workgroup (it depends on the plane), never per load.  No scratch, each output slot written by
+ *                  one thread, no atomics, bitwise repeatable.  One launch however many planes; no allocation, no host
+ *                  synchronisation.
  *   diag_video_window: the evaluator's video metric (fme/ace/aggregator/inference/video.py:33-255), ace_amd/evaluator/video.py:
  *                  per time slot of the whole inference and per pixel, the means over the samples of both sides and, for the
  *                  extended videos, of their squares and of the squared error, with the smallest and largest error - for all
@@ -711,6 +745,9 @@ int ace_diag_fill_planes(const float* const* srcs, const long* strides, const in
                          int nlon, void* stream);
 int ace_diag_time_segments(const float* const* srcs, const long* strides, const int* rows, const int* edges, double* sums,
                            float* means, int nrows, int nseg, int nplanes, int batch, int steps, long hw, void* stream);
+int ace_diag_region_segments(const float* const* srcs, const long* strides, const int* rows, const int* bounds, double* sums,
+                             float* means, int nrows, int nseg, int nplanes, int batch, int steps, int nlat, int nlon, int lat0,
+                             int nlat_r, int lon0, int nlon_r, void* stream);
 int ace_diag_video_window(const float* const* gen, const long* gen_strides, const float* const* target, const long* target_strides,
                           const int* rows, double* mean, double* sq, float* err, int nrows, int n_time, int t0, int assign,
                           int nplanes, int batch, int steps, long hw, void* stream);
