@@ -23,6 +23,7 @@ from .samudra import CapturedSamudraForward, Samudra, SamudraBuilder  # noqa: F4
 from .corrector import AtmosphereCorrectorConfig  # noqa: F401
 from .ocean import OceanConfig  # noqa: F401
 from .derived_variables import AtmosphericDeriveFn, compute_derived_quantities  # noqa: F401
+from .ocean_derived_variables import OceanDeriveFn, compute_ocean_derived_quantities  # noqa: F401
 from .timeaxis import TimeAxis  # noqa: F401
 from .insolation import InsolationConfig  # noqa: F401
 from .derived_forcings import DerivedForcingsConfig, ForcingDeriver, ForcingWindow  # noqa: F401

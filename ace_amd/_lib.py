@@ -78,6 +78,32 @@ class OceanFields(ctypes.Structure):
                 ("hfgeou", Plane)]
 
 
+# ---- the ocean's derived variables (ace_ocean_derive_window): struct ace_ocean_derive_field / _level / _desc
+OCEAN_DERIVE_OUTPUTS = ("ocean_heat_content", "ocean_heat_content_tendency", "implied_tendency_of_ocean_heat_content_due_to_advection",
+                        "net_energy_flux_into_ocean_column", "sea_ice_fraction", "HI", "hfds")      # bit i of `want`, slot i of `out`
+
+
+class OceanDeriveField(ctypes.Structure):
+    """struct ace_ocean_derive_field"""
+    _fields_ = [("base", c_void_p), ("bstride", c_long), ("tstride", c_long)]
+
+
+class OceanDeriveLevel(ctypes.Structure):
+    """struct ace_ocean_derive_level"""
+    _fields_ = [("f", OceanDeriveField), ("head", c_void_p), ("head_bstride", c_long)]
+
+
+class OceanDeriveDesc(ctypes.Structure):
+    """struct ace_ocean_derive_desc"""
+    _fields_ = [("nlev", c_int), ("thetao", OceanDeriveLevel * OCEAN_MAX_LEVELS), ("dz", c_void_p), ("mask0", c_void_p),
+                ("area_m2", c_void_p), ("hfds", OceanDeriveField), ("hfds_total_area", OceanDeriveField), ("hfgeou", OceanDeriveField),
+                ("sea_surface_fraction", OceanDeriveField), ("land_fraction", OceanDeriveField),
+                ("ocean_sea_ice_fraction", OceanDeriveField), ("sea_ice_fraction", OceanDeriveField), ("sea_ice_volume", OceanDeriveField),
+                ("out", c_void_p * len(OCEAN_DERIVE_OUTPUTS)), ("out_bstride", c_long), ("out_tstride", c_long),
+                ("want", ctypes.c_uint), ("has_head", c_int), ("dt_seconds", c_double), ("batch", c_int), ("steps", c_int),
+                ("hw", c_long), ("t_chunk", c_int)]
+
+
 class GemmRoute(ctypes.Structure):
     """struct ace_gemm_route"""
     _fields_ = [("family", c_int), ("tile", c_int)]
@@ -201,6 +227,8 @@ SIGNATURES = {
     "ace_ocean_phys_destroy": (None, [c_void_p]),
     "ace_ocean_phys_apply": (c_int, [c_void_p, POINTER(OceanFields), c_int, c_void_p]),
     "ace_ocean_phys_launches": (c_int, [c_void_p, POINTER(c_long), POINTER(c_long)]),
+    "ace_ocean_derive_last_error": (c_char_p, []),
+    "ace_ocean_derive_window": (c_int, [POINTER(OceanDeriveDesc), c_void_p]),
     "ace_mask_last_error": (c_char_p, []),
     # srcs, src_strides, dsts, dst_strides, mask_idx, hits, nmask, fill, nplanes, batch, hw, stream
     "ace_mask_planes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_long,

@@ -31,6 +31,7 @@ from torch import nn
 
 from .ocean import Prescriber
 from .ocean_corrector import OCEAN_FIELD_NAME_PREFIXES
+from .ocean_derived_variables import OceanDeriveFn
 from .stepper import PrognosticState, Stepper, derive_over_window
 
 TensorMapping = Mapping[str, torch.Tensor]
@@ -737,8 +738,10 @@ class CoupledStepper:
                 compute_derived_variables: bool = False) -> Tuple[Dict[str, TensorDict], Dict[str, PrognosticState]]:
         """stepper.py:1388-1409: ({"atmosphere": name -> (B, n_outer * n_inner, H, W), "ocean": name -> (B, n_outer, H, W)},
         the final state).  The state - a ``PrognosticState`` per realm carrying the component's ``stepper_state`` - can be fed
-        back as the next window's ``initial_condition``.  ``compute_derived_variables``: the atmosphere's, as ``Stepper.predict``
-        computes them; this package has no ocean derive function, the ocean's output is returned as generated."""
+        back as the next window's ``initial_condition``.  ``compute_derived_variables``: each realm's, as ``Stepper.predict``
+        computes them with the component's ``derive_func``: the atmosphere's on its hybrid sigma-pressure coordinate, the ocean's
+        (ocean heat content and its budget, sea-ice thickness, ...) on its depth coordinate, the first step's tendencies taken
+        against the initial condition."""
         with torch.no_grad():
             outs = list(self.predict_generator(initial_condition, forcing))
         data: Dict[str, TensorDict] = {}
@@ -748,7 +751,8 @@ class CoupledStepper:
             if not steps:
                 raise ValueError("the forcing records hold no coupled step")
             data[realm] = {k: torch.stack([o.data[k] for o in steps], dim=self.TIME_DIM) for k in steps[0].data}
-            if compute_derived_variables and realm == "atmosphere":
+            # an ocean without a depth coordinate derives nothing (the reference's NullDeriveFn)
+            if compute_derived_variables and (realm == "atmosphere" or isinstance(stepper.derive_func, OceanDeriveFn)):
                 data[realm] = derive_over_window(stepper.derive_func, data[realm], initial_condition[realm], forcing[realm],
                                                  1, len(steps))
             state[realm] = _prognostic_state(steps[-1].data, stepper.prognostic_names, steps[-1].stepper_state)

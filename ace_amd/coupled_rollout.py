@@ -31,6 +31,7 @@ from .coupled import (MAX_NAMES, OFRAC_CARRIED, OFRAC_FROM_OCEAN_SIF, OFRAC_FROM
                       TensorDict, TensorMapping, _check)
 from .ocean_rollout import OceanRolloutEngine
 from .rollout import RolloutEngine, WindowEngine
+from .ocean_derived_variables import OceanDeriveFn
 from .stepper import PrognosticState, derive_over_window
 
 # a (B, H, W) plane - or, as a destination, the first level of a window - of an engine: realm "atmosphere" / "ocean"; buffer "ic",
@@ -388,8 +389,11 @@ class CoupledRolloutEngine:
             state[realm] = PrognosticState({k: eng.out[k][:, -1:] for k in eng.prognostic})
             state[realm].stepper_state = carried[realm]
         if compute_derived_variables:
-            data["atmosphere"] = derive_over_window(self.stepper.atmosphere.derive_func, data["atmosphere"],
-                                                    initial_condition["atmosphere"], forcing["atmosphere"], 1, self.atmosphere.T)
+            for realm, eng in (("atmosphere", self.atmosphere), ("ocean", self.ocean)):
+                derive_func = getattr(self.stepper, realm).derive_func
+                if realm == "ocean" and not isinstance(derive_func, OceanDeriveFn):
+                    continue              # an ocean without a depth coordinate derives nothing (the reference's NullDeriveFn)
+                data[realm] = derive_over_window(derive_func, data[realm], initial_condition[realm], forcing[realm], 1, eng.T)
         return data, state
 
 

@@ -258,6 +258,9 @@ class InsolationConfig:
         return names
 
 
+EARTH_RADIUS = 6371000.0     # fme/core/constants.py, m
+
+
 class LatLonGrid:
     """The slice of fme.core.coordinates.LatLonCoordinates this needs: 1-D lat / lon in degrees -> ``meshgrid`` on a device."""
 
@@ -267,6 +270,17 @@ class LatLonGrid:
 
     def to(self, device) -> "LatLonGrid":
         return LatLonGrid(self.lat.to(device), self.lon.to(device))
+
+    @property
+    def area_weights(self) -> torch.Tensor:
+        """coordinates.py:642-646: (nlat, nlon) weights summing to 1, the ones ``DatasetInfo.area_weights`` and the aggregators use"""
+        from .atmosphere import spherical_area_weights
+        return spherical_area_weights(self.lat, len(self.lon))
+
+    @property
+    def area_weights_m2(self) -> torch.Tensor:
+        """coordinates.py:648-650: cell areas in square metres"""
+        return 4 * torch.pi * EARTH_RADIUS**2 * self.area_weights
 
     @property
     def meshgrid(self) -> Tuple[torch.Tensor, torch.Tensor]:

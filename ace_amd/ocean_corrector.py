@@ -109,6 +109,12 @@ class DepthCoordinate:
             out["deptho"] = self.deptho
         return out
 
+    def build_derive_function(self, timestep, horizontal_coordinates=None):
+        """coordinates.py:349-354: the ocean's derived variables on this coordinate (``horizontal_coordinates``: the cell areas the
+        sea-ice thickness needs)."""
+        from .ocean_derived_variables import OceanDeriveFn
+        return OceanDeriveFn(self, timestep, horizontal_coordinates)
+
     def depth_integral(self, integrand: torch.Tensor) -> torch.Tensor:
         """sum_k x_k dz_k with NaNs counted as zero; NaN where the top level is masked."""
         if len(self.idepth) != integrand.shape[-1] + 1:

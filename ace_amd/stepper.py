@@ -27,6 +27,16 @@ class PrognosticState(dict):
 
 def derive_over_window(derive_func, data: TensorDict, initial_condition: TensorMapping, forcing: TensorMapping,
                        n_ic: int, n_forward_steps: int) -> TensorDict:
+    """single_module.py:1236-1245: the derived variables of a window's generated steps, the first step's tendencies taken against
+    the initial condition.  A derive function with a ``window`` method (``OceanDeriveFn``) reads the initial condition where it
+    lies; any other gets the concatenated window."""
+    if hasattr(derive_func, "window"):
+        return derive_func.window(data, initial_condition, forcing, n_ic, n_forward_steps)
+    return derive_by_concatenation(derive_func, data, initial_condition, forcing, n_ic, n_forward_steps)
+
+
+def derive_by_concatenation(derive_func, data: TensorDict, initial_condition: TensorMapping, forcing: TensorMapping,
+                            n_ic: int, n_forward_steps: int) -> TensorDict:
     """single_module.py:1236-1245: prepend the initial condition (names it does not hold are NaN there,
     batch_data.py:889-913), compute the derived variables against the forcing of the same time levels, drop the initial
     time level again."""
@@ -52,6 +62,7 @@ class Stepper:
         self._multi_call = None
         self.replace_multi_call(multi_call)
         self._dataset_info = dataset_info
+        self._ocean_derive_func = None         # built on first use (see `derive_func`)
         # forcings computed from the time axis (StepperConfig.derived_forcings, single_module.py:532-539, 870)
         self._derived_forcings = DerivedForcingsConfig.from_state(derived_forcings)
         self.forcing_deriver = self._derived_forcings.build(dataset_info)
@@ -231,9 +242,18 @@ class Stepper:
 
     @property
     def derive_func(self):
-        """single_module.py:606-613, 895-897: the derived-variable function of the dataset's vertical coordinate."""
+        """single_module.py:606-613, 895-897: the derived-variable function of the dataset's vertical coordinate: the atmosphere's
+        on a hybrid sigma-pressure coordinate (or none), the ocean's (``OceanDeriveFn``, with the dataset's horizontal coordinates
+        for the cell areas) on a depth coordinate.  The ocean's is built once: it keeps its device tables."""
+        vc = self._step_obj._vertical_coordinate
+        depth = getattr(self._dataset_info, "ocean_vertical_coordinate", None) if vc is None else None
+        if depth is not None:
+            if self._ocean_derive_func is None or self._ocean_derive_func.depth_coordinate is not depth:
+                self._ocean_derive_func = depth.build_derive_function(self._step_obj._timestep,
+                                                                      getattr(self._dataset_info, "horizontal_coordinates", None))
+            return self._ocean_derive_func
         from .derived_variables import AtmosphericDeriveFn
-        return AtmosphericDeriveFn(self._step_obj._vertical_coordinate, self._step_obj._timestep)
+        return AtmosphericDeriveFn(vc, self._step_obj._timestep)
 
     def predict(self, initial_condition: TensorMapping, forcing: TensorMapping,
                 n_forward_steps: Optional[int] = None, compute_derived_variables: bool = False, labels=None,

@@ -995,6 +995,92 @@ int ace_ocean_phys_apply(ace_ocean_phys* h, const ace_ocean_fields* fields, int 
 /* Route query: O1 / O2 launches this handle has made. */
 int ace_ocean_phys_launches(const ace_ocean_phys* h, long* o1, long* o2);
 
+/* ------------------------------------------------------------------------------------------
+ * The ocean's derived variables (fme/core/ocean_derived_variables.py; OceanData, fme/core/ocean_data.py) over one window of
+ * batch x steps x hw pixels, any subset of the seven in one launch.  Every input plane is read once, every wanted output
+ * written once; no atomics, no scratch, no allocation, no host synchronisation; all fp64 work in a fixed order, so two
+ * identical calls - and calls that differ in t_chunk only - give identical bytes.
+ *
+ * A field is {base, bstride, tstride}: the plane of sample b at step t is the hw contiguous floats at base + b * bstride +
+ * t * tstride (strides in floats, any 4-byte alignment; tstride 0 is a field constant in time); base NULL: absent.  A thetao
+ * level carries in addition `head`, the plane of the time level before step 0 (the initial condition) at head + b *
+ * head_bstride; NULL: the initial condition has no such level.  dz is (nlev, hw) fp32 (DepthCoordinate.dz, 0 where masked),
+ * mask0 (hw) fp32 the top level's ocean mask, area_m2 (hw) fp32 the cell areas in square metres (HI only; else NULL).
+ * Name resolution is the host's job: which of the reference's alternatives applies follows from which planes are present.
+ *
+ * With CP_RHO = 3992.0 * 1035.0 (SPECIFIC_HEAT_OF_SEA_WATER_CM4 * DENSITY_OF_SEA_WATER_CM4) as one double and ssf the
+ * sea_surface_fraction plane, or 1 - land_fraction in fp32 when that is absent:
+ *   S(b, t, p)   CP_RHO * sum over k = 0 .. nlev - 1, in that order, of (double) thetao_k * (double) dz_k(p) in fp64 (every product
+ *                is exact), a NaN thetao_k contributing 0 (the reference's nansum); S(b, -1, p) is the same sum over the head
+ *                planes, an absent head plane counting as NaN
+ *   OHC          ocean_heat_content: (float) S where mask0(p) > 0, NaN elsewhere
+ *   OHC_TENDENCY ocean_heat_content_tendency: where mask0(p) > 0, (float) ((S_t - S_{t-1}) / dt_seconds), the difference taken on
+ *                the fp64 sums; NaN where mask0(p) <= 0; at t = 0 without has_head +0.0 everywhere, land included (the
+ *                reference's zeros_like row)
+ *   HFDS         hfds (only when the hfds plane is absent): hfds_total_area / ssf, the correctly rounded fp32 quotient
+ *   NET_FLUX     net_energy_flux_into_ocean_column: (hfds + hfgeou) * ssf in fp32, in that order; hfds the plane or the
+ *                quotient above; an absent hfgeou is +0.0
+ *   ADVECTION    implied_tendency_of_ocean_heat_content_due_to_advection: the fp32 tendency as output minus the net flux, fp32
+ *   SEA_ICE_FRACTION  sea_ice_fraction (only when that plane is absent): ocean_sea_ice_fraction * (1 - land_fraction) in fp32
+ *   HI           sea-ice thickness: with frac = ocean_sea_ice_fraction * ssf, or (sea_ice_fraction * ssf) / (1 - land_fraction)
+ *                when ocean_sea_ice_fraction is absent, both in fp32, and vol = sea_ice_volume, area = area_m2:
+ *                (double) vol * 1e9 / ((double) area * (double) frac) in fp64 (both products exact), rounded to fp32.  At
+ *                special inputs it has the value of the reference's where(isnan(vol), NaN, nan_to_num(exp(9 ln 10 + ln vol -
+ *                ln area - ln frac))) on the extended reals, the first matching row of
+ *                    vol NaN                                   NaN
+ *                    frac, area or 1 - land_fraction NaN       0
+ *                    vol < 0, frac < 0 or area < 0             0
+ *                    vol == 0, whatever frac                   0
+ *                    frac == +inf or area == +inf              0
+ *                    vol == +inf                               FLT_MAX
+ *                    vol > 0 and frac == 0 (or area == 0)      FLT_MAX
+ *                    any overflow past FLT_MAX                 FLT_MAX
+ * Output i of `want` (bit 1 << i, i one of ACE_OCEAN_DERIVE_*) is written at out[i] + b * out_bstride + t * out_tstride; of an
+ * output not in `want` not one byte is touched, and its out[i] is not read.
+ *
+ * Time is cut into chunks of t_chunk steps (0: chosen by the library so that a small window still fills the device); a
+ * chunk's first step recomputes S of the step before it, so chunks are independent.
+ *
+ * Refused (ACE_ERR_INVALID before any launch, the reason behind ace_ocean_derive_last_error, nothing written): a wanted output
+ * with an absent input (for OHC, OHC_TENDENCY and ADVECTION: dz, mask0 and every thetao_k, k < nlev, with nlev in 1 ..
+ * ACE_OCEAN_MAX_LEVELS; dt_seconds > 0 for the latter two) or a NULL destination; HFDS or SEA_ICE_FRACTION wanted while its
+ * plane exists; nlev outside 0 .. ACE_OCEAN_MAX_LEVELS whatever is wanted; batch outside 1 .. 65535, steps < 1, hw < 1,
+ * t_chunk < 0, more than 65535 time chunks; bits of `want` above the seven.  want == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------ */
+#define ACE_OCEAN_DERIVE_OHC 0                 /* the reference's registration order */
+#define ACE_OCEAN_DERIVE_OHC_TENDENCY 1
+#define ACE_OCEAN_DERIVE_ADVECTION 2
+#define ACE_OCEAN_DERIVE_NET_FLUX 3
+#define ACE_OCEAN_DERIVE_SEA_ICE_FRACTION 4
+#define ACE_OCEAN_DERIVE_HI 5
+#define ACE_OCEAN_DERIVE_HFDS 6
+#define ACE_OCEAN_DERIVE_NOUT 7
+
+typedef struct ace_ocean_derive_field { const float* base; long bstride, tstride; } ace_ocean_derive_field;
+typedef struct ace_ocean_derive_level { ace_ocean_derive_field f; const float* head; long head_bstride; } ace_ocean_derive_level;
+
+typedef struct ace_ocean_derive_desc {
+    int nlev;
+    ace_ocean_derive_level thetao[ACE_OCEAN_MAX_LEVELS];
+    const float* dz;
+    const float* mask0;
+    const float* area_m2;
+    ace_ocean_derive_field hfds, hfds_total_area, hfgeou, sea_surface_fraction, land_fraction, ocean_sea_ice_fraction,
+        sea_ice_fraction, sea_ice_volume;
+    float* out[ACE_OCEAN_DERIVE_NOUT];
+    long out_bstride, out_tstride;
+    unsigned want;
+    int has_head;
+    double dt_seconds;
+    int batch, steps;
+    long hw;
+    int t_chunk;
+} ace_ocean_derive_desc;
+
+const char* ace_ocean_derive_last_error(void);
+/* `desc` is a HOST struct of device pointers (copied into the kernel arguments). */
+int ace_ocean_derive_window(const ace_ocean_derive_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
