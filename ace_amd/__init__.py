@@ -14,6 +14,9 @@ from .sfno import SphericalFourierNeuralOperatorBuilder, SphericalFourierNeuralO
 from .packer import Packer  # noqa: F401
 from .normalizer import StandardNormalizer  # noqa: F401
 from .step import SecondaryDecoderConfig, SingleModuleStep, SingleModuleStepConfig, StepArgs, StepOutput, StepperState  # noqa: F401
+from .global_mean_removal import (  # noqa: F401
+    DEFAULT_TEMPERATURE_FIELD_NAMES, GlobalMeanRemoval, GlobalMeanRemovalState, PerChannelGlobalMeanRemoval,
+    PerChannelGlobalMeanRemovalConfig, SharedGlobalMeanRemoval, SharedGlobalMeanRemovalConfig, extra_channel_source_field)
 from .rand import RandomState, randn, randn_like, use_cpu_randn, use_generator  # noqa: F401
 from .mlp import ColumnMLP, MLPConfig  # noqa: F401
 from .checkpoint import LoadedStepper, StepperOverrideConfig, apply_stepper_override, load_stepper  # noqa: F401

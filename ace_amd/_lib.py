@@ -236,6 +236,15 @@ SIGNATURES = {
     # srcs, src_strides, mask_idx, hits, nmask, fill, stage, stage_strides, mean, std, dst, npack, nplanes, batch, hw, stream
     "ace_mask_pack_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    "ace_gmr_chunks": (c_long, [c_long]),
+    # srcs, strides, plane_idx, nsrc, partials, batch, K, hw, stream
+    "ace_gmr_partials": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_long, c_void_p]),
+    # srcs, strides, plane_idx, nsrc, partials, means, batch, K, hw, stream
+    "ace_gmr_sample_means": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p]),
+    # srcs, strides, mean, std, shift_idx, partials, clim_mean, extra_idx, extra_std, dst, shift, batch, nin, nextra, K, hw, stream
+    "ace_gmr_pack_normalize": (c_int, [c_void_p] * 11 + [c_int] * 4 + [c_long, c_void_p]),
+    # src, mean, std, dsts, strides, shift_idx, shift, batch, nch, K, hw, stream
+    "ace_gmr_unpack_denormalize": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_long, c_void_p]),
     "ace_couple_last_error": (c_char_p, []),
     # srcs, src_strides, dsts, dst_strides, masks, npass, mode, interpolate, n_inner, batch, hw, stream
     "ace_couple_ocean_to_atmosphere": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_long, c_void_p]),

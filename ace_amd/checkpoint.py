@@ -158,9 +158,8 @@ def stepper_config_from_state(state: Mapping[str, Any], ignore_unsupported: bool
     step_cfg.pop("normalization", None)
     builder = step_cfg.pop("builder")
     unsupported = []
-    for k in ("global_mean_removal", "input_dropout"):
-        if step_cfg.get(k) is not None:
-            unsupported.append(k)
+    if step_cfg.get("input_dropout") is not None:
+        unsupported.append("input_dropout")
     if step_cfg.get("include_channel_mask_inputs"):
         unsupported.append("include_channel_mask_inputs")
     if unsupported and not ignore_unsupported:

@@ -693,6 +693,10 @@ class CoupledStepper:
         from .checkpoint import load_stepper
         ocean = load_stepper(state["ocean_state"], device=device, ignore_unsupported=ignore_unsupported)
         atmosphere = load_stepper(state["atmosphere_state"], device=device, ignore_unsupported=ignore_unsupported)
+        for realm, loaded in (("ocean", ocean), ("atmosphere", atmosphere)):
+            if loaded.stepper.config.global_mean_removal is not None:
+                raise NotImplementedError(f"coupled stepper: the {realm} component's step carries global_mean_removal, which the "
+                                          "coupled exchange has not been built for; load the component on its own with load_stepper")
         config = CoupledStepperConfig.from_state(state["config"])
         if "dataset_info" in state:
             dataset_info = CoupledDatasetInfo.from_state(state["dataset_info"])

@@ -206,6 +206,9 @@ def check_supported(stepper: CoupledStepper, n_coupled_steps: int, graph: Option
     atmosphere, ocean = stepper.atmosphere, stepper.ocean
     a_step = atmosphere._step_obj
     net = a_step.module.torch_module
+    for realm, component in (("atmosphere", atmosphere), ("ocean", ocean)):
+        if getattr(component._step_obj, "global_mean_removal", None) is not None:
+            raise _refuse(f"global_mean_removal on the {realm} component is not supported")
     if not hasattr(net, "_ensure_native"):
         raise _refuse(f"the atmosphere's module is a {type(net).__name__}, not of the SFNO family")
     if hasattr(net, "draw_noise"):

@@ -986,6 +986,51 @@ extern "C" int ace_unpack_denormalize(const float* src, const float* mean, const
     return ACE_OK;
 }
 
+// global-mean removal (gmr.hip): the argument checks on the host, before the first HIP call
+static bool gmr_bad_shape(int batch, int nch, int K, long hw) {
+    return batch < 1 || batch > 65535 || nch < 1 || nch > 65535 || K < 1 || K > 65535 || hw < 1 || gmr_chunks(hw) > 0x7fffffffL;
+}
+extern "C" long ace_gmr_chunks(long hw) { return gmr_chunks(hw); }
+extern "C" int ace_gmr_partials(const float* const* srcs, const long* strides, const int* plane_idx, int nsrc, double* partials,
+                                int batch, int K, long hw, void* stream) {
+    if (gmr_bad_shape(batch, nsrc, K, hw)) return fail(ACE_ERR_INVALID, "ace_gmr_partials: bad shape");
+    if (!srcs || !strides || !plane_idx || !partials) return fail(ACE_ERR_INVALID, "ace_gmr_partials: null argument");
+    HIP_TRY(launch_gmr_partials(srcs, strides, plane_idx, nsrc, partials, batch, K, hw, static_cast<hipStream_t>(stream)));
+    return ACE_OK;
+}
+extern "C" int ace_gmr_sample_means(const float* const* srcs, const long* strides, const int* plane_idx, int nsrc,
+                                    double* partials, float* means, int batch, int K, long hw, void* stream) {
+    if (gmr_bad_shape(batch, nsrc, K, hw)) return fail(ACE_ERR_INVALID, "ace_gmr_sample_means: bad shape");
+    if (!srcs || !strides || !plane_idx || !partials || !means)
+        return fail(ACE_ERR_INVALID, "ace_gmr_sample_means: null argument");
+    HIP_TRY(launch_gmr_partials(srcs, strides, plane_idx, nsrc, partials, batch, K, hw, static_cast<hipStream_t>(stream)));
+    HIP_TRY(launch_gmr_sample_means(partials, means, batch, K, hw, static_cast<hipStream_t>(stream)));
+    return ACE_OK;
+}
+extern "C" int ace_gmr_pack_normalize(const float* const* srcs, const long* strides, const float* mean, const float* std_,
+                                      const int* shift_idx, const double* partials, const float* clim_mean,
+                                      const int* extra_idx, const float* extra_std, float* dst, float* shift, int batch, int nin,
+                                      int nextra, int K, long hw, void* stream) {
+    if (gmr_bad_shape(batch, nin, K, hw) || K > nin || nextra < 0 || nin + nextra > 65535)
+        return fail(ACE_ERR_INVALID, "ace_gmr_pack_normalize: bad shape (1 <= K <= nin, nextra >= 0)");
+    if (!srcs || !strides || !mean || !std_ || !shift_idx || !partials || !clim_mean || !dst || !shift ||
+        (nextra > 0 && (!extra_idx || !extra_std)))
+        return fail(ACE_ERR_INVALID, "ace_gmr_pack_normalize: null argument");
+    HIP_TRY(launch_gmr_pack_normalize(srcs, strides, mean, std_, shift_idx, partials, clim_mean, extra_idx, extra_std, dst, shift,
+                                      batch, nin, nextra, K, hw, static_cast<hipStream_t>(stream)));
+    return ACE_OK;
+}
+extern "C" int ace_gmr_unpack_denormalize(const float* src, const float* mean, const float* std_, float* const* dsts,
+                                          const long* strides, const int* shift_idx, const float* shift, int batch, int nch, int K,
+                                          long hw, void* stream) {
+    if (gmr_bad_shape(batch, nch, K, hw)) return fail(ACE_ERR_INVALID, "ace_gmr_unpack_denormalize: bad shape");
+    if (!src || !mean || !std_ || !dsts || !strides || !shift_idx || !shift)
+        return fail(ACE_ERR_INVALID, "ace_gmr_unpack_denormalize: null argument");
+    HIP_TRY(launch_gmr_unpack_denormalize(src, mean, std_, dsts, strides, shift_idx, shift, batch, nch, K, hw,
+                                          static_cast<hipStream_t>(stream)));
+    return ACE_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // the network
 // ---------------------------------------------------------------------------------------------

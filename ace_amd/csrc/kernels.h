@@ -389,4 +389,17 @@ hipError_t launch_pack_normalize(const float* const* srcs, const long* strides, 
 hipError_t launch_unpack_denormalize(const float* src, const float* mean, const float* stdv, float* const* dsts,
                                      const long* strides, int Bt, int nch, long HW, hipStream_t s);
 
+// global-mean removal folded into the stepper glue (gmr.hip; the contract is stated with ace_gmr_* in include/ace_sfno.h)
+long gmr_chunks(long HW);
+hipError_t launch_gmr_partials(const float* const* srcs, const long* strides, const int* plane_idx, int nsrc, double* partials,
+                               int Bt, int K, long HW, hipStream_t s);
+hipError_t launch_gmr_sample_means(const double* partials, float* means, int Bt, int K, long HW, hipStream_t s);
+hipError_t launch_gmr_pack_normalize(const float* const* srcs, const long* strides, const float* mean, const float* stdv,
+                                     const int* shift_idx, const double* partials, const float* clim_mean,
+                                     const int* extra_idx, const float* extra_std, float* dst, float* shift, int Bt, int nin,
+                                     int nextra, int K, long HW, hipStream_t s);
+hipError_t launch_gmr_unpack_denormalize(const float* src, const float* mean, const float* stdv, float* const* dsts,
+                                         const long* strides, const int* shift_idx, const float* shift, int Bt, int nch, int K,
+                                         long HW, hipStream_t s);
+
 }  // namespace ace

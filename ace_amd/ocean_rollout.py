@@ -60,6 +60,8 @@ class OceanRolloutEngine(WindowEngine):
         step = stepper._step_obj
         cfg = step.config
         net = step.module.torch_module
+        if getattr(step, "global_mean_removal", None) is not None:      # whatever the module: the fused masking pack knows no shift
+            raise _refuse("global_mean_removal is not supported")
         if not isinstance(net, Samudra):
             if hasattr(net, "_ensure_native"):      # the SFNO family
                 raise NotImplementedError(f"OceanRolloutEngine runs Samudra steppers; a {type(net).__name__} stepper runs through "

@@ -12,6 +12,11 @@ Per step s the engine enqueues
 so the numbers are bit-identical to `Stepper.predict` (same kernels, same (x-mean)/std and y*std+mean roundings).
 Nothing is allocated and the host never synchronises inside the window.
 
+A stepper with global-mean removal (ace_amd/global_mean_removal.py) replaces 1 by ace_gmr_partials + ace_gmr_pack_normalize (the
+per-sample means of the step's own inputs, the shift added in front of the normaliser, the synthetic channels written behind
+the in_names) and 3 by ace_gmr_unpack_denormalize (the shift taken off the listed outputs): csrc/gmr.hip.  Without the option the
+engine issues exactly the calls above.
+
 `WindowEngine` is what every static-buffer engine shares (`OceanRolloutEngine`, ocean_rollout.py, is the other): the buffers,
 the one statement of the window layout (`in_plane` / `next_plane` / `out_plane`), the tail of a forward, the window graph and
 load / predict / continue_from_last.  An engine supplies its pack and forward (`_enqueue_step`), what its captured graphs depend
@@ -63,7 +68,11 @@ class WindowEngine:
         self.target_names = sorted(set(next_data) - set(self.forcing_names))
         f32 = dict(dtype=torch.float32, device=dev)
         i64 = dict(dtype=torch.int64, device=dev)
-        self.x = torch.zeros(B, len(self.in_names), H, W, **f32)
+        # global-mean removal (ace_amd/global_mean_removal.py): its synthetic channels are packed behind the in_names
+        gmr = getattr(step, "global_mean_removal", None)
+        self.extra_names = list(gmr.extra_channel_names) if gmr is not None else []
+        self._gmr = None                # RolloutEngine's tables of the fused pack / unpack (_build_gmr)
+        self.x = torch.zeros(B, len(self.in_names) + len(self.extra_names), H, W, **f32)
         self.ic = {n: torch.zeros(B, 1, H, W, **f32) for n in self.prognostic}
         self.forcing = {n: torch.zeros(B, T + 1, H, W, **f32) for n in self.forcing_names}
         self.target = {n: torch.zeros(B, T + 1, H, W, **f32) for n in self.target_names}
@@ -117,6 +126,12 @@ class WindowEngine:
             y.index_add_(1, self._res_out, self.x.index_select(1, self._res_in))
         if self._fill_out:      # 0 in normalised space denormalises to the mean
             _nan_to_zero(y)
+        if self._gmr is not None:       # ... minus the shift of the listed outputs (single_module.py:666-668)
+            g = self._gmr
+            _lib.check(L.ace_gmr_unpack_denormalize(y.data_ptr(), self.out_mean.data_ptr(), self.out_std.data_ptr(), dst,
+                                                    dst_strides.data_ptr(), g["out_idx"].data_ptr(), g["shift"].data_ptr(), self.B,
+                                                    len(self.out_names), g["K"], self.HW, stream))
+            return
         _lib.check(L.ace_unpack_denormalize(y.data_ptr(), self.out_mean.data_ptr(), self.out_std.data_ptr(), dst,
                                             dst_strides.data_ptr(), self.B, len(self.out_names), self.HW, stream))
 
@@ -277,6 +292,7 @@ class RolloutEngine(WindowEngine):
             self._sec_dst_ptrs, self._sec_dst_ptr_addr = self._table([[self.out_plane(n, s).data_ptr() for n in self.sec_names]
                                                                       for s in range(T)])
             self._sec_dst_strides = torch.full((len(self.sec_names),), T * self.HW, **i64)
+        self._gmr = self._build_gmr(step)
         self._mc_state = None
         if self._mc is not None:
             from .multi_call import get_multi_call_name
@@ -323,6 +339,45 @@ class RolloutEngine(WindowEngine):
                             next_names=self.forcing_names + self.target_names, locate_gen=locate(self.out_plane),
                             locate_in=locate(self.in_plane), locate_next=locate(self.next_plane), device=self.device)
 
+    def _build_gmr(self, step):
+        """The device tables of the fused global-mean removal (csrc/gmr.hip; include/ace_sfno.h "Global-mean removal"): the K
+        reduced planes as indices into the pack's pointer-table row, the k of every shifted input / output channel, the
+        climatological means and the synthetic channels' sources, the fp64 partials and the (B, K) shift buffer.  None when the
+        stepper has no global-mean removal (or it processes nothing)."""
+        gmr = getattr(step, "global_mean_removal", None)
+        if gmr is None:
+            return None
+        from .global_mean_removal import SharedGlobalMeanRemoval, extra_channel_source_field
+        if isinstance(gmr, SharedGlobalMeanRemoval):    # one offset, from the reference field, for every listed name
+            reduced = [gmr.reference_field]
+            k_of = {n: 0 for n in gmr.field_names}
+        else:                                           # per channel: every processed input has its own
+            reduced = [n for n in gmr.field_names if n in self.in_names]
+            k_of = {n: k for k, n in enumerate(reduced)}
+        # The secondary decoder's diagnostics are unpacked by their own launch, which knows no shift (cf. the force-positive clash)
+        clash = sorted(set(k_of).intersection(self.sec_names))
+        if clash:
+            raise NotImplementedError(f"secondary-decoder diagnostics {clash} are un-shifted by global_mean_removal: use "
+                                      "Stepper.predict for this configuration")
+        if not reduced:
+            return None
+        dev, norm = self.device, step.normalizer
+        i32 = dict(dtype=torch.int32, device=dev)
+        sources = [extra_channel_source_field(n) for n in self.extra_names]
+        stat = lambda table, names: torch.stack([table[n].to(dev) for n in names]).to(torch.float32).contiguous()   # noqa: E731
+        K = len(reduced)
+        return {
+            "K": K,
+            "planes": torch.tensor([self.in_names.index(n) for n in reduced], **i32),
+            "in_idx": torch.tensor([k_of.get(n, -1) for n in self.in_names], **i32),
+            "out_idx": torch.tensor([k_of.get(n, -1) for n in self.out_names], **i32),
+            "clim": stat(norm.means, reduced),
+            "extra_idx": torch.tensor([reduced.index(n) for n in sources], **i32) if sources else None,
+            "extra_std": stat(norm.stds, sources) if sources else None,
+            "partials": torch.zeros(self.B * K * int(_lib.lib().ace_gmr_chunks(self.HW)), dtype=torch.float64, device=dev),
+            "shift": torch.zeros(self.B, K, dtype=torch.float32, device=dev),
+        }
+
     # -- one step, enqueued on the current stream
     def _enqueue_step(self, s: int, use_library_graph: bool):
         L = _lib.lib()
@@ -344,8 +399,21 @@ class RolloutEngine(WindowEngine):
     def _evaluate(self, L, stream, s: int, use_library_graph: bool, src: int, dst: int, dst_strides: torch.Tensor, secondary: bool):
         """Pack -> forward -> unpack of window position s: the inputs from the planes of the pointer table row `src`, the outputs
         into those of `dst` (and, with `secondary`, the secondary decoder's diagnostics into their output planes)."""
-        _lib.check(L.ace_pack_normalize(src, self._src_stride_addr[s], self.in_mean.data_ptr(), self.in_std.data_ptr(),
-                                        self.x.data_ptr(), self.B, len(self.in_names), self.HW, stream))
+        if self._gmr is not None:
+            # forward_transform + normalize + pack (single_module.py:651-659): the shifts of THIS evaluation's inputs - a multi-call
+            # re-evaluation with a scaled forcing has its own - reduced in one launch, applied by the pack
+            g = self._gmr
+            nin, nextra = len(self.in_names), len(self.extra_names)
+            _lib.check(L.ace_gmr_partials(src, self._src_stride_addr[s], g["planes"].data_ptr(), nin, g["partials"].data_ptr(),
+                                          self.B, g["K"], self.HW, stream))
+            _lib.check(L.ace_gmr_pack_normalize(src, self._src_stride_addr[s], self.in_mean.data_ptr(), self.in_std.data_ptr(),
+                                                g["in_idx"].data_ptr(), g["partials"].data_ptr(), g["clim"].data_ptr(),
+                                                g["extra_idx"].data_ptr() if nextra else None,
+                                                g["extra_std"].data_ptr() if nextra else None, self.x.data_ptr(),
+                                                g["shift"].data_ptr(), self.B, nin, nextra, g["K"], self.HW, stream))
+        else:
+            _lib.check(L.ace_pack_normalize(src, self._src_stride_addr[s], self.in_mean.data_ptr(), self.in_std.data_ptr(),
+                                            self.x.data_ptr(), self.B, len(self.in_names), self.HW, stream))
         if self._fill_in:
             _nan_to_zero(self.x)
         if self._conditioned:   # NoiseConditionedSFNO: fresh conditioning noise every evaluation (stochastic_sfno.py:128-146), merged

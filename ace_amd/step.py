@@ -175,9 +175,14 @@ class SingleModuleStepConfig:
         from .corrector import AtmosphereCorrectorConfig
         from .ocean import OceanConfig
         from .ocean_corrector import OceanCorrectorConfig, corrector_config_from_state
-        for field in ("global_mean_removal", "input_dropout"):
-            if getattr(self, field) is not None:
-                raise NotImplementedError(f"SingleModuleStepConfig.{field} is outside the accelerated hot path")
+        from .global_mean_removal import config_from_state as gmr_config_from_state
+        if self.input_dropout is not None:
+            raise NotImplementedError("SingleModuleStepConfig.input_dropout is outside the accelerated hot path")
+        # a configuration instance or its state (as found in a checkpoint's step config); validated as the reference does
+        # (single_module.py:101-102)
+        self.global_mean_removal = gmr_config_from_state(self.global_mean_removal)
+        if self.global_mean_removal is not None:
+            self.global_mean_removal.validate_names(self.in_names, self.out_names)
         self.secondary_decoder = SecondaryDecoderConfig.from_state(self.secondary_decoder)
         # ocean / corrector: dataclass instances or their state dicts (as found in a checkpoint's step config)
         if isinstance(self.ocean, dict):
@@ -250,16 +255,27 @@ def step_with_adjustments(input: TensorMapping, next_step_input_data: TensorMapp
                           network_calls: Callable[[TensorDict], TensorDict], normalizer: StandardNormalizer,
                           residual_prediction: bool, prognostic_names: List[str],
                           prescribed_prognostic_names: Optional[List[str]] = None,
-                          stepper_state=None, corrector=None, ocean=None) -> StepOutput:
-    """single_module.py:595-733 with global_mean_removal=None: normalise, network, (residual), denormalise, corrector,
-    ocean, prescribed prognostics - in the reference's order (single_module.py:669-716)."""
+                          stepper_state=None, corrector=None, ocean=None, global_mean_removal=None,
+                          data_mask=None) -> StepOutput:
+    """single_module.py:595-733: (global-mean removal), normalise, network, (residual), denormalise, (global means restored),
+    corrector, ocean, prescribed prognostics - in the reference's order (single_module.py:650-716).  The corrector, the ocean and
+    the prescribed prognostics see the unshifted input and the physical output."""
     if prescribed_prognostic_names is None:
         prescribed_prognostic_names = []
-    input_norm = normalizer.normalize(input)
+    gmr_state = None
+    if global_mean_removal is not None:
+        network_input, gmr_state = global_mean_removal.forward_transform(input, data_mask)
+        input_norm = normalizer.normalize(network_input)
+        # the synthetic channels are produced in normalised space: merged after the normaliser (single_module.py:656-659)
+        input_norm = {**input_norm, **global_mean_removal.extras_normalized(gmr_state)}
+    else:
+        input_norm = normalizer.normalize(input)
     output_norm = network_calls(input_norm)
     if residual_prediction:
         output_norm = {**output_norm, **{k: input_norm[k] + output_norm[k] for k in prognostic_names}}
     output = normalizer.denormalize(output_norm)
+    if global_mean_removal is not None:
+        output = global_mean_removal.inverse_transform(output, gmr_state)
     if corrector is not None:
         cstate = stepper_state.corrector_state if stepper_state is not None else None
         output, cstate = corrector(input, output, next_step_input_data, cstate)
@@ -284,9 +300,13 @@ class SingleModuleStep:
 
     def __init__(self, config: SingleModuleStepConfig, dataset_info, normalizer: StandardNormalizer,
                  init_weights: Callable[[List[nn.Module]], None] = lambda _m: None, device=None):
-        n_in_channels = len(config.in_names)
+        # global-mean removal (single_module.py:287-298): its synthetic channels are packed after the in_names
+        self._global_mean_removal = (config.global_mean_removal.build(normalizer, list(config.in_names))
+                                     if config.global_mean_removal is not None else None)
+        extra_names = self._global_mean_removal.extra_channel_names if self._global_mean_removal is not None else []
+        n_in_channels = len(config.in_names) + len(extra_names)
         n_out_channels = len(config.out_names)
-        self.in_packer = Packer(list(config.in_names))
+        self.in_packer = Packer(list(config.in_names) + extra_names)
         self.out_packer = Packer(list(config.out_names))
         self._normalizer = normalizer
         module = config.builder.build(n_in_channels=n_in_channels, n_out_channels=n_out_channels,
@@ -314,6 +334,11 @@ class SingleModuleStep:
     @property
     def normalizer(self) -> StandardNormalizer:
         return self._normalizer
+
+    @property
+    def global_mean_removal(self):
+        """The step's ``GlobalMeanRemoval`` transform, None without the option."""
+        return self._global_mean_removal
 
     @property
     def input_names(self) -> List[str]:
@@ -359,6 +384,7 @@ class SingleModuleStep:
             prognostic_names=self.prognostic_names,
             prescribed_prognostic_names=self._config.prescribed_prognostic_names,
             stepper_state=args.stepper_state, corrector=self._corrector, ocean=self._ocean,
+            global_mean_removal=self._global_mean_removal, data_mask=args.data_mask,
         )
 
     def get_state(self):

@@ -321,6 +321,58 @@ int ace_unpack_denormalize(const float* src, const float* mean, const float* std
                            const long* strides, int batch, int nch, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Global-mean removal (fme/core/step/global_mean_removal.py, applied by step_with_adjustments,
+ * fme/core/step/single_module.py:650-668) folded into the stepper glue above.  Tables as there: DEVICE pointer tables, per-sample
+ * strides in floats, planes of hw contiguous fp32 pixels at any 4-byte alignment.  16-byte accesses only on a (plane, sample)
+ * with hw % 4 == 0 and 16-byte aligned addresses, chosen once per workgroup.  Stream-ordered; no allocation, host
+ * synchronisation or atomics; no workgroup waits for another; legal inside hipGraph capture.  Errors through ace_last_error.
+ *
+ * K reduced planes (1 for "shared": the reference field; the processed fields for "per_channel"), named by plane_idx: DEVICE int
+ * [K], indices into the nsrc entries of srcs / strides.  An index outside [0, nsrc) is not read and makes that mean NaN.
+ *
+ * THE REDUCTION ORDER.  C = ace_gmr_chunks(hw) chunks of 4096 pixels (the last one shorter); partials: DEVICE fp64 [batch][K][C].
+ *   chunk c of plane x, pixels x[4096 c + i], i = 0 .. n - 1 (n = min(4096, hw - 4096 c)); a pixel past n counts as +0.0:
+ *     a[t][q] = sum over r = 0, 1, 2, 3 in this order of (double) x[4096 c + 4 (256 r + t) + q]    t = 0 .. 255, q = 0 .. 3,
+ *               starting from +0.0
+ *     s[t]    = (a[t][0] + a[t][1]) + (a[t][2] + a[t][3])
+ *     per group w of 64 consecutive t (lane l = t - 64 w): for off = 32, 16, 8, 4, 2, 1: s[l] = s[l] + s[l + off] for l < off
+ *     partials[b][k][c] = ((s[0] + s[64]) + s[128]) + s[192]
+ *   every operation an fp64 addition, rounded to nearest.  The 16-byte and the 4-byte load paths give the same bits.
+ *   sample_mean[b][k] = (float) ((...((partials[b][k][0] + partials[b][k][1]) + ...) + partials[b][k][C - 1]) / (double) hw)
+ *                       (chunk order; one fp64 division, one rounding to fp32) - replaces t.mean(dim=...) of
+ *                       global_mean_removal.py:230 / :315, which is an fp32 sum in torch's order
+ *   shift[b][k]       = clim_mean[k] - sample_mean[b][k]      fp32 subtraction (global_mean_removal.py:231 / :316)
+ * Every entry below that needs a mean or a shift forms it this way from the partials: there is no other order.
+ *
+ *   gmr_partials:           the partials of the K planes (replaces the reduction of global_mean_removal.py:230 / :315)
+ *   gmr_sample_means:       gmr_partials, then means[b][k] = sample_mean[b][k] (DEVICE fp32 [batch][K])
+ *   gmr_pack_normalize:     ace_pack_normalize over nin channels with shift_idx: DEVICE int [nin], the k of channel j or -1:
+ *                             k >= 0: dst[b][j][p] = ((src + shift[b][k]) - mean[j]) / std[j]   three roundings
+ *                                     (global_mean_removal.py:247 / :322, then normalizer.py:221)
+ *                             else:   dst[b][j][p] = (src - mean[j]) / std[j]                    as ace_pack_normalize
+ *                           then nextra synthetic channels (extra_idx: DEVICE int [nextra], extra_std: DEVICE fp32 [nextra]):
+ *                             dst[b][nin + e][p] = (-shift[b][extra_idx[e]]) / extra_std[e]
+ *                                     (global_mean_removal.py:236-238 / :329-331; single_module.py:659)
+ *                           dst is [batch][nin + nextra][hw]; shift: DEVICE fp32 [batch][K], written here (1 <= K <= nin)
+ *   gmr_unpack_denormalize: ace_unpack_denormalize with shift_idx: DEVICE int [nch], the k of output channel j or -1:
+ *                             k >= 0: dsts[j][...] = (src * std[j] + mean[j]) - shift[b][k]     the product rounded before the
+ *                                     sum (normalizer.py:236), then one fp32 subtraction (global_mean_removal.py:265 / :347)
+ *                             else:   as ace_unpack_denormalize
+ *                           shift: what gmr_pack_normalize wrote.
+ * ------------------------------------------------------------------------------------------ */
+long ace_gmr_chunks(long hw);
+int ace_gmr_partials(const float* const* srcs, const long* strides, const int* plane_idx, int nsrc, double* partials, int batch,
+                     int K, long hw, void* stream);
+int ace_gmr_sample_means(const float* const* srcs, const long* strides, const int* plane_idx, int nsrc, double* partials,
+                         float* means, int batch, int K, long hw, void* stream);
+int ace_gmr_pack_normalize(const float* const* srcs, const long* strides, const float* mean, const float* std_,
+                           const int* shift_idx, const double* partials, const float* clim_mean, const int* extra_idx,
+                           const float* extra_std, float* dst, float* shift, int batch, int nin, int nextra, int K, long hw,
+                           void* stream);
+int ace_gmr_unpack_denormalize(const float* src, const float* mean, const float* std_, float* const* dsts, const long* strides,
+                               const int* shift_idx, const float* shift, int batch, int nch, int K, long hw, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Static spatial masking (fme/core/spatial_masking.py:98-150): data[name] = fill where round(mask) == mask_value, per plane.
  * hits: DEVICE uint8 [nmask][hw], one plane per distinct 2-D mask (broadcast over the batch), nonzero where the reference's
  * `torch.round(mask).to(torch.int64) == mask_value` holds - computed by the caller with exactly those torch ops, so the kernels
