@@ -25,6 +25,7 @@ from .healpix import CapturedHEALPixForward, HEALPixUNet, HEALPixUNetBuilder  # 
 from .samudra import CapturedSamudraForward, Samudra, SamudraBuilder  # noqa: F401
 from .corrector import AtmosphereCorrectorConfig  # noqa: F401
 from .ocean import OceanConfig  # noqa: F401
+from .ice_corrector import FusedIceCorrector, IceBudgetCorrectionConfig, IceCorrector, IceCorrectorConfig  # noqa: F401
 from .derived_variables import AtmosphericDeriveFn, compute_derived_quantities  # noqa: F401
 from .ocean_derived_variables import OceanDeriveFn, compute_ocean_derived_quantities  # noqa: F401
 from .timeaxis import TimeAxis  # noqa: F401

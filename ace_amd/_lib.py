@@ -78,6 +78,21 @@ class OceanFields(ctypes.Structure):
                 ("hfgeou", Plane)]
 
 
+# ---- sea-ice budget corrector (ace_ice_budget_*): struct ace_ice_var / ace_ice_fields
+ICE_MAX_VARS, ICE_FLAG_BYTES = 3, 64
+
+
+class IceVar(ctypes.Structure):
+    """struct ace_ice_var"""
+    _fields_ = [("old_mass", Plane), ("source", Plane), ("sink", Plane), ("transport", Plane), ("mass", Plane), ("area_mode", c_int),
+                ("masked", c_int)]
+
+
+class IceFields(ctypes.Structure):
+    """struct ace_ice_fields"""
+    _fields_ = [("var", IceVar * ICE_MAX_VARS), ("nvars", c_int)]
+
+
 # ---- the ocean's derived variables (ace_ocean_derive_window): struct ace_ocean_derive_field / _level / _desc
 OCEAN_DERIVE_OUTPUTS = ("ocean_heat_content", "ocean_heat_content_tendency", "implied_tendency_of_ocean_heat_content_due_to_advection",
                         "net_energy_flux_into_ocean_column", "sea_ice_fraction", "HI", "hfds")      # bit i of `want`, slot i of `out`
@@ -229,6 +244,11 @@ SIGNATURES = {
     "ace_ocean_phys_launches": (c_int, [c_void_p, POINTER(c_long), POINTER(c_long)]),
     "ace_ocean_derive_last_error": (c_char_p, []),
     "ace_ocean_derive_window": (c_int, [POINTER(OceanDeriveDesc), c_void_p]),
+    "ace_ice_budget_last_error": (c_char_p, []),
+    "ace_ice_budget_scratch_bytes": (c_long, [c_int, c_long]),
+    # fields, timestep, batch, H, W, scratch, stream
+    "ace_ice_budget_apply": (c_int, [POINTER(IceFields), c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ace_ice_budget_launches": (c_int, [POINTER(c_long), POINTER(c_long), POINTER(c_long)]),
     "ace_mask_last_error": (c_char_p, []),
     # srcs, src_strides, dsts, dst_strides, mask_idx, hits, nmask, fill, nplanes, batch, hw, stream
     "ace_mask_planes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_long,

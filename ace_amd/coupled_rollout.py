@@ -209,6 +209,9 @@ def check_supported(stepper: CoupledStepper, n_coupled_steps: int, graph: Option
     for realm, component in (("atmosphere", atmosphere), ("ocean", ocean)):
         if getattr(component._step_obj, "global_mean_removal", None) is not None:
             raise _refuse(f"global_mean_removal on the {realm} component is not supported")
+        from .ice_corrector import IceCorrector
+        if isinstance(component._step_obj._corrector, IceCorrector):
+            raise _refuse(f"a sea-ice corrector (ice_corrector) on the {realm} component is not supported")
     if not hasattr(net, "_ensure_native"):
         raise _refuse(f"the atmosphere's module is a {type(net).__name__}, not of the SFNO family")
     if hasattr(net, "draw_noise"):

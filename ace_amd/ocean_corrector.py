@@ -406,11 +406,15 @@ class OceanCorrectorConfig:
 
 
 def corrector_config_from_state(state):
-    """the step config's ``corrector``: an AtmosphereCorrectorConfig / OceanCorrectorConfig, a CorrectorSelector state
-    ({"type", "config"}) or a bare atmosphere corrector state (what every checkpoint without a selector carries)."""
+    """the step config's ``corrector``: an AtmosphereCorrectorConfig / OceanCorrectorConfig / IceCorrectorConfig, a
+    CorrectorSelector state ({"type", "config"}) or a bare atmosphere corrector state (what every checkpoint without a selector
+    carries)."""
     from .corrector import AtmosphereCorrectorConfig
     if isinstance(state, Mapping) and state.get("type") == "ocean_corrector" and "config" in state:
         return OceanCorrectorConfig.from_state(state)
+    if isinstance(state, Mapping) and state.get("type") == "ice_corrector" and "config" in state:
+        from .ice_corrector import IceCorrectorConfig
+        return IceCorrectorConfig.from_state(state)
     return AtmosphereCorrectorConfig.from_state(state)
 
 

@@ -10,7 +10,8 @@ Per step s the engine enqueues, in the order of ``Stepper.step`` and ``step_with
                               `graph=None`: eager launches)
   3. ace_unpack_denormalize   network output -> out[name][:, s] (residual_prediction adds the normalised prognostic inputs first)
   4. ace_ocean_phys_*         the ocean corrector (O1, plus O2 with the heat-content budget), in place on out[:, s], reading the
-                              masked input and the masked next-step forcing
+                              masked input and the masked next-step forcing; with a sea-ice corrector ace_ice_budget_apply instead
+                              (its flags stay on the device: no readback, so the step is capturable)
   5. ace_mask_planes          the provider's output masker (NaN where the mask is 0), in place on out[:, s], which is also the
                               state of step s + 1
 Every handle, hit plane and workspace is made at construction or in a warm-up outside capture; nothing is allocated and the host
@@ -55,6 +56,7 @@ class OceanRolloutEngine(WindowEngine):
     def check_supported(stepper: Stepper):
         """The refusals that need no device, raised before any device work (the constructor's first act).  Returns the stepper's
         (input masker, output masker), each None when it is no static spatial masking."""
+        from .ice_corrector import IceCorrector
         from .ocean_corrector import OceanCorrector
         from .samudra import Samudra
         step = stepper._step_obj
@@ -78,8 +80,8 @@ class OceanRolloutEngine(WindowEngine):
         if list(cfg.prescribed_prognostic_names):
             raise _refuse("prescribed prognostic names are not supported")
         corrector = step._corrector
-        if corrector is not None and not isinstance(corrector, OceanCorrector):
-            raise _refuse(f"a {type(corrector).__name__} is not an ocean corrector")
+        if corrector is not None and not isinstance(corrector, (OceanCorrector, IceCorrector)):
+            raise _refuse(f"a {type(corrector).__name__} is not an ocean corrector (nor a sea-ice corrector)")
         in_mask = stepper._input_process_func if isinstance(stepper._input_process_func, StaticSpatialMasking) else None
         out_mask = stepper._output_masking if isinstance(stepper._output_masking, StaticSpatialMasking) else None
         for m in (in_mask, out_mask):
@@ -110,16 +112,18 @@ class OceanRolloutEngine(WindowEngine):
         self._fused_corrector = None
         stage_in, stage_next = [], []
         if corrector is not None and corrector.corrections:
+            from .ice_corrector import FusedIceCorrector, IceCorrector
             from .ocean_phys import FusedOceanCorrector
             diag = [n for n in self.out_names if n not in self.in_names]
             inp = _Reads({**{n: self.in_plane(n, 0) for n in self.in_names}, **{n: self.out_plane(n, 0) for n in diag}})
             nxt = _Reads({n: self.next_plane(n, 0) for n in self.forcing_names})
             gen = {n: self.out_plane(n, 0) for n in self.out_names}
             try:
-                fc = FusedOceanCorrector(corrector, B, (H, W), dev)
+                # both fused handles have fields(inp, gen, nxt) -> a struct of planes and apply(struct, stream)
+                fc = (FusedIceCorrector if isinstance(corrector, IceCorrector) else FusedOceanCorrector)(corrector, B, (H, W), dev)
                 fc.fields(inp, gen, nxt)
             except (ValueError, KeyError, TypeError, NotImplementedError) as e:
-                raise _refuse(f"the ocean corrector configuration is not supported by the fused corrector ({e})") from e
+                raise _refuse(f"the {type(corrector).__name__} configuration is not supported by the fused corrector ({e})") from e
             read_diag = sorted(inp.read.intersection(diag))
             if read_diag:
                 raise _refuse(f"the ocean corrector reads the step outputs {read_diag} from the input, which only a step after the "

@@ -217,7 +217,11 @@ class RolloutEngine(WindowEngine):
         step = stepper._step_obj
         if getattr(step, "secondary_decoder", None) is not None and graph == "window":
             raise NotImplementedError("graph='window' with a secondary decoder: its module call is not captured; use graph='step'")
+        from .ice_corrector import IceCorrector
         from .ocean_corrector import OceanCorrector
+        if isinstance(step._corrector, IceCorrector):
+            raise NotImplementedError("RolloutEngine: a stepper with a sea-ice corrector (ice_corrector) runs through "
+                                      "Stepper.predict (or, with a Samudra module, OceanRolloutEngine)")
         if isinstance(step._corrector, OceanCorrector):
             raise NotImplementedError("RolloutEngine: a stepper with an ocean corrector (ocean_corrector) runs through "
                                       "Stepper.predict; the fused post-step physics of the engine is the atmosphere corrector's")

@@ -174,6 +174,7 @@ class SingleModuleStepConfig:
     def __post_init__(self):
         from .corrector import AtmosphereCorrectorConfig
         from .ocean import OceanConfig
+        from .ice_corrector import IceCorrectorConfig
         from .ocean_corrector import OceanCorrectorConfig, corrector_config_from_state
         from .global_mean_removal import config_from_state as gmr_config_from_state
         if self.input_dropout is not None:
@@ -189,9 +190,9 @@ class SingleModuleStepConfig:
             self.ocean = OceanConfig.from_state(self.ocean)
         if self.ocean is not None and not isinstance(self.ocean, OceanConfig):
             raise NotImplementedError("SingleModuleStepConfig.ocean must be an OceanConfig (prescribed SST or slab ocean) or its state")
-        if not isinstance(self.corrector, (AtmosphereCorrectorConfig, OceanCorrectorConfig, dict, type(None))):
+        if not isinstance(self.corrector, (AtmosphereCorrectorConfig, OceanCorrectorConfig, IceCorrectorConfig, dict, type(None))):
             raise NotImplementedError("SingleModuleStepConfig.corrector must be an AtmosphereCorrectorConfig, an "
-                                      "OceanCorrectorConfig or its state")
+                                      "OceanCorrectorConfig, an IceCorrectorConfig or its state")
         if self.corrector is None or isinstance(self.corrector, dict):
             self.corrector = corrector_config_from_state(self.corrector)
         if self.include_channel_mask_inputs:

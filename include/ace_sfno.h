@@ -1133,6 +1133,67 @@ const char* ace_ocean_derive_last_error(void);
 /* `desc` is a HOST struct of device pointers (copied into the kernel arguments). */
 int ace_ocean_derive_window(const ace_ocean_derive_desc* desc, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sea-ice budget corrector (fme/core/corrector/ice.py, "ice_corrector": IceBudgetCorrectionConfig).  For each of up to three
+ * variables v, in the order given (the reference's: simass, the concentration, sisnmass), the three budget terms of the step's
+ * output (source, sink, transport: planes corrected in place) are rebalanced so that the new mass old + dt * (s + k + t) is not
+ * negative, not above 1 (area_mode) and zero where there is no ice (masked), and the output's prognostic plane is overwritten
+ * with that mass.  `old` is the input's plane of the variable and is only read.
+ *
+ * Per pixel, everything in fp64, every operation rounded on its own (no fused multiply-add), with dt = timestep:
+ *   s = (double) source * dt, k = (double) sink * dt, t = (double) transport * dt, o = (double) old
+ *   new(s, k, t) = o + ((s + k) + t)
+ *   rebalance(s, k, t, m, mass, sign), m the pixel's stage mask, mass = 0 where m is false:
+ *       nz_x = |x| > 0 for x in s, k, t;  n = nz_s + nz_k + nz_t;  share = (m and n > 0) ? mass / max(n, 1) : 0
+ *       r_x = (m and nz_x) ? share : 0;  if (m and n == 0) r_t = mass
+ *       tmp = k + sign * r_k;  ko = tmp > 0 ? tmp : 0;  r_k = r_k - ko;  r_t = r_t + ko
+ *       tmp = s + sign * r_s;  so = tmp < 0 ? tmp : 0;  r_s = r_s - sign * so;  r_t = r_t + sign * so
+ *       s = s + sign * r_s;  k = k + sign * r_k;  t = t + sign * r_t
+ *   stage 1            m = new < 0,                      mass = -new,     sign = +1
+ *   stage 2 (area_mode) m = new > 1,                     mass = new - 1,  sign = -1
+ *   stage 3 (masked)    m = (ice mass == 0) and new > 0, mass = new,      sign = -1
+ *   b_x = x / dt (a division);  source, sink, transport = (float) b_x;  prognostic = (float) (o + dt * ((b_s + b_k) + b_t))
+ * Comparisons are IEEE: a NaN pixel enters no mask and comes out NaN.  A stage is run for EVERY pixel of the (batch, H, W)
+ * tensor - where m is false it still moves a positive sink and a negative source into the transport - if and only if m is
+ * true at ANY pixel of the tensor after the stages before it, and is skipped for every pixel otherwise: the reference's
+ * `if torch.any(mask)`.  The "ice mass" of stage 3 is the fp64 mass of variable 0 as corrected by this call, BEFORE it is
+ * rounded to fp32 (a mass that rounds to 0.0f is still ice; NaN is not zero); masked[0] must be 0.
+ *
+ * Contract.  A call is stream-ordered and makes no host readback, no synchronisation and no allocation: at most 2 * nvars kernel
+ * launches (per variable: a flags pass that ORs, over the tensor, each pixel's stage masks under every hypothesis about the
+ * earlier stages - 7 bits - and an apply pass that resolves the path from them and recomputes its pixel once along it) plus
+ * one clearing of the flag words on the stream.  An OR is order-independent: two calls on the same inputs give the same bits,
+ * and so do 16-byte and 4-byte plane alignments.  `scratch` is caller-owned device memory of ace_ice_budget_scratch_bytes(batch,
+ * hw) bytes, 16-byte aligned, that must not be shared by calls in flight on different streams: flag words, then one byte per
+ * pixel (the fp64 "ice mass == 0" predicate of variable 0).  Every plane holds `batch` samples of H * W contiguous floats.
+ *
+ * Refused (ACE_ERR_INVALID before any launch, the reason behind ace_ice_budget_last_error, nothing written): NULL fields or
+ * scratch (with nvars > 0), nvars outside 0 .. ACE_ICE_MAX_VARS, an absent plane, masked[0] set, a timestep that is not a
+ * positive finite number, batch outside 1 .. 65535, H or W < 1, a scratch that is not 16-byte aligned.  nvars == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------ */
+#define ACE_ICE_MAX_VARS 3
+#define ACE_ICE_FLAG_BYTES 64                  /* head of the scratch: one 32-bit flag word per variable, padded */
+
+typedef struct ace_ice_var {
+    ace_phys_plane old_mass;                   /* input of the step (read only) */
+    ace_phys_plane source, sink, transport;    /* output of the step, corrected in place */
+    ace_phys_plane mass;                       /* output of the step, overwritten */
+    int area_mode;                             /* a concentration: capped at 1 */
+    int masked;                                /* zero where variable 0's corrected mass is zero */
+} ace_ice_var;
+
+typedef struct ace_ice_fields {
+    ace_ice_var var[ACE_ICE_MAX_VARS];
+    int nvars;
+} ace_ice_fields;
+
+const char* ace_ice_budget_last_error(void);
+long ace_ice_budget_scratch_bytes(int batch, long hw);
+/* `fields` is a HOST struct of device planes (copied into the kernel arguments). */
+int ace_ice_budget_apply(const ace_ice_fields* fields, double timestep, int batch, int H, int W, void* scratch, void* stream);
+/* Launch counter of this process: flags passes, apply passes and flag clearings enqueued so far (any may be NULL). */
+int ace_ice_budget_launches(long* flags, long* apply, long* clears);
+
 #ifdef __cplusplus
 }
 #endif
