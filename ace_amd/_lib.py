@@ -149,6 +149,18 @@ class DftStageDesc(ctypes.Structure):
                 ("ride_dst", c_void_p), ("ride_dst_alone", c_void_p)]
 
 
+class DhconvRoute(ctypes.Structure):
+    """struct ace_dhconv_route"""
+    _fields_ = [("storage", c_int), ("kspan", c_int), ("units", c_int * 3), ("max_chunks", c_int), ("units_per_xcd", c_int)]
+
+
+class DhconvDesc(ctypes.Structure):
+    """struct ace_dhconv_desc"""
+    _fields_ = [("coeffs", c_void_p), ("weight", c_void_p), ("out", c_void_p), ("out_absmax", c_void_p),
+                ("n", c_int), ("c", c_int), ("L", c_int), ("Mm", c_int), ("groups", c_int), ("storage", c_int),
+                ("e_fill", c_float)]
+
+
 # every symbol include/ace_sfno.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ace_last_error": (c_char_p, []),
@@ -168,6 +180,7 @@ SIGNATURES = {
     "ace_dft_stage": (c_int, [c_void_p, POINTER(DftStageDesc), POINTER(DftRoute), c_void_p]),
     "ace_mlp_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_void_p]),
     "ace_dhconv_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ace_dhconv_strip_op": (c_int, [POINTER(DhconvDesc), POINTER(DhconvRoute), c_void_p]),
     "ace_instance_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_long, c_void_p]),
     "ace_conditional_layer_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
                                            c_int, c_int, c_int, c_long, c_void_p]),

@@ -869,43 +869,104 @@ static hipError_t upload_dhconv_units(int L, int Mrows, int trimul, int C, DevBu
 // kernel the network uses (dhconv_strip.hip: compensated fp16, filter streamed once).  Operator-level entry for tests and
 // micro-benchmarks: converts to the internal layouts, prepares the filter planes on every call and synchronises.
 extern "C" int ace_dhconv_f16x3(const float* coeffs, const float* weight, float* out, int n, int c, int L, int Mm, void* stream) {
-    if (!coeffs || !weight || !out || n <= 0 || c <= 0 || L <= 0 || Mm <= 0) return fail(ACE_ERR_INVALID, "ace_dhconv_f16x3: bad argument");
-    if (c % 128 != 0) return fail(ACE_ERR_INVALID, "ace_dhconv_f16x3: needs channels % 128 == 0");
+    ace_dhconv_desc d = {};
+    d.coeffs = coeffs; d.weight = weight; d.out = out;
+    d.n = n; d.c = c; d.L = L; d.Mm = Mm; d.groups = 1; d.storage = 0;
+    return ace_dhconv_strip_op(&d, nullptr, stream);
+}
+
+// The same contraction in every form dhconv_strip.hip has: dense or block-diagonal filter, the latter as dense planes (zero blocks
+// skipped) or as the diagonal blocks alone; optional range maximum of the output.  The launch is the network's (dhconv_strip_args):
+// the same planes, slots, work list and kernel - only the operands are prepared here, on every call.
+extern "C" int ace_dhconv_strip_op(const ace_dhconv_desc* d, ace_dhconv_route* route, void* stream) {
+    if (!d || !d->coeffs || !d->weight || !d->out || d->n <= 0 || d->c <= 0 || d->L <= 0 || d->Mm <= 0 || std::isnan(d->e_fill))
+        return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: bad argument");
+    const int n = d->n, c = d->c, L = d->L, Mm = d->Mm, G = d->groups;
+    if (c % 128 != 0) return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: needs channels % 128 == 0");
+    if (G < 1 || c % G != 0) return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: groups must divide channels");
+    if (d->storage != 0 && d->storage != 1) return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: storage is 0 (dense planes) or 1 (diagonal blocks)");
+    const bool native = d->storage == 1;
+    if (native && !dhconv_native_groups_ok(c, G))
+        return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: diagonal-block storage needs groups > 1 and channels / groups in {32, 64, 128} or a multiple of 128");
+    if ((double)L * Mm * 2.0 * n * c >= 2147483647.0 || (double)L * 2.0 * c * c >= 2147483647.0)
+        return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: a test entry for operands below 2^31 elements");
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const int cg = c / G;
     const long N2 = 2L * n * c;
     const size_t spec = (size_t)L * Mm * N2;
-    DevBuf D, Dp, E, Wh, Wl, slots;
+    const long wnumel = native || G > 1 ? (long)G * L * cg * cg * 2 : (long)c * c * L * 2;   // the caller's tensor
+    DevBuf D, Dp, E, Wd, Wh, Wl, slots;
     HIP_TRY(D.alloc(spec, true));
     HIP_TRY(Dp.alloc(spec, true));          // hi | lo planes: two halves per element = one float
-    HIP_TRY(E.alloc(spec, true));           // rows m > l are never written: they stay zero
+    HIP_TRY(E.alloc(spec, d->e_fill == 0.f));   // rows m > l are never written: they keep e_fill
+    if (d->e_fill != 0.f) {
+        unsigned bits;
+        std::memcpy(&bits, &d->e_fill, 4);
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(E.p), (int)bits, spec, s));
+    }
     HIP_TRY(slots.alloc(2 * AMAX_SHARDS, true));
-    const size_t wh = (size_t)L * 2 * c * c;
+    const int kstore = native ? cg : c;
+    const size_t wh = (size_t)L * 2 * kstore * c;
     HIP_TRY(Wh.alloc((wh + 1) / 2, false));
     HIP_TRY(Wl.alloc((wh + 1) / 2, false));
     unsigned* dslot = reinterpret_cast<unsigned*>(slots.p);
     unsigned* wslot = dslot + AMAX_SHARDS;
-    HIP_TRY(launch_ref_to_spec(coeffs, D.p, n, c, L, Mm, s));
+    HIP_TRY(launch_ref_to_spec(d->coeffs, D.p, n, c, L, Mm, s));
     HIP_TRY(launch_absmax(D.p, (long)spec, dslot, s));
-    HIP_TRY(launch_absmax(weight, (long)c * c * L * 2, wslot, s));
+    HIP_TRY(launch_absmax(d->weight, wnumel, wslot, s));
     float dmx = 0.f, wmx = 0.f;
     ACE_TRY(read_range_slot(dslot, s, &dmx));
     ACE_TRY(read_range_slot(wslot, s, &wmx));
-    const float dscale = pow2_scale(dmx, 12), wscale = pow2_scale(wmx, 10);   // the kernel derives 2^(12 - exponent) from the slot itself
+    // The planes are scaled by 2^e and the kernel undoes 2^e from the slot: both from range_exponent().  (Until the range cases of
+    // tests/test_gpu_dhconv_strip.py this line took pow2_scale(dmx, 12), which has no clamp where the kernel's exponent has one: beyond
+    // it the result was off by a power of two.)  Where the clamp acts the planes do not hold max |coeffs| in [2^11, 2^12) and the
+    // low end loses bits the 2e-6 bar needs: refused, not computed.
+    bool clamped = false;
+    const float dscale = std::ldexp(1.0f, range_exponent(dmx, &clamped)), wscale = pow2_scale(wmx, 10);
+    if (clamped) return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: max |coeffs| outside [2^-89, 2^112): the planes' power-of-two scale is clamped there");
     HIP_TRY(launch_split_f16(D.p, N2, Dp.p, reinterpret_cast<_Float16*>(Dp.p) + spec, N2, (long)L * Mm, (int)N2, dscale, s));
-    HIP_TRY(launch_pack_dhconv_f16c(weight, Wh.p, Wl.p, c, c, L, wscale, s));
+    if (native) {
+        HIP_TRY(launch_pack_dhconv_f16g(d->weight, Wh.p, Wl.p, c, G, L, wscale, s));
+    } else if (G > 1) {
+        HIP_TRY(Wd.alloc((size_t)c * c * L * 2, false));
+        HIP_TRY(launch_csfno_weight_to_dense(d->weight, Wd.p, c, G, L, s));
+        HIP_TRY(launch_pack_dhconv_f16c(Wd.p, Wh.p, Wl.p, c, c, L, wscale, s));
+    } else {
+        HIP_TRY(launch_pack_dhconv_f16c(d->weight, Wh.p, Wl.p, c, c, L, wscale, s));
+    }
     DhconvStripArgs ds;
     ds.Dhi = reinterpret_cast<const _Float16*>(Dp.p); ds.Dlo = ds.Dhi + spec;
     ds.sD = (long)Mm * N2; ds.amax = dslot;
     ds.Whi = reinterpret_cast<const _Float16*>(Wh.p); ds.Wlo = reinterpret_cast<const _Float16*>(Wl.p);
-    ds.sW = (long)2 * c * c; ds.bscale = wscale;
-    ds.E = E.p; ds.sE = (long)Mm * N2;
+    ds.sW = (long)2 * kstore * c; ds.bscale = wscale;
+    ds.E = E.p; ds.sE = (long)Mm * N2; ds.omax = d->out_absmax;
     ds.C = c; ds.L = L; ds.Mrows = Mm * n; ds.trimul = n;
+    ds.groups = G;
+    if (native) ds.kstore = kstore;
+    std::vector<int> u;
+    ds.units_per_xcd = dhconv_build_units(L, Mm * n, n, c, u);
     DevBuf units;
-    HIP_TRY(upload_dhconv_units(L, Mm * n, n, c, units, &ds.units_per_xcd));
+    HIP_TRY(units.alloc(u.size(), false));
+    HIP_TRY(hipMemcpy(units.p, u.data(), u.size() * sizeof(int), hipMemcpyHostToDevice));
     ds.units = reinterpret_cast<const int*>(units.p);
-    if (!dhconv_strip_eligible(ds)) return fail(ACE_ERR_INVALID, "ace_dhconv_f16x3: shape not covered by dhconv_strip.hip");
+    if (!dhconv_strip_eligible(ds)) return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: shape not covered by dhconv_strip.hip");
+    if (d->out_absmax) HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
     HIP_TRY(launch_dhconv_strip(ds, s));
-    HIP_TRY(launch_spec_to_ref(E.p, out, n, c, L, Mm, s));
+    HIP_TRY(launch_spec_to_ref(E.p, d->out, n, c, L, Mm, s, true));   // entries with m > l: what E held, i.e. e_fill unless the kernel stored there
+    if (route) {
+        const bool skip = G > 1 && (cg % 128 == 0 || 128 % cg == 0);
+        *route = ace_dhconv_route{};
+        route->storage = native ? 1 : 0;
+        route->kspan = skip ? std::max(cg, 128) : c;
+        route->units_per_xcd = ds.units_per_xcd;
+        std::map<std::pair<int, int>, int> chunks;
+        for (size_t k = 0; k + 3 < u.size(); k += 4) {
+            const int rows = u[k + 3];
+            if (rows <= 0) continue;
+            ++route->units[(rows + 31) / 32 - 1];
+            route->max_chunks = std::max(route->max_chunks, ++chunks[{u[k], u[k + 1]}]);
+        }
+    }
     HIP_TRY(hipStreamSynchronize(s));
     return ACE_OK;
 }

@@ -366,7 +366,7 @@ hipError_t launch_cond_layer_norm(const float* x, const float* noise, const floa
                                   int J, long HW, hipStream_t s, unsigned* omax = nullptr);
 
 // layout converters between the internal spectral layout and the reference's (n, L, M) complex64
-hipError_t launch_spec_to_ref(const float* D, float* out, int Bt, int C, int L, int Mm, hipStream_t s);
+hipError_t launch_spec_to_ref(const float* D, float* out, int Bt, int C, int L, int Mm, hipStream_t s, bool whole = false);   // whole: entries with m > l copied, not zeroed
 // triangular_consumer: the scratch is read by an exactly triangular kernel only (entries with m > l may stay unwritten)
 hipError_t launch_ref_to_spec(const float* in, float* E, int Bt, int C, int L, int Mm, hipStream_t s, unsigned* omax = nullptr, bool triangular_consumer = false);
 

@@ -2939,7 +2939,8 @@ hipError_t launch_instnorm_stats(const float* x, const float* gamma, const float
 // reference's [b][c][r][ri] (complex64, r fastest): a 32 x 32 (r, c) tile is read and written in 128 / 256-byte runs (the
 // first version walked one side with a stride of 2 C Bt floats per lane: the reference's own `sht` benchmark, 1024 fields,
 // spent 1.1 of its 1.5 ms here).  TO_REF: entries with m > l are written as zeros without reading the internal buffer (the
-// triangular Legendre stage never writes them), so the standalone transform needs no memset of its scratch.
+// triangular Legendre stage never writes them), so the standalone transform needs no memset of its scratch; `tri` > 0: they are copied
+// like the others (ace_dhconv_strip_op: what the scratch held beyond a degree's rows is part of what its tests look at).
 // omax (from-reference direction, optional): atomicMax of the bit pattern of max |value| over the launch - the range of the
 // coefficients for the f16x3 Legendre stage, taken here instead of in a pass of its own over the converted tensor.
 template <bool TO_REF>
@@ -2956,7 +2957,7 @@ __global__ __launch_bounds__(256) void spec_layout_kernel(const float* __restric
             const long r = r0 + ty + 8 * k;
             const int c = c0 + tx;
             float re = 0.f, im = 0.f;
-            if (r < R && c < C && (int)(r % Mm) <= (int)(r / Mm)) {
+            if (r < R && c < C && (tri > 0 || (int)(r % Mm) <= (int)(r / Mm))) {
                 const float* p = src + (r * Bt + b) * 2 * C + c;
                 re = p[0];
                 im = p[C];
@@ -3024,11 +3025,11 @@ static inline unsigned grid_for(long total, int block) {
     if (g < 1) g = 1;
     return (unsigned)g;
 }
-hipError_t launch_spec_to_ref(const float* D, float* out, int Bt, int C, int L, int Mm, hipStream_t s) {
+hipError_t launch_spec_to_ref(const float* D, float* out, int Bt, int C, int L, int Mm, hipStream_t s, bool whole) {
     const long R = (long)L * Mm;
     if ((R + 31) / 32 > 0x7fffffffL || (C + 31) / 32 > 65535 || Bt > 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL(spec_layout_kernel<true>, dim3((unsigned)((R + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)Bt), dim3(256), 0, s, D, out, Bt, C, L, Mm,
-                       static_cast<unsigned*>(nullptr), 0);
+                       static_cast<unsigned*>(nullptr), whole ? 1 : 0);
     return hipGetLastError();
 }
 hipError_t launch_ref_to_spec(const float* in, float* E, int Bt, int C, int L, int Mm, hipStream_t s, unsigned* omax, bool triangular_consumer) {

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "range_exponent.h"
 #include "strip_pack.h"
 
 namespace ace {
@@ -47,11 +48,7 @@ constexpr int TS_BYTES = 2048;              // per-wave transpose buffer: 16 row
 constexpr int LDS_BYTES = NSLOT * SLOT_BYTES + 4 * TS_BYTES;   // 80 KiB: two workgroups per CU
 
 SDEV unsigned slot_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-SDEV int pow2_exponent_for(float mx) {
-    int e = 0;
-    if (mx > 0.f && mx < 3.0e38f) { (void)frexpf(mx, &e); e = 12 - e; }
-    return e > 100 ? 100 : (e < -100 ? -100 : e);
-}
+SDEV int pow2_exponent_for(float mx) { return range_exponent(mx); }   // range_exponent.h: the planes' consumer (dhconv_strip.hip) takes the same
 SDEV float wave_max_bits(unsigned raw) {
     float mx = __uint_as_float(raw);
 #pragma unroll

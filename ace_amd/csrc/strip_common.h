@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "range_exponent.h"
 
 namespace ace {
 namespace {
@@ -25,11 +26,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) char* lds_cptr;
 
 MDEV unsigned slot_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-MDEV int pow2_exponent_for(float mx) {
-    int e = 0;
-    if (mx > 0.f && mx < 3.0e38f) { (void)frexpf(mx, &e); e = 12 - e; }
-    return e > 100 ? 100 : (e < -100 ? -100 : e);
-}
+MDEV int pow2_exponent_for(float mx) { return range_exponent(mx); }   // range_exponent.h: the host's operator entries call the same
 MDEV float wave_max_bits(unsigned raw) {
     float mx = __uint_as_float(raw);
 #pragma unroll

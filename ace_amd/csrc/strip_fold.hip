@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "range_exponent.h"
 #include "strip_pack.h"
 
 namespace ace {
@@ -45,11 +46,7 @@ constexpr int fold_lds_bytes(int nh) { return FNSLOT * 2 * nh * 2048 + 4 * FTS_B
 constexpr int FLDS_BYTES = fold_lds_bytes(NH_MAX);
 
 FDEV unsigned slot_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-FDEV int pow2_exponent_for(float mx) {
-    int e = 0;
-    if (mx > 0.f && mx < 3.0e38f) { (void)frexpf(mx, &e); e = 12 - e; }
-    return e > 100 ? 100 : (e < -100 ? -100 : e);
-}
+FDEV int pow2_exponent_for(float mx) { return range_exponent(mx); }   // range_exponent.h: the planes' consumer (dhconv_strip.hip) takes the same
 FDEV float wave_max_bits(unsigned raw) {
     float mx = __uint_as_float(raw);
 #pragma unroll

@@ -6,6 +6,8 @@
 #include <cmath>
 #include <cstddef>
 
+#include "range_exponent.h"   // the exponent of DYNAMIC operands (planes a kernel rescales from a range slot): one clamp for host and device
+
 namespace ace {
 
 // 2^(top - e) with maxabs = f 2^e, f in [0.5, 1): maxabs * scale lands in [2^(top - 1), 2^top).  1 for zero, infinite or NaN input.

@@ -186,6 +186,36 @@ int ace_mlp_f16x3(const float* x, const float* w1, const float* b1, const float*
  * synchronises. */
 int ace_dhconv_f16x3(const float* coeffs, const float* weight, float* out, int n, int c, int L, int Mm, void* stream);
 
+/* The same kernel (csrc/dhconv_strip.hip) in every form it has, one launch, as the network launches it.  ace_dhconv_f16x3 is this
+ * entry with groups = 1, storage = 0, no out_absmax and e_fill = 0.
+ *   coeffs / out (n, c, L, Mm) complex64 interleaved.  Entries of coeffs with m > l are not read; entries of out with m > l are
+ *     never stored by the kernel: they come back as e_fill, the value the internal output scratch holds before the launch
+ *     (0 unless given; NaN is refused).
+ *   groups = 1: weight (c, c, L, 2), out[b,o,l,m] = sum_i coeffs[b,i,l,m] weight[i,o,l]  (contractions.py:183-195).
+ *   groups = G > 1: weight as the reference holds a grouped filter, (G, L, c / G [out], c / G [in], 2),
+ *     out[b,g,o,l,m] = sum_i coeffs[b,g,i,l,m] weight[g,l,o,i]  (conditional_sfno/s2convolutions.py:119-135).
+ *   storage 0: dense filter planes (c rows per output column); a grouped weight is expanded to (c, c, L, 2) with exact zeros first,
+ *              and the kernel skips the zero blocks when c / G is a multiple or a divisor of 128;
+ *           1: the diagonal blocks alone (c / G rows per output column); needs G > 1 and c / G in {32, 64, 128} or a multiple of 128.
+ *   out_absmax: NULL, or 64 words that receive the bit pattern of max |out| over the stored values (the maximum over the 64 words
+ *     is the maximum; the entry zeroes them first).
+ * Needs c % 128 == 0, G dividing c, operands below 2^31 elements and max |coeffs| in [2^-89, 2^112) (or zero): outside it the
+ * power-of-two scale of the coefficient planes is clamped and they do not hold the operator's precision.  Whatever the strip kernel
+ * does not take is ACE_ERR_INVALID with a message that names the constraint, never another engine.  route (optional) receives what ran:
+ * storage as above; kspan = input channels a workgroup contracts over (c, or max(c / G, 128) with zero-block skipping);
+ * units[s - 1] = workgroups with s active 32-row strips (s = 1 .. 3); max_chunks = the largest number of row chunks of one (degree,
+ * 128-column group); units_per_xcd = length of each of the 8 per-XCD work lists, padding included.
+ * Test / micro-benchmark entry: prepares the planes on every call and synchronises. */
+typedef struct ace_dhconv_route { int storage, kspan, units[3], max_chunks, units_per_xcd; } ace_dhconv_route;
+typedef struct ace_dhconv_desc {
+    const float* coeffs; const float* weight; float* out;
+    unsigned* out_absmax;
+    int n, c, L, Mm;
+    int groups, storage;
+    float e_fill;
+} ace_dhconv_desc;
+int ace_dhconv_strip_op(const ace_dhconv_desc* desc, ace_dhconv_route* route, void* stream);
+
 /* nn.InstanceNorm2d(C, eps, affine) (sfnonet.py:593-601) on (n, C, hw); gamma/beta may be NULL. */
 int ace_instance_norm(const float* x, const float* gamma, const float* beta, float eps, float* y, int n, int c,
                       long hw, void* stream);

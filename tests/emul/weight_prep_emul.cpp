@@ -49,6 +49,44 @@ static void check_pow2_scale() {
     std::printf("pow2_scale: %d inputs\n", n);
 }
 
+// range_exponent (range_exponent.h): the exponent of a DYNAMIC operand's planes, the one function the kernels (strip_common.h) and the
+// host entries that write planes for them (capi.hip: ace_dhconv_strip_op) share.  Inside its clamp it is pow2_scale(mx, 12)'s exponent;
+// beyond it the two part by a power of two - which is what ace_dhconv_f16x3 got wrong while it scaled with pow2_scale and the
+// kernel unscaled with the clamped exponent (max |coeffs| = 2^-95: e = 106 against 100; 2^115: -104 against -100).
+static void check_range_exponent() {
+    std::vector<float> in = {0.f, -1.f, std::numeric_limits<float>::denorm_min(), FLT_MIN, 2.9e38f, 3.0e38f, FLT_MAX, INFINITY, NAN};
+    for (int k : {-120, -95, -90, -89, -88, -20, 0, 11, 12, 30, 111, 112, 113, 115, 120}) {
+        const float p = std::ldexp(1.0f, k);
+        in.push_back(std::nextafterf(p, 0.f)); in.push_back(p); in.push_back(std::nextafterf(p, INFINITY));
+    }
+    int n = 0, nclamped = 0;
+    for (float mx : in) {
+        bool clamped = true;
+        const int e = range_exponent(mx, &clamped);
+        CHECK(e == range_exponent(mx), "range_exponent(%a) depends on the flag", mx);
+        CHECK(e >= -100 && e <= 100, "range_exponent(%a) = %d", mx, e);
+        if (!(mx > 0.f) || !(mx < 3.0e38f)) { CHECK(e == 0 && !clamped, "range_exponent(%a) = %d, expected 0", mx, e); ++n; continue; }
+        int f = 0;
+        (void)std::frexp(mx, &f);
+        const int raw = 12 - f;
+        CHECK(e == (raw > 100 ? 100 : raw < -100 ? -100 : raw) && clamped == (raw != e), "range_exponent(%a) = %d (clamped %d), 12 - exponent = %d", mx, e, (int)clamped, raw);
+        if (!clamped) {   // the planes hold mx in [2^11, 2^12), and the static rule agrees bit for bit
+            const float v = mx * std::ldexp(1.0f, e);
+            CHECK(v >= 2048.f && v < 4096.f, "range_exponent(%a): scaled %a", mx, v);
+            CHECK(same_bits(std::ldexp(1.0f, e), pow2_scale(mx, 12)), "range_exponent(%a) and pow2_scale(.., 12) differ inside the clamp", mx);
+            CHECK(mx >= std::ldexp(1.0f, -89) && mx < std::ldexp(1.0f, 112), "unclamped outside [2^-89, 2^112): %a", mx);
+        } else {          // ... outside they differ: the host must not take pow2_scale there
+            CHECK(!same_bits(std::ldexp(1.0f, e), pow2_scale(mx, 12)), "range_exponent(%a): clamped, yet equal to pow2_scale", mx);
+            CHECK(mx < std::ldexp(1.0f, -89) || mx >= std::ldexp(1.0f, 112), "clamped inside [2^-89, 2^112): %a", mx);
+            ++nclamped;
+        }
+        ++n;
+    }
+    CHECK(range_exponent(std::ldexp(1.0f, -95)) == 100 && range_exponent(std::ldexp(1.0f, 115)) == -100, "the two ends the operator test runs");
+    CHECK(nclamped >= 10, "only %d clamped inputs", nclamped);
+    std::printf("range_exponent: %d inputs, %d beyond the clamp\n", n, nclamped);
+}
+
 static void check_weight_norms() {
     const int shapes[4][3] = {{1, 1, 1}, {3, 5, 5}, {16, 33, 64}, {128, 384, 384}};   // rows, cols, ld
     std::mt19937 rng(20240611);
@@ -122,6 +160,7 @@ static void check_storage_question() {
 
 int main() {
     check_pow2_scale();
+    check_range_exponent();
     check_weight_norms();
     check_storage_question();
     if (bad) { std::printf("%d checks FAILED\n", bad); return 1; }

@@ -77,6 +77,20 @@ def test_dhconv_work_list(tmp_path):
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_dhconv_strip_body_index_algebra(tmp_path):
+    """ace_amd/csrc/dhconv_strip.hip, dhconv_body restated per wave and lane on the launch's real work list: A-piece source addresses
+    with the XOR slot against the fragment reads, the piece order, the stage window of a skipping launch, the dense and the
+    diagonal-blocks B address with its clamp, live stages, row map and store mask - every address in bounds (dummy tail included),
+    every filter element of a unit fetched once by a live stage, every output row below rows(l) written once, values against direct
+    complex sums; C in {128, 256, 384, 512}, every grouped form, every shape of tests/_dhconv_ref.py."""
+    exe = str(tmp_path / "dhconv_strip_emul")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "emul", "dhconv_strip_emul.cpp")], check=True)
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "worst" in res.stdout and "FAILED" not in res.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_fft_unit_mappings_and_offset_bound(tmp_path):
     """ace_amd/csrc/fft_units.h (the workgroup -> (channel block, latitude) mappings of fft.hip, with and without rider workgroups,
     and the bound on the kernels' 32-bit lane offsets): every unit exactly once, every rider exactly once and first in its XCD's
@@ -91,7 +105,8 @@ def test_fft_unit_mappings_and_offset_bound(tmp_path):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_weight_preparation_arithmetic_and_storage_question(tmp_path):
     """ace_amd/csrc/weight_prep.h and conv_roles.h (host arithmetic of weight upload): pow2_scale against the rule written out at zero,
-    denormal, power-of-two neighbours, FLT_MAX, inf and NaN; weight_norms exact in max |w| and within (1 + 2e-6) above the long-double
+    denormal, power-of-two neighbours, FLT_MAX, inf and NaN; range_exponent (the one exponent host and kernels take for dynamic
+    planes) against its rule, equal to pow2_scale(., 12) inside its clamp and different beyond it (2^-95 and 2^115 among the inputs); weight_norms exact in max |w| and within (1 + 2e-6) above the long-double
     row sums, padding columns never read; the conv_ws / conv_wl storage question on the data grid against a block's own grid."""
     exe = str(tmp_path / "weight_prep_emul")
     subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "emul", "weight_prep_emul.cpp")], check=True)
