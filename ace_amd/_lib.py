@@ -3,6 +3,7 @@
 The product path has no CPU or eager-torch fallback: if the HIP library is
 missing this module raises, loudly, at first use."""
 
+import contextlib
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_void_p
@@ -320,6 +321,14 @@ SIGNATURES = {
     "ace_diag_region_segments": (c_int, [c_void_p] * 6 + [c_int] * 11 + [c_void_p]),
     # gen, gen_strides, target, target_strides, rows, mean, sq, err, nrows, n_time, t0, assign, nplanes, batch, steps, hw, stream
     "ace_diag_video_window": (c_int, [c_void_p] * 8 + [c_int] * 7 + [c_long, c_void_p]),
+    # srcs, src_strides, dsts, dst_strides, nplanes, batch, hw, stream
+    "ace_stepdiag_snapshot": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_long, c_void_p]),
+    # outs, out_strides, snaps, snap_strides, nplanes, batch, steps, hw, stream
+    "ace_stepdiag_delta_window": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_long, c_void_p]),
+    "ace_diag_correction_partial_doubles": (c_long, [c_int, c_int, c_int, c_long]),
+    # deltas, strides, stds, rows, wrows, weights, nw, partial, signed_sum, magnitude_sum, series, nrows, n_time, t0, nplanes, batch,
+    # steps, hw, stream
+    "ace_diag_correction_window": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 4 + [c_int] * 6 + [c_long, c_void_p]),
 }
 
 _lib = None
@@ -374,6 +383,24 @@ def ptr(t) -> int:
     if not t.is_contiguous():
         raise RuntimeError("tensor must be contiguous")
     return t.data_ptr()
+
+
+@contextlib.contextmanager
+def capture_without_gc():
+    """Around a ``torch.cuda.graph`` capture: collect the dead Python cycles first and keep the collector off until the capture
+    ends.  ``torch.cuda.graph`` no longer collects on entry, and a cycle that dies inside the capture may own device resources whose
+    release (a ``hipFree`` behind a native handle's ``__del__``, the graph of an engine no longer in use) invalidates the capture:
+    the next launch then fails with hipErrorStreamCaptureInvalidated.  When the collector runs depends on the allocation count,
+    i.e. on unrelated host code."""
+    import gc
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def current_stream() -> int:

@@ -5,8 +5,9 @@ series (``mean``, reduced.py:370-497), the time-mean maps (``time_mean``, time_m
 xarray, netCDF, wandb and torch_harmonics are not on this stack: logs hold tensors and floats where the reference logs images and
 figures, ``get_dataset`` returns plain dicts of tensors, ``flush_diagnostics`` writes ``torch.save`` archives with the reference's
 stems (``<sub-aggregator>_diagnostics.pt`` for its ``.nc``, as ``TensorFileWriter`` writes ``restart.pt``), and the spectrum's SHT
-is the project's own forward transform.  Not built: the ``annual`` and ``enso_index`` sub-aggregators, step diagnostics, reference
-time means and HEALPix grids.  The evaluator that compares a rollout with a target record (``InferenceEvaluatorAggregator``) is
+is the project's own forward transform.  Not built: the ``annual`` and ``enso_index`` sub-aggregators, reference time means and
+HEALPix grids.  The correction metrics of the corrector's step diagnostics (ace_amd/step_diagnostics.py) are opt-in:
+``InferenceAggregatorConfig(step_diagnostics=StepDiagnosticsMetricConfig())`` with ``build(..., normalize=...)``.  The evaluator that compares a rollout with a target record (``InferenceEvaluatorAggregator``) is
 ace_amd/evaluator/.
 
 The reference flood-fills the NaNs of a masked field before the spectrum (``SmoothFloodFill(num_steps=4)``, spectrum.py:331).  Here
@@ -48,8 +49,11 @@ def _is_healpix(dataset_info) -> bool:
 
 @dataclasses.dataclass
 class InferenceAggregatorConfig:
-    """main.py:785-890 (same fields).  ``time_mean_reference_data`` (a netCDF path) and a non-default ``step_diagnostics`` are
-    refused at build time: there is no netCDF reader and no step-diagnostics aggregator here.  ``fill_masked_spectrum`` (not a
+    """main.py:785-890 (same fields).  ``time_mean_reference_data`` (a netCDF path) is refused at build time: there is no netCDF
+    reader here.  ``step_diagnostics``: a ``StepDiagnosticsMetricConfig`` (ace_amd/step_diagnostics.py) or its dict builds the
+    correction aggregator; ``None`` / ``{}`` (the default) builds none - one deliberate difference from the reference, whose
+    default ``StepDiagnosticsMetricConfig()`` is on; pass that for the reference's behaviour.  A dict with any other key is
+    refused (``NotImplementedError``): nothing else of the step diagnostics is built.  ``fill_masked_spectrum`` (not a
     field of the reference, which always fills): flood-fill masked names before the spectrum instead of omitting them; the
     reference's behaviour is ``True``, the default ``False`` keeps what this aggregator computed before the fill was built."""
     log_global_mean_time_series: bool = True
@@ -58,23 +62,26 @@ class InferenceAggregatorConfig:
     fill_masked_spectrum: bool = False
 
     def build(self, dataset_info, n_timesteps: int, output_dir: Optional[str] = None, save_diagnostics: bool = False,
-              sht_factory: Optional[Callable[[int, int], Callable]] = None) -> "InferenceAggregator":
+              sht_factory: Optional[Callable[[int, int], Callable]] = None, normalize=None) -> "InferenceAggregator":
         """``sht_factory(nlat, nlon)``: the forward SHT of the spectrum (default: the native
-        ``ace_amd.sht.RealSHT(nlat, nlon, grid="legendre-gauss", precision="fp32")``, device tensors only)."""
+        ``ace_amd.sht.RealSHT(nlat, nlon, grid="legendre-gauss", precision="fp32")``, device tensors only).  ``normalize``: the
+        stepper's normaliser (or its bound ``normalize``), which the correction metrics of ``step_diagnostics`` need."""
+        from .step_diagnostics import StepDiagnosticsMetricConfig
+        step_diagnostics = StepDiagnosticsMetricConfig.from_state(self.step_diagnostics)
         if self.time_mean_reference_data is not None:
             raise NotImplementedError("time_mean_reference_data is a netCDF file and there is no netCDF reader here; "
                                       "compare the time-mean maps of get_dataset() offline")
-        if self.step_diagnostics not in (None, {}):
-            raise NotImplementedError("step_diagnostics: only the default configuration is supported (no step-diagnostics "
-                                      "aggregator is built)")
         if _is_healpix(dataset_info):
             raise NotImplementedError("the inference aggregator is built for lat-lon grids only, not HEALPix")
         if getattr(dataset_info, "area_weights", None) is None:
             raise ValueError("the inference aggregator needs the dataset's area weights: build the DatasetInfo with lat (and "
                              "lon) or area_weights")
-        return InferenceAggregator(dataset_info, int(n_timesteps), log_global_mean_time_series=self.log_global_mean_time_series,
-                                   output_dir=output_dir, save_diagnostics=save_diagnostics, sht_factory=sht_factory,
-                                   fill_masked_spectrum=self.fill_masked_spectrum)
+        agg = InferenceAggregator(dataset_info, int(n_timesteps), log_global_mean_time_series=self.log_global_mean_time_series,
+                                  output_dir=output_dir, save_diagnostics=save_diagnostics, sht_factory=sht_factory,
+                                  fill_masked_spectrum=self.fill_masked_spectrum)
+        if step_diagnostics is not None:
+            agg._correction = step_diagnostics.build(agg, int(n_timesteps), self.log_global_mean_time_series, normalize)
+        return agg
 
 
 def _default_sht(nlat: int, nlon: int):
@@ -112,6 +119,7 @@ class InferenceAggregator:
         from .fill import FillTables
         self._fill = FillTables()
         self._n_seen = 0
+        self._correction = None           # the CorrectionDeltaAggregator of a configured ``step_diagnostics`` (step_diagnostics.py)
         self._path: Optional[str] = None
         self._launches = 0
         # per-time-index record count (reduced.py: _n_batches), host side
@@ -210,6 +218,21 @@ class InferenceAggregator:
                                         len(names), B, T, H, W, _lib.current_stream()))
         return planes, 1
 
+    @property
+    def records_step_diagnostics(self) -> bool:
+        """True when ``record_batch`` takes the window's ``StepDiagnostics`` (a correction aggregator was built): the drivers then
+        pass ``step_diagnostics=`` and otherwise call ``record_batch`` as ever."""
+        return self._correction is not None
+
+    def _record_step_diagnostics(self, step_diagnostics) -> None:
+        """main.py:588-592: the window's corrector deltas at ``i_time_start`` = the steps seen so far, before the other metrics"""
+        if self._correction is not None:
+            self._correction.fused = self._correction.fused and self.fused
+            self._correction.record_batch(step_diagnostics, self._n_seen)
+        elif step_diagnostics is not None:
+            raise ValueError("record_batch was given step_diagnostics, but this aggregator was built without a correction "
+                             "aggregator: configure step_diagnostics=StepDiagnosticsMetricConfig() and a normalizer")
+
     # ---- routing ------------------------------------------------------------------------------------------------------
     def route(self, data: TensorMapping) -> str:
         """"fused" when ``record_batch`` on this window runs the HIP kernels, "torch" when it runs the torch ops."""
@@ -255,11 +278,13 @@ class InferenceAggregator:
         return []
 
     @torch.no_grad()
-    def record_batch(self, data: TensorMapping):
+    def record_batch(self, data: TensorMapping, step_diagnostics=None):
         """main.py:937-960: name -> (B, T, H, W), derived variables included, at time index ``i_time_start`` = the steps seen
-        so far.  Returns no per-step logs (see ``record_initial_condition``)."""
+        so far; ``step_diagnostics``: the window's ``StepDiagnostics`` for the correction metrics.  Returns no per-step logs (see
+        ``record_initial_condition``)."""
         if len(data) == 0:
             raise ValueError("data is empty")
+        self._record_step_diagnostics(step_diagnostics)
         data = dict(data)
         n = next(iter(data.values())).shape[1]
         self._record(data, i_time_start=self._n_seen, with_maps=True)
@@ -468,6 +493,8 @@ class InferenceAggregator:
             ds["mean"] = {f"{metric}-{n}": v.cpu() for metric, d in self._series_data().items() for n, v in d.items()}
         ds["time_mean"] = {f"gen_map-{n}": v.cpu() for n, v in self._time_mean_data().items()}
         ds["power_spectrum"] = {n: v.cpu() for n, v in self._spectrum_data().items()}
+        if self._correction is not None:
+            ds.update(self._correction.datasets())
         return ds
 
     @torch.no_grad()
@@ -479,6 +506,8 @@ class InferenceAggregator:
             logs[f"time_mean/gen_map/{n}"] = v.cpu()
         for n, v in self._spectrum_data().items():
             logs[f"power_spectrum/{n}"] = v.cpu()
+        if self._correction is not None:
+            logs.update(self._correction.summary_logs())
         return logs
 
     @torch.no_grad()
@@ -494,6 +523,9 @@ class InferenceAggregator:
                 for k in keys:
                     row[f"mean/{k}"] = series[k][i]
                 rows.append(row)
+            if self._correction is not None:
+                for row, extra in zip(rows, self._correction.series_rows()):
+                    row.update(extra)
         if not rows:
             rows.append({})
         rows[-1].update(self.get_summary_logs())

@@ -15,7 +15,7 @@ from typing import Any, Dict, List, Mapping, Optional, Tuple
 
 import torch
 
-from .atmosphere import (GRAVITY, SPECIFIC_HEAT_OF_DRY_AIR_CONST_VOLUME, AreaWeightedMean, AtmosphereData,
+from .atmosphere import (ATMOSPHERE_FIELD_NAME_PREFIXES, GRAVITY, SPECIFIC_HEAT_OF_DRY_AIR_CONST_VOLUME, AreaWeightedMean, AtmosphereData,
                          HybridSigmaPressureCoordinate, compute_layer_thickness)
 
 TensorMapping = Mapping[str, torch.Tensor]
@@ -229,6 +229,43 @@ class AtmosphereCorrector:
             if name in config.needs_geometry() and name not in skip:
                 self.corrections.append(name)
         self._cfg = config
+        # the names the last call wrote (the union of its corrections' ``changed`` key sets): what the reference's
+        # CorrectionSequence reports a delta for (registry.py:161-198)
+        self.last_modified_names: List[str] = []
+
+    def modified_names(self, gen_names) -> List[str]:
+        """The names a call on outputs ``gen_names`` writes, from the configuration alone and in the order the corrections write
+        them: ``last_modified_names`` before any data exists (the fused path sizes its buffers from it).  A method of the built
+        corrector, not a static one: the set depends on which corrections this dataset's geometry lets it build
+        (``self.corrections``).  ``last_modified_names`` is per-call state on the corrector: read it right after the call, as
+        ``step_with_adjustments`` does; a second user of the same object (the multi-call copies) overwrites it.  Name resolution is
+        ``AtmosphereData``'s: the first prefix present among ``gen_names``."""
+        gen = list(gen_names)
+        out: List[str] = []
+
+        def add(names):
+            out.extend(n for n in names if n not in out)
+
+        def single(standard):
+            return [p for p in ATMOSPHERE_FIELD_NAME_PREFIXES[standard] if p in gen][:1]
+
+        moisture = self._cfg.moisture_budget_correction or ""
+        for name in self.corrections:
+            if name == "force_positive":
+                add(self.force_positive_names)
+            elif name == "conserve_dry_air":
+                add(single("surface_pressure"))
+            elif name == "zero_global_mean_moisture_advection":
+                add(single("tendency_of_total_water_path_due_to_advection"))
+            elif name == "moisture_budget_correction":
+                add(single("precipitation_rate") if moisture.endswith("precipitation") else single("latent_heat_flux"))
+                if moisture.startswith("advection"):
+                    add(single("tendency_of_total_water_path_due_to_advection"))
+                if self._cfg.clip_frozen_precipitation:
+                    add(single("frozen_precipitation_rate"))
+            else:
+                add(AtmosphereData({n: None for n in gen}).get_all_vertical_level_names("air_temperature"))
+        return out
 
     def _vcoord(self, device):
         key = str(device)
@@ -241,6 +278,7 @@ class AtmosphereCorrector:
         gen = dict(gen_data)
         dev = next(iter(gen.values())).device
         vc = self._vcoord(dev) if self._vc is not None else None
+        modified: List[str] = []
         for name in self.corrections:
             if name == "force_positive":
                 changed = force_positive(gen, self.force_positive_names)
@@ -260,4 +298,6 @@ class AtmosphereCorrector:
                 changed = _force_conserve_total_energy(input_data, gen, forcing_data, self._mean, vc, self._dt, eb.method,
                                                        eb.constant_unaccounted_heating)
             gen.update(changed)
+            modified.extend(n for n in changed if n not in modified)
+        self.last_modified_names = modified
         return gen, corrector_state

@@ -238,7 +238,11 @@ def check_supported(stepper: CoupledStepper, n_coupled_steps: int, graph: Option
 
 
 class CoupledRolloutEngine:
-    def __init__(self, stepper: CoupledStepper, batch: int, n_coupled_steps: int, graph: Optional[str] = "step"):
+    def __init__(self, stepper: CoupledStepper, batch: int, n_coupled_steps: int, graph: Optional[str] = "step",
+                 step_diagnostics: bool = False):
+        if step_diagnostics:
+            raise NotImplementedError("CoupledRolloutEngine: step_diagnostics (the corrector deltas) are built for RolloutEngine "
+                                      "only, not for the coupled stepper")
         self.plan, masks = check_supported(stepper, n_coupled_steps, graph)
         plan = self.plan
         self.stepper, self.graph_mode = stepper, graph
@@ -342,7 +346,7 @@ class CoupledRolloutEngine:
                     torch.cuda.current_stream().wait_stream(side)
                     self._launches = 0
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
+                    with _lib.capture_without_gc(), torch.cuda.graph(g):
                         for i in range(self.n_outer):
                             self._enqueue_step(i, False, interpolate)
                     self._window_graph = g

@@ -32,7 +32,7 @@ the files are ``torch.save`` archives ``<label>.pt``; a ``TimeSlice`` selection 
 ``CFTimeIndex``), a zarr ``format`` and ``separate_ensemble_members`` raise ``NotImplementedError``; a box that holds no grid point
 raises ``ValueError`` at build time where the reference would write empty arrays.
 
-Not built: netCDF / zarr output, the step-diagnostics writer (``save_step_diagnostics``), the histogram and video writers, and the
+Not built: netCDF / zarr output, the step-diagnostics writer (``save_step_diagnostics``; the records themselves are, step_diagnostics.py), the histogram and video writers, and the
 coupled loop's writer."""
 import dataclasses
 import logging
@@ -992,8 +992,8 @@ class _RawSubset(TensorFileWriter):
 @dataclasses.dataclass
 class DataWriterConfig:
     """main.py:36-100 (same fields and defaults).  ``files``: a list of ``FileWriterConfig``, one extra region- / time-selected file
-    (or pair of files) each; their file names must differ.  ``save_step_diagnostics=True`` is refused at build time: there are no
-    step-diagnostics records here.  So are an empty ``files`` list and an entry that is not a ``FileWriterConfig``."""
+    (or pair of files) each; their file names must differ.  ``save_step_diagnostics=True`` is refused at build time: the records
+    exist (ace_amd/step_diagnostics.py) but their file writer is not built.  So are an empty ``files`` list and an entry that is not a ``FileWriterConfig``."""
     save_prediction_files: bool = True
     save_monthly_files: bool = True
     save_step_diagnostics: bool = False
@@ -1020,8 +1020,8 @@ class DataWriterConfig:
 
     def _refuse(self):
         if self.save_step_diagnostics:
-            raise NotImplementedError("save_step_diagnostics: no step-diagnostics records are produced here, so there is no "
-                                      "step-diagnostics writer")
+            raise NotImplementedError("save_step_diagnostics: the step-diagnostics records are produced (predict(..., "
+                                      "step_diagnostics=True)), but the step-diagnostics file writer is not built")
         if self.files is not None and (not self.files or len(self._file_configs()) != len(self.files)):
             raise NotImplementedError("files: a non-empty list of FileWriterConfig entries is what is built; got "
                                       f"{[type(f).__name__ for f in self.files]}")

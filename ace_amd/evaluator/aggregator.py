@@ -139,9 +139,10 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         return []
 
     @torch.no_grad()
-    def record_batch(self, prediction: TensorMapping, target: TensorMapping, time=None):
+    def record_batch(self, prediction: TensorMapping, target: TensorMapping, time=None, step_diagnostics=None):
         """main.py:579-627: a paired window, each name -> (B, T, H, W), at time index ``i_time_start`` = the steps seen so far;
-        ``time``: the ``TimeAxis`` (B, T) of the window's steps, needed when ``needs_time``.  Returns no per-step logs and does not
+        ``time``: the ``TimeAxis`` (B, T) of the window's steps, needed when ``needs_time``; ``step_diagnostics``: the window's
+        ``StepDiagnostics``, recorded before the other metrics (main.py:588-592).  Returns no per-step logs and does not
         synchronise."""
         if len(prediction) == 0:
             raise ValueError("No prediction values in data")
@@ -150,6 +151,7 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         B, n = next(iter(prediction.values())).shape[:2]
         if B % self.n_ensemble_per_ic != 0:
             raise ValueError(f"a window of {B} samples is not a multiple of n_ensemble_per_ic = {self.n_ensemble_per_ic}")
+        self._record_step_diagnostics(step_diagnostics)
         if self.uses_time and time is None:
             self._without_time()
         if self.uses_time:
@@ -200,7 +202,10 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         ``<metric>-<name>`` (T,); ``time_mean`` / ``time_mean_norm``: ``bias_map-<name>``, ``gen_map-<name>`` (H, W);
         ``power_spectrum``: ``<name>`` (2, lmax) with the leading source axis [prediction, target]; ``zonal_mean``:
         ``gen-<name>``, ``error-<name>`` (n_slots, H)."""
-        return self._blocks("dataset")
+        out = self._blocks("dataset")
+        if self._correction is not None:
+            out.update(self._correction.datasets())
+        return out
 
     def _blocks(self, which: str) -> Dict[str, Dict[str, Any]]:
         """label -> block of every family's ``dataset()`` or ``logs()``, the paired labels first in their reporting order (the
@@ -215,6 +220,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
         """main.py:668-676: the logs of the sub-aggregators that are not time series, and ``loss`` =
         ``time_mean_norm/rmse/channel_mean``."""
         logs = {f"{label}/{k}": v for label, block in self._blocks("logs").items() for k, v in block.items()}
+        if self._correction is not None:
+            logs.update(self._correction.summary_logs())
         key = self._labels.get("time_mean_norm")
         return InferenceSummary(logs=logs, loss=logs.get(f"{key}/rmse/channel_mean") if key else None)
 
@@ -232,5 +239,8 @@ class InferenceEvaluatorAggregator(InferenceAggregator):
                 row[f"{label}/forecast_step"] = i
                 for k in sorted(series):
                     row[f"{label}/{k}"] = series[k][i]
+        if self._correction is not None and self._log_series:
+            for row, extra in zip(rows, self._correction.series_rows()):
+                row.update(extra)
         rows[-1].update(self.get_summary_logs())
         return rows

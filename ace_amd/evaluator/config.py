@@ -252,6 +252,9 @@ class InferenceEvaluatorAggregatorConfig:
               n_ensemble_per_ic: int = 1, video_max_bytes: int = 32 << 30) -> "InferenceEvaluatorAggregator":
         """``normalize``: a ``StandardNormalizer``, its bound ``normalize``, or anything exposing per-name ``means`` and ``stds``
         (the fused path reads the statistics, the torch path calls it); a bare callable serves the torch path only.
+        ``step_diagnostics`` (a field): a ``StepDiagnosticsMetricConfig`` (ace_amd/step_diagnostics.py) or its dict builds the
+        correction aggregator; ``None`` / ``{}`` (the default) builds none - one deliberate difference from the reference, whose
+        default ``StepDiagnosticsMetricConfig()`` is on; a dict with any other key raises ``NotImplementedError``.
         ``n_ensemble_per_ic``: the samples of a window are ``n_ic x n_ensemble_per_ic`` members, sample ``b = i * n_ensemble_per_ic +
         e`` (``inference.repeat_members``); with 1 the ensemble entries are accepted but neither recorded nor reported
         (main.py:560-562, 604-621).  ``video_max_bytes``: the most the video metric's accumulators may take (names x n_timesteps
@@ -261,9 +264,8 @@ class InferenceEvaluatorAggregatorConfig:
         if self.monthly_reference_data is not None or self.time_mean_reference_data is not None:
             raise NotImplementedError("monthly_reference_data / time_mean_reference_data are netCDF files and there is no netCDF "
                                       "reader here; compare the maps of get_dataset() offline")
-        if self.step_diagnostics not in (None, {}):
-            raise NotImplementedError("step_diagnostics: only the default configuration is supported (no step-diagnostics "
-                                      "aggregator is built)")
+        from ..step_diagnostics import StepDiagnosticsMetricConfig
+        step_diagnostics = StepDiagnosticsMetricConfig.from_state(self.step_diagnostics)     # refuses what is not built
         for field, typed, bare, _ in _FIELDS:
             if bare == "raises" and getattr(self, field).enabled and not isinstance(getattr(self, field), typed):
                 if field in ("histogram", "video"):
@@ -355,7 +357,7 @@ class InferenceEvaluatorAggregatorConfig:
             raise ValueError("the inference evaluator aggregator needs the dataset's area weights: build the DatasetInfo with lat "
                              "(and lon) or area_weights")
         from .aggregator import InferenceEvaluatorAggregator
-        return InferenceEvaluatorAggregator(
+        agg = InferenceEvaluatorAggregator(
             dataset_info, int(n_ic_steps), int(n_forward_steps), normalize, labels=labels, skipped=skipped,
             zonal_mean_max_size=getattr(self.zonal_mean, "zonal_mean_max_size", 4096), channel_mean_names=channel_mean_names,
             report_directional_bias=getattr(self.power_spectrum, "report_directional_bias", True), output_dir=output_dir,
@@ -363,3 +365,7 @@ class InferenceEvaluatorAggregatorConfig:
             histogram=self.histogram if self.histogram.enabled else None, video=self.video if self.video.enabled else None,
             video_max_bytes=int(video_max_bytes), calendar=calendar, **regress, **stepped,
             n_ensemble_per_ic=int(n_ensemble_per_ic), fill_masked=bool(getattr(self.power_spectrum, "fill_masked", False)))
+        if step_diagnostics is not None:
+            # step_diagnostics.py:115-165: the per-step series go with the evaluator's own (``mean`` / ``mean_norm`` enabled)
+            agg._correction = step_diagnostics.build(agg, int(n_ic_steps) + int(n_forward_steps), agg._log_series, normalize)
+        return agg

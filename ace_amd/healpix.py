@@ -1502,7 +1502,7 @@ class CapturedHEALPixForward:
                     net(self.x)
             torch.cuda.current_stream(example.device).wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with _lib.capture_without_gc(), torch.cuda.graph(self.graph):
                 self.y = net(self.x)
 
     def __call__(self, inputs: torch.Tensor) -> torch.Tensor:

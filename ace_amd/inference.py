@@ -138,6 +138,11 @@ class Looper:
         self._len = len(data.loader)
         self._loader = iter(data.loader)
         self._time = None
+        self._step_diagnostics = None
+
+    def get_step_diagnostics(self):
+        """The ``StepDiagnostics`` of the last batch, ``None`` when the predict function attached none."""
+        return self._step_diagnostics
 
     def __iter__(self):
         return self
@@ -158,6 +163,7 @@ class Looper:
             output, self._prognostic_state = self._predict(self._prognostic_state, forcing, compute_derived_variables=True)
         else:
             output, self._prognostic_state = self._predict(self._prognostic_state, forcing)
+        self._step_diagnostics = getattr(output, "step_diagnostics", None)
         return output
 
     def get_prognostic_state(self) -> TensorDict:
@@ -231,7 +237,10 @@ def run_inference(predict: Callable, data: InferenceData, aggregator=None, write
     for batch in looper:
         _append_batch(writer, batch, time=looper.get_time())
         if aggregator is not None:
-            logs = aggregator.record_batch(data=batch)
+            if getattr(aggregator, "records_step_diagnostics", False):      # built with a correction aggregator (step_diagnostics.py)
+                logs = aggregator.record_batch(data=batch, step_diagnostics=looper.get_step_diagnostics())
+            else:
+                logs = aggregator.record_batch(data=batch)
             if record_logs is not None:
                 record_logs(logs)
     state = looper.get_prognostic_state()
@@ -268,10 +277,13 @@ def run_evaluator(predict: Callable, data: InferenceData, aggregator, writer=Non
         needs, has =getattr(aggregator, "needs_time", False), getattr(win, "time", None) is not None
         if needs and not has:                             # the trend metric regresses against the times of the window's steps
             raise ValueError("this aggregator needs the windows' time axis: build the ForcingWindows with time=")
+        extra = {}
+        if getattr(aggregator, "records_step_diagnostics", False):      # built with a correction aggregator (step_diagnostics.py)
+            extra["step_diagnostics"] = getattr(out, "step_diagnostics", None)
         if needs or (has and getattr(aggregator, "uses_time", False)):      # the calendar metrics take it when there is one
-            logs = aggregator.record_batch(prediction=out, target=target, time=win.time[:, 1:])
+            logs = aggregator.record_batch(prediction=out, target=target, time=win.time[:, 1:], **extra)
         else:
-            logs = aggregator.record_batch(prediction=out, target=target)
+            logs = aggregator.record_batch(prediction=out, target=target, **extra)
         if record_logs is not None:
             record_logs(logs)
     writer.write(state, "restart.nc")
@@ -284,14 +296,17 @@ class EnginePredict:
     """``PredictFunction`` on the static-buffer ``RolloutEngine`` (``OceanRolloutEngine`` for a Samudra stepper): one engine per window length (the last window of a
     rollout may be shorter), built on first use.  Outputs are copied out of the engine's buffers (the next window reuses them)."""
 
-    def __init__(self, stepper, batch: int, graph: Optional[str] = "step", labels=None):
-        """``labels``: the batch's labels for a label-conditioned stepper (BatchLabels, or a (batch, n_labels) tensor in the module's
+    def __init__(self, stepper, batch: int, graph: Optional[str] = "step", labels=None, step_diagnostics: bool = False):
+        """``step_diagnostics``: the returned outputs carry ``.step_diagnostics`` (the corrector deltas of the window, cloned out of
+        the engine's buffer with the outputs; ace_amd/step_diagnostics.py); off by default, where the reference always attaches them.
+        ``labels``: the batch's labels for a label-conditioned stepper (BatchLabels, or a (batch, n_labels) tensor in the module's
         encoding) - the reference takes them from the forcing batch (fme/core/generics/inference.py); every engine of this predict
         function gets them before its first window."""
         self._stepper = stepper
         self._batch = batch
         self._graph = graph
         self._labels = labels
+        self._step_diagnostics = bool(step_diagnostics)
         self._engines: Dict[int, Any] = {}
 
     def set_labels(self, labels) -> None:
@@ -318,13 +333,20 @@ class EnginePredict:
         if eng is None:
             # a Samudra ocean stepper (input / output masking, the ocean corrector) runs on its own engine
             engine = OceanRolloutEngine if isinstance(self._stepper._step_obj.module.torch_module, Samudra) else RolloutEngine
-            eng = self._engines[n_steps] = engine(self._stepper, batch=self._batch, n_forward_steps=n_steps, graph=self._graph)
+            extra = {"step_diagnostics": True} if self._step_diagnostics else {}      # an engine without the option refuses it
+            eng = self._engines[n_steps] = engine(self._stepper, batch=self._batch, n_forward_steps=n_steps, graph=self._graph,
+                                                  **extra)
             if self._labels is not None:
                 eng.set_labels(self._labels)
         out, state = eng.predict(initial_condition, forcing)
         kept = type(state)({k: v.clone() for k, v in state.items()})
         kept.stepper_state = getattr(state, "stepper_state", None)
+        diags = getattr(out, "step_diagnostics", None)
         out = {k: v.clone() for k, v in out.items()}
+        if self._step_diagnostics:
+            from .step_diagnostics import StepDiagnostics, WindowData
+            out = WindowData(out, step_diagnostics=None if diags is None else
+                             StepDiagnostics(delta={k: v.clone() for k, v in diags.delta.items()}))
         if compute_derived_variables:
             from .stepper import derive_over_window
             out = derive_over_window(self._stepper.derive_func, out, initial_condition, forcing, 1, n_steps)

@@ -93,7 +93,11 @@ class OceanRolloutEngine(WindowEngine):
             raise RuntimeError("OceanRolloutEngine runs on an MI355X: load the stepper onto a 'cuda' device (there is no CPU path)")
         return in_mask, out_mask
 
-    def __init__(self, stepper: Stepper, batch: int, n_forward_steps: int, graph: Optional[str] = "step"):
+    def __init__(self, stepper: Stepper, batch: int, n_forward_steps: int, graph: Optional[str] = "step",
+                 step_diagnostics: bool = False):
+        if step_diagnostics:
+            raise NotImplementedError("OceanRolloutEngine: step_diagnostics (the corrector deltas) are built for the atmosphere "
+                                      "corrector on RolloutEngine only, not for the ocean corrector")
         self._check_graph(graph)
         in_mask, out_mask = self.check_supported(stepper)
         step = stepper._step_obj

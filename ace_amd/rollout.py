@@ -159,7 +159,7 @@ class WindowEngine:
                         self._enqueue_step(0, False)
                     torch.cuda.current_stream().wait_stream(side)
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
+                    with _lib.capture_without_gc(), torch.cuda.graph(g):
                         for s in range(self.T):
                             self._enqueue_step(s, False)
                     self._window_graph = g
@@ -232,7 +232,11 @@ class RolloutEngine(WindowEngine):
             raise NotImplementedError("graph='window' with multi-call diagnostics is not captured; use graph='step'")
 
     def __init__(self, stepper: Stepper, batch: int, n_forward_steps: int, graph: Optional[str] = "step",
-                 in_override: Optional[Mapping[Tuple[str, int], torch.Tensor]] = None):
+                 in_override: Optional[Mapping[Tuple[str, int], torch.Tensor]] = None, step_diagnostics: bool = False):
+        """``step_diagnostics``: ``predict`` returns its outputs as a ``WindowData`` whose ``.step_diagnostics`` holds the corrector
+        deltas of the window (ace_amd/step_diagnostics.py: views of a static buffer, overwritten by the next window); ``None`` when
+        the stepper has no corrector or it writes nothing.  Off by default - the reference always attaches them - and then the engine
+        enqueues exactly what it did before the option existed."""
         self._check_graph(graph)
         self.check_supported(stepper, graph)
         step = stepper._step_obj
@@ -323,8 +327,21 @@ class RolloutEngine(WindowEngine):
         slab = self._ocean is not None and getattr(self._ocean, "is_slab", False)   # the fused kernel knows the prescribed SST only
         if (self._corrector is not None or self._ocean is not None or self.prescribed) and not slab and not os.environ.get("ACE_NO_FUSED_PHYSICS"):
             self._physics = self._build_physics()
+        # corrector deltas (step_diagnostics.py): the uncorrected planes are copied aside between the unpack and the physics
+        self._step_diagnostics = bool(step_diagnostics)
+        self._recorder = self._build_recorder() if self._step_diagnostics else None
         self.net._ensure_native(dev, B)
         self.net.sync_weights()
+
+    def _build_recorder(self):
+        from .step_diagnostics import CorrectionDeltaRecorder, diagnosed_names
+        names = diagnosed_names(self._corrector, self._ocean, self.out_names, self.prescribed)
+
+        def locate(name, s):
+            p = self.out_plane(name, s)
+            return p.data_ptr(), p.stride(0)
+
+        return CorrectionDeltaRecorder(names, self.B, (self.H, self.W), self.T, locate, self.device) if names else None
 
     def _build_physics(self):
         from .physics import FusedPhysics
@@ -387,6 +404,8 @@ class RolloutEngine(WindowEngine):
         L = _lib.lib()
         stream = _lib.current_stream()
         self._evaluate(L, stream, s, use_library_graph, self._src_ptr_addr[s], self._dst_ptr_addr[s], self._dst_strides, True)
+        if self._recorder is not None:  # the network output of step s, before the corrector edits it in place
+            self._recorder.snapshot(s, stream)
         if self._physics is not None:   # corrector -> ocean -> prescribed prognostics (single_module.py:669-716), four launches
             self._physics.apply(s, stream)
         elif self._corrector is not None or self._ocean is not None or self.prescribed:
@@ -544,6 +563,8 @@ class RolloutEngine(WindowEngine):
         self._after_window()
 
     def _after_window(self):
+        if self._recorder is not None:  # one launch per window, after the replay: the snapshots become out - snapshot
+            self._recorder.finish_window(_lib.current_stream())
         if self.graph_mode == "window" and self._have_ref is not None and self._physics is None:
             # host-side view of the hook state the captured region keeps in its static buffer (a replay does not run
             # the Python that set it at capture time); a copy, so that a state handed out survives the next load()
@@ -571,10 +592,21 @@ class RolloutEngine(WindowEngine):
             self._window_graph = None
             if self._physics is not None:
                 self._physics = self._build_physics()
+            if self._step_diagnostics:      # the new corrector writes other names
+                self._recorder = self._build_recorder()
         # The captured forwards hold scalars derived from the weights by value (ace_sfno_set_weight): whoever uploaded last -
         # this call, net.forward, Stepper.predict, another engine on the same net - the library's generation counter tells.
         return (int(self.net._native.value or 0) if hasattr(self.net._native, "value") else int(self.net._native),
                 int(_lib.lib().ace_sfno_weights_generation(self.net._native)))
+
+    def predict(self, initial_condition, forcing, time=None):
+        """``WindowEngine.predict``; with ``step_diagnostics`` the outputs come back as a ``WindowData`` carrying the window's deltas."""
+        out, state = super().predict(initial_condition, forcing, time)
+        if not self._step_diagnostics:
+            return out, state
+        from .step_diagnostics import WindowData
+        diags = self._recorder.step_diagnostics() if self._recorder is not None else None
+        return WindowData(out, step_diagnostics=diags), state
 
     def _carry_in(self, carried):
         carried_random = getattr(carried, "random_state", None)

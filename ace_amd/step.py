@@ -88,7 +88,8 @@ class StepperState:
 
 @dataclasses.dataclass
 class StepOutput:
-    """output.py:12-28 (corrector diagnostics are always empty on this path)."""
+    """output.py:12-28.  ``corrector_diagnostics``: name -> ``corrected - network output`` of the names the corrector wrote, filled
+    only when the step is asked for it (``step_diagnostics=True``); empty otherwise."""
 
     output: TensorDict
     stepper_state: Any = None
@@ -257,10 +258,13 @@ def step_with_adjustments(input: TensorMapping, next_step_input_data: TensorMapp
                           residual_prediction: bool, prognostic_names: List[str],
                           prescribed_prognostic_names: Optional[List[str]] = None,
                           stepper_state=None, corrector=None, ocean=None, global_mean_removal=None,
-                          data_mask=None) -> StepOutput:
+                          data_mask=None, step_diagnostics: bool = False) -> StepOutput:
     """single_module.py:595-733: (global-mean removal), normalise, network, (residual), denormalise, (global means restored),
     corrector, ocean, prescribed prognostics - in the reference's order (single_module.py:650-716).  The corrector, the ocean and
-    the prescribed prognostics see the unshifted input and the physical output."""
+    the prescribed prognostics see the unshifted input and the physical output.  ``step_diagnostics`` (off by default; the
+    reference always does this): ``StepOutput.corrector_diagnostics`` gets ``corrected - output`` of every name the atmosphere
+    corrector wrote (single_module.py:669-733), without the prescribed prognostic names; the ocean's surface temperature among
+    them raises ``ValueError``."""
     if prescribed_prognostic_names is None:
         prescribed_prognostic_names = []
     gmr_state = None
@@ -277,20 +281,33 @@ def step_with_adjustments(input: TensorMapping, next_step_input_data: TensorMapp
     output = normalizer.denormalize(output_norm)
     if global_mean_removal is not None:
         output = global_mean_removal.inverse_transform(output, gmr_state)
+    delta: TensorDict = {}
     if corrector is not None:
         cstate = stepper_state.corrector_state if stepper_state is not None else None
+        uncorrected = output
         output, cstate = corrector(input, output, next_step_input_data, cstate)
+        if step_diagnostics:
+            if not hasattr(corrector, "last_modified_names"):
+                raise NotImplementedError(f"step_diagnostics: the deltas of {type(corrector).__name__} are not built (only the "
+                                          "atmosphere corrector reports them)")
+            delta = {n: (output[n] - uncorrected[n]).detach() for n in corrector.last_modified_names}
         if cstate is not None:      # keep the other fields of an incoming state (single_module.py:683-693)
             stepper_state = (StepperState(corrector_state=cstate) if stepper_state is None
                              else dataclasses.replace(stepper_state, corrector_state=cstate))
     if ocean is not None:
+        # the ocean writes after the corrector: its name among the deltas would make them inexact (single_module.py:692-706)
+        overlap = {ocean.surface_temperature_name} & set(delta)
+        if overlap:
+            raise ValueError(f"post-corrector adjustment names overlap the corrector's modified names: {sorted(overlap)}")
         output = ocean(input, output, next_step_input_data)
     for name in prescribed_prognostic_names:
         if name in next_step_input_data:
             output = {**output, name: next_step_input_data[name]}
         else:
             raise ValueError(f"prescribed_prognostic_name '{name}' not in next_step_input_data")
-    return StepOutput(output=output, stepper_state=stepper_state)
+    # a prescribed overwrite replaces the output: the corrector's delta no longer describes it (single_module.py:717-728)
+    delta = {n: v for n, v in delta.items() if n not in prescribed_prognostic_names}
+    return StepOutput(output=output, stepper_state=stepper_state, corrector_diagnostics=delta)
 
 
 class SingleModuleStep:
@@ -368,7 +385,8 @@ class SingleModuleStep:
             mods.extend(self.secondary_decoder.torch_modules)
         return nn.ModuleList(mods)
 
-    def step(self, args: StepArgs, wrapper: Callable[[nn.Module], nn.Module] = lambda x: x) -> StepOutput:
+    def step(self, args: StepArgs, wrapper: Callable[[nn.Module], nn.Module] = lambda x: x,
+             step_diagnostics: bool = False) -> StepOutput:
         def network_call(input_norm: TensorDict) -> TensorDict:
             if args.data_mask is not None:
                 raise NotImplementedError("data masks are outside the accelerated hot path")
@@ -385,7 +403,7 @@ class SingleModuleStep:
             prognostic_names=self.prognostic_names,
             prescribed_prognostic_names=self._config.prescribed_prognostic_names,
             stepper_state=args.stepper_state, corrector=self._corrector, ocean=self._ocean,
-            global_mean_removal=self._global_mean_removal, data_mask=args.data_mask,
+            global_mean_removal=self._global_mean_removal, data_mask=args.data_mask, step_diagnostics=step_diagnostics,
         )
 
     def get_state(self):

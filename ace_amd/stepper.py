@@ -31,8 +31,13 @@ def derive_over_window(derive_func, data: TensorDict, initial_condition: TensorM
     the initial condition.  A derive function with a ``window`` method (``OceanDeriveFn``) reads the initial condition where it
     lies; any other gets the concatenated window."""
     if hasattr(derive_func, "window"):
-        return derive_func.window(data, initial_condition, forcing, n_ic, n_forward_steps)
-    return derive_by_concatenation(derive_func, data, initial_condition, forcing, n_ic, n_forward_steps)
+        out = derive_func.window(data, initial_condition, forcing, n_ic, n_forward_steps)
+    else:
+        out = derive_by_concatenation(derive_func, data, initial_condition, forcing, n_ic, n_forward_steps)
+    if hasattr(data, "step_diagnostics"):       # a window that carries its corrector deltas (``predict(step_diagnostics=True)``) keeps them
+        from .step_diagnostics import WindowData
+        out = WindowData(out, step_diagnostics=data.step_diagnostics)
+    return out
 
 
 def derive_by_concatenation(derive_func, data: TensorDict, initial_condition: TensorMapping, forcing: TensorMapping,
@@ -205,15 +210,18 @@ class Stepper:
         for m in self.modules:
             m.eval()
 
-    def step(self, args: StepArgs, wrapper: Callable[[nn.Module], nn.Module] = lambda x: x) -> StepOutput:
-        """single_module.py:1045-1075."""
+    def step(self, args: StepArgs, wrapper: Callable[[nn.Module], nn.Module] = lambda x: x,
+             step_diagnostics: bool = False) -> StepOutput:
+        """single_module.py:1045-1075.  ``step_diagnostics``: fill ``corrector_diagnostics`` (off by default, see
+        ``step_with_adjustments``)."""
         from .rand import use_generator
         args = args.apply_input_process_func(self._input_process_func)
         # single_module.py:1063-1068: a seeded rollout's generator is active around every network call of the step (the
         # multi-call copies run inside the wrapped step there, i.e. under the same generator, in call order)
         random_state = args.stepper_state.random_state if args.stepper_state is not None else None
         with use_generator(None if random_state is None else random_state.generator):
-            result = self._step_obj.step(args=args, wrapper=wrapper)
+            result = (self._step_obj.step(args=args, wrapper=wrapper, step_diagnostics=True) if step_diagnostics
+                      else self._step_obj.step(args=args, wrapper=wrapper))
             output = result.output
             if self._multi_call is not None:     # multi_call.py:296-312: its own state and diagnostics are discarded
                 output = {**self._multi_call.step(args=args, wrapper=wrapper).output, **output}
@@ -223,7 +231,8 @@ class Stepper:
                           corrector_diagnostics=self._output_masking(dict(diags)) if diags else {})
 
     def predict_generator(self, ic_dict: TensorMapping, forcing_dict: TensorMapping, n_forward_steps: int,
-                          labels=None, data_mask=None, stepper_state=None) -> Generator[StepOutput, None, None]:
+                          labels=None, data_mask=None, stepper_state=None,
+                          step_diagnostics: bool = False) -> Generator[StepOutput, None, None]:
         """single_module.py:1124-1167."""
         state = {k: ic_dict[k].squeeze(self.TIME_DIM) for k in ic_dict}
         for step in range(n_forward_steps):
@@ -234,8 +243,9 @@ class Stepper:
             }
             next_step_input_dict = {k: forcing_dict[k][:, step + 1] for k in self._step_obj.next_step_input_names}
             input_data = {**state, **input_forcing}
-            result = self.step(StepArgs(input=input_data, next_step_input_data=next_step_input_dict, labels=labels,
-                                        data_mask=data_mask, stepper_state=stepper_state))
+            args = StepArgs(input=input_data, next_step_input_data=next_step_input_dict, labels=labels, data_mask=data_mask,
+                            stepper_state=stepper_state)
+            result = self.step(args, step_diagnostics=True) if step_diagnostics else self.step(args)
             state = result.output
             stepper_state = result.stepper_state
             yield result
@@ -257,14 +267,25 @@ class Stepper:
 
     def predict(self, initial_condition: TensorMapping, forcing: TensorMapping,
                 n_forward_steps: Optional[int] = None, compute_derived_variables: bool = False, labels=None,
-                time=None, compute_derived_forcings: bool = True) -> Tuple[TensorDict, TensorDict]:
+                time=None, compute_derived_forcings: bool = True,
+                step_diagnostics: bool = False) -> Tuple[TensorDict, TensorDict]:
         """single_module.py:1169-1259 on plain dicts: initial_condition name -> (B, 1, H, W) prognostic state,
         forcing name -> (B, 1 + n_forward_steps, H, W).  Returns (output name -> (B, n_forward_steps, H, W),
         final prognostic state name -> (B, 1, H, W)).  The returned state is a ``PrognosticState`` (a dict) that carries
         the per-sample ``stepper_state`` (corrector dry-air reference) the way the reference's does
         (fme/ace/data_loading/batch_data.py:214-235): feed it back as the next window's initial condition.
         ``time``: the (B, 1 + n_forward_steps) ``TimeAxis`` of the forcing window (or ``forcing`` is a ``ForcingWindow`` carrying
-        it) - needed only when the stepper derives forcings from it (single_module.py:1202-1203)."""
+        it) - needed only when the stepper derives forcings from it (single_module.py:1202-1203).
+        ``step_diagnostics``: the returned data is a ``WindowData`` (a dict) whose ``.step_diagnostics`` is the window's
+        ``StepDiagnostics`` (``delta[name]`` = corrected - network output, (B, n_forward_steps, H, W), output masking applied) or
+        ``None`` when the stepper has no corrector or it wrote nothing.  The reference always attaches the record
+        (single_module.py:1211-1259); here it is produced only on request, so that nothing changes for a caller who does not ask.
+        Only the atmosphere corrector reports deltas: an ocean or sea-ice corrector raises ``NotImplementedError``."""
+        if step_diagnostics:
+            corrector = self._step_obj._corrector
+            if corrector is not None and not hasattr(corrector, "modified_names"):
+                raise NotImplementedError(f"step_diagnostics: the deltas of {type(corrector).__name__} are not built (only the "
+                                          "atmosphere corrector reports them)")
         if compute_derived_forcings:
             forcing = self.forcing_deriver(forcing, time)
         any_forcing = next(iter(forcing.values()))
@@ -274,9 +295,15 @@ class Stepper:
             if v.shape[self.TIME_DIM] != self.n_ic_timesteps:
                 raise ValueError(f"Initial condition must have {self.n_ic_timesteps} timesteps, got {v.shape[1]}.")
         with torch.no_grad():
+            extra = {"step_diagnostics": True} if step_diagnostics else {}
             outs = list(self.predict_generator(initial_condition, forcing, n_forward_steps, labels=labels,   # BatchLabels of a conditional module
-                                               stepper_state=getattr(initial_condition, "stepper_state", None)))
+                                               stepper_state=getattr(initial_condition, "stepper_state", None), **extra))
         data = {k: torch.stack([o.output[k] for o in outs], dim=self.TIME_DIM) for k in outs[0].output}
+        if step_diagnostics:
+            from .step_diagnostics import StepDiagnostics, WindowData
+            delta = {k: torch.stack([o.corrector_diagnostics[k] for o in outs], dim=self.TIME_DIM)
+                     for k in outs[0].corrector_diagnostics}
+            data = WindowData(data, step_diagnostics=StepDiagnostics(delta=delta) if delta else None)
         if compute_derived_variables:
             data = derive_over_window(self.derive_func, data, initial_condition, forcing, self.n_ic_timesteps, n_forward_steps)
         prognostic_state = PrognosticState({k: data[k][:, -1:] for k in self.prognostic_names})

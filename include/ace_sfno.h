@@ -835,6 +835,54 @@ int ace_diag_video_window(const float* const* gen, const long* gen_strides, cons
                           int nplanes, int batch, int steps, long hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Corrector step diagnostics (csrc/stepdiag.hip; fme/core/step/step_diagnostics.py and
+ * fme/ace/aggregator/inference/step_diagnostics.py).  Errors are reported behind ace_diag_last_error.  All three calls are
+ * stream-ordered, allocate nothing, never synchronise the host and may be captured into a graph.
+ *
+ * ace_stepdiag_snapshot      one launch: for k < nplanes and b < batch, dsts[k][b * dst_strides[k] + p] = srcs[k][b * src_strides[k]
+ *                  + p] for p < hw.  srcs / dsts: DEVICE tables of nplanes pointers to fp32 planes at any 4-byte boundary;
+ *                  src_strides / dst_strides: DEVICE int64 per-sample strides in floats.  A workgroup moves 16 bytes per access
+ *                  when hw is a multiple of 4 and both bases and both strides are 16-byte aligned, 4 bytes otherwise (chosen once
+ *                  per workgroup).  The engine calls it between the unpack and the in-place physics of every step.
+ * ace_stepdiag_delta_window  one launch: for k < nplanes, b < batch, t < steps and p < hw, with o = outs[k] + b * out_strides[2k]
+ *                  + t * out_strides[2k + 1] and s = snaps[k] + b * snap_strides[2k] + t * snap_strides[2k + 1]:
+ *                  s[p] = fl32(o[p] - s[p]), one IEEE fp32 subtraction, in place over the snapshot buffer (what torch's
+ *                  corrected - output gives, bit for bit).  Needs batch * steps <= 65535 (a grid dimension).
+ * ace_diag_correction_window  the correction metrics of a window of deltas, two launches (the window pass and its combine).
+ *                  deltas: DEVICE table of nplanes pointers to (batch, steps, hw) fp32 deltas, planes of hw contiguous floats at
+ *                  any 4-byte boundary; strides: DEVICE int64 [nplanes][2] (sample, step) in floats; stds: DEVICE fp32 [nplanes];
+ *                  rows / wrows / weights / nw: as ace_diag_window (weights DEVICE fp32 [nw][hw]); rows must not name one row
+ *                  twice (not checked).  partial: DEVICE fp64 scratch of ace_diag_correction_partial_doubles(nplanes, batch,
+ *                  steps, hw) values.  signed_sum, magnitude_sum: DEVICE fp64 [nrows][hw]; series: DEVICE fp64 [2][nrows][n_time].
+ *                  Per element n = fl32(d / std_j), the correctly rounded fp32 quotient (what torch's delta / std gives),
+ *                  widened to fp64 for everything that follows.  With w the weight row wrows[j] and, for a sample b and step t,
+ *                  wmean(x) = sum_p w x / sum_p w over the pixels of non-zero weight:
+ *                    series[0][row][t0 + t] += (1 / batch) sum_b wmean(|n|)
+ *                    series[1][row][t0 + t] += (1 / batch) sum_b sqrt(wmean((n - wmean(n))^2))
+ *                  samples in order.  A pixel of weight 0 is skipped, NaN included; a NaN at non-zero weight propagates; a sample
+ *                  with no weighted pixel gives NaN.  Each wave reduces its 256 pixels in two passes over registers (mean, then
+ *                  the central moment), the waves' partials are merged by Chan's update in a fixed order (lane strides over the
+ *                  partials, then an xor butterfly), so the series agree with a plain fp64 statement to rounding (1e-12), not bit
+ *                  for bit.  And at every pixel p, whatever its weight (a NaN stays a NaN, as in the reference's maps):
+ *                    signed_sum[row][p] += acc_n       magnitude_sum[row][p] += acc_a
+ *                  where acc_n, acc_a start at 0.0 and take n, |n| of (b, t) with b outer and t inner: a host statement in plain
+ *                  fp64 reproduces them bit for bit.  A plane whose rows[j] is outside [0, nrows) or whose wrows[j] is outside
+ *                  [0, nw) contributes to nothing.  One read of the delta planes; no normalised or absolute copy; no atomics, no
+ *                  workgroup waits for another, bitwise repeatable.
+ *                  Refused (ACE_ERR_INVALID, nothing written): nplanes or steps > 65535, batch, hw, nw or nrows < 1, t0 < 0 or
+ *                  t0 + steps > n_time, a NULL argument.  nplanes == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------ */
+int ace_stepdiag_snapshot(const float* const* srcs, const long* src_strides, float* const* dsts, const long* dst_strides, int nplanes,
+                          int batch, long hw, void* stream);
+int ace_stepdiag_delta_window(const float* const* outs, const long* out_strides, float* const* snaps, const long* snap_strides,
+                              int nplanes, int batch, int steps, long hw, void* stream);
+long ace_diag_correction_partial_doubles(int nplanes, int batch, int steps, long hw);
+int ace_diag_correction_window(const float* const* deltas, const long* strides, const float* stds, const int* rows, const int* wrows,
+                               const float* weights, int nw, double* partial, double* signed_sum, double* magnitude_sum,
+                               double* series, int nrows, int n_time, int t0, int nplanes, int batch, int steps, long hw,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Post-step physics (fme/core/step/single_module.py:669-716): the AtmosphereCorrector
  * (fme/core/corrector/atmosphere.py:349-398 order, 404-700 corrections), the prescribed-SST Ocean
  * (fme/core/ocean.py:167-222, fme/core/prescriber.py:54-117) and the prescribed prognostics, applied in place on the
