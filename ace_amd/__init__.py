@@ -19,6 +19,7 @@ from .global_mean_removal import (  # noqa: F401
     PerChannelGlobalMeanRemovalConfig, SharedGlobalMeanRemoval, SharedGlobalMeanRemovalConfig, extra_channel_source_field)
 from .rand import RandomState, randn, randn_like, use_cpu_randn, use_generator  # noqa: F401
 from .mlp import ColumnMLP, MLPConfig  # noqa: F401
+from .landnet import LandNet, LandNetBuilder  # noqa: F401
 from .checkpoint import LoadedStepper, StepperOverrideConfig, apply_stepper_override, load_stepper  # noqa: F401
 from .csfno import NoiseConditionedSFNO, NoiseConditionedSFNOBuilder  # noqa: F401
 from .healpix import CapturedHEALPixForward, HEALPixUNet, HEALPixUNetBuilder  # noqa: F401
@@ -34,6 +35,7 @@ from .derived_forcings import DerivedForcingsConfig, ForcingDeriver, ForcingWind
 from .multi_call import MultiCallConfig  # noqa: F401
 from .stepper import PrognosticState, Stepper  # noqa: F401
 from .ocean_rollout import OceanRolloutEngine  # noqa: F401
+from .land_rollout import LandRolloutEngine  # noqa: F401
 from .coupled import (ComponentConfig, ComponentStepPrediction, CoupledDatasetInfo, CoupledOceanFractionConfig,  # noqa: F401
                       CoupledStepper, CoupledStepperConfig, Coupler, load_coupled_stepper)
 from .coupled_rollout import CoupledEnginePredict, CoupledRolloutEngine, plan_coupled_window  # noqa: F401

@@ -270,6 +270,13 @@ SIGNATURES = {
     # srcs, src_strides, mask_idx, hits, nmask, fill, stage, stage_strides, mean, std, dst, npack, nplanes, batch, hw, stream
     "ace_mask_pack_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    "ace_pixel_mlp_last_error": (c_char_p, []),
+    # n_layers, dims, w_dev, bias_dev, act, embed_layer, stream, handle
+    "ace_pixel_mlp_create": (c_int, [c_int, POINTER(c_int), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int), c_int, c_void_p,
+                                     POINTER(c_void_p)]),
+    "ace_pixel_mlp_destroy": (None, [c_void_p]),
+    # handle, x, embed, y, batch, hw, stream
+    "ace_pixel_mlp_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p]),
     "ace_gmr_chunks": (c_long, [c_long]),
     # srcs, strides, plane_idx, nsrc, partials, batch, K, hw, stream
     "ace_gmr_partials": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_long, c_void_p]),

@@ -293,7 +293,7 @@ def run_evaluator(predict: Callable, data: InferenceData, aggregator, writer=Non
 
 
 class EnginePredict:
-    """``PredictFunction`` on the static-buffer ``RolloutEngine`` (``OceanRolloutEngine`` for a Samudra stepper): one engine per window length (the last window of a
+    """``PredictFunction`` on the static-buffer ``RolloutEngine`` (``OceanRolloutEngine`` for a Samudra stepper, ``LandRolloutEngine`` for a LandNet one): one engine per window length (the last window of a
     rollout may be shorter), built on first use.  Outputs are copied out of the engine's buffers (the next window reuses them)."""
 
     def __init__(self, stepper, batch: int, graph: Optional[str] = "step", labels=None, step_diagnostics: bool = False):
@@ -324,6 +324,8 @@ class EnginePredict:
 
     def __call__(self, initial_condition: TensorDict, forcing: TensorDict,
                  compute_derived_variables: bool = False) -> Tuple[TensorDict, TensorDict]:
+        from .land_rollout import LandRolloutEngine
+        from .landnet import LandNet
         from .ocean_rollout import OceanRolloutEngine
         from .rollout import RolloutEngine
         from .samudra import Samudra
@@ -332,7 +334,8 @@ class EnginePredict:
         eng = self._engines.get(n_steps)
         if eng is None:
             # a Samudra ocean stepper (input / output masking, the ocean corrector) runs on its own engine
-            engine = OceanRolloutEngine if isinstance(self._stepper._step_obj.module.torch_module, Samudra) else RolloutEngine
+            net = self._stepper._step_obj.module.torch_module
+            engine = OceanRolloutEngine if isinstance(net, Samudra) else LandRolloutEngine if isinstance(net, LandNet) else RolloutEngine
             extra = {"step_diagnostics": True} if self._step_diagnostics else {}      # an engine without the option refuses it
             eng = self._engines[n_steps] = engine(self._stepper, batch=self._batch, n_forward_steps=n_steps, graph=self._graph,
                                                   **extra)

@@ -25,8 +25,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .masking import StaticSpatialMasking, _check
-from .rollout import WindowEngine, _nan_to_zero
+from .rollout import MaskedWindowEngine, _nan_to_zero
 from .stepper import Stepper
 
 
@@ -51,7 +50,7 @@ def _refuse(what: str) -> NotImplementedError:
     return NotImplementedError(f"OceanRolloutEngine: {what}; run this stepper through Stepper.predict")
 
 
-class OceanRolloutEngine(WindowEngine):
+class OceanRolloutEngine(MaskedWindowEngine):
     @staticmethod
     def check_supported(stepper: Stepper):
         """The refusals that need no device, raised before any device work (the constructor's first act).  Returns the stepper's
@@ -82,13 +81,7 @@ class OceanRolloutEngine(WindowEngine):
         corrector = step._corrector
         if corrector is not None and not isinstance(corrector, (OceanCorrector, IceCorrector)):
             raise _refuse(f"a {type(corrector).__name__} is not an ocean corrector (nor a sea-ice corrector)")
-        in_mask = stepper._input_process_func if isinstance(stepper._input_process_func, StaticSpatialMasking) else None
-        out_mask = stepper._output_masking if isinstance(stepper._output_masking, StaticSpatialMasking) else None
-        for m in (in_mask, out_mask):
-            if m is not None:
-                for k, t in m._mask.masks.items():
-                    if tuple(t.shape) != tuple(step._img_shape):
-                        raise _refuse(f"the mask '{k}' of shape {tuple(t.shape)} is not a 2-D {tuple(step._img_shape)} plane")
+        in_mask, out_mask = MaskedWindowEngine._static_maskers(stepper, _refuse)
         if next(net.parameters()).device.type != "cuda":
             raise RuntimeError("OceanRolloutEngine runs on an MI355X: load the stepper onto a 'cuda' device (there is no CPU path)")
         return in_mask, out_mask
@@ -107,7 +100,6 @@ class OceanRolloutEngine(WindowEngine):
         super().__init__(stepper, net, batch, n_forward_steps, graph)
         dev, B, T, H, W, HW = self.device, batch, n_forward_steps, self.H, self.W, self.HW
         f32 = dict(dtype=torch.float32, device=dev)
-        i64 = dict(dtype=torch.int64, device=dev)
 
         # ---- the corrector: which masked planes it reads (probed once on the unmasked views), staged by the pack
         in_plan = in_mask.plan(self.in_names) if in_mask is not None else [(None, None)] * len(self.in_names)
@@ -144,13 +136,7 @@ class OceanRolloutEngine(WindowEngine):
         # ---- step tables of ace_mask_pack_normalize: planes = the inputs (packed), then the extra staged next-step planes
         planes = self.in_names + extra
         self._nplanes = n = len(planes)
-        if in_mask is not None:
-            self._in_idx, self._in_fill = in_mask.device_tables(planes, dev, (H, W))
-            _, self._in_hits = in_mask.hit_planes(dev, (H, W))
-        else:
-            self._in_idx = torch.full((n,), -1, dtype=torch.int32, device=dev)
-            self._in_fill = torch.zeros(n, **f32)
-            self._in_hits = None
+        self._build_input_mask(in_mask, planes)
         rows = []
         for s in range(T):
             srcs = [self.in_plane(o, s) for o in self.in_names] + [self.next_plane(o, s) for o in extra]
@@ -170,16 +156,7 @@ class OceanRolloutEngine(WindowEngine):
                 self._fields.append(self._fused_corrector.fields(inp, gen, nxt))
 
         # ---- the output masker, in place on out[:, s]
-        self._out_names_masked = []
-        if out_mask is not None:
-            self._out_names_masked = [o for o, (k, _) in zip(self.out_names, out_mask.plan(self.out_names)) if k is not None]
-        self._out_mask = out_mask
-        if self._out_names_masked:
-            self._out_idx, self._out_fill = out_mask.device_tables(self._out_names_masked, dev, (H, W))
-            _, self._out_hits = out_mask.hit_planes(dev, (H, W))
-            self._omask_ptrs, self._omask_addr = self._table([[self.out_plane(o, s).data_ptr() for o in self._out_names_masked]
-                                                              for s in range(T)])
-            self._omask_strides = torch.full((len(self._out_names_masked),), T * HW, **i64)
+        self._build_output_mask(out_mask)
 
         self._captured = None          # graph="step": CapturedSamudraForward on self.x
 
@@ -187,13 +164,8 @@ class OceanRolloutEngine(WindowEngine):
     def _enqueue_step(self, s: int, replay_forward: bool):
         L = _lib.lib()
         stream = _lib.current_stream()
-        B, HW = self.B, self.HW
         srcs, src_strides, stage, stage_strides = self._pack_addr[s]
-        hits = self._in_hits
-        _check(L.ace_mask_pack_normalize(srcs, src_strides, self._in_idx.data_ptr(), hits.data_ptr() if hits is not None else None,
-                                         hits.shape[0] if hits is not None else 0, self._in_fill.data_ptr(), stage, stage_strides,
-                                         self.in_mean.data_ptr(), self.in_std.data_ptr(), self.x.data_ptr(), len(self.in_names),
-                                         self._nplanes, B, HW, stream))
+        self._mask_pack_normalize(L, stream, srcs, src_strides, stage, stage_strides, self._nplanes)
         if self._fill_in:
             _nan_to_zero(self.x)
         if replay_forward:
@@ -204,11 +176,7 @@ class OceanRolloutEngine(WindowEngine):
         self._unpack(L, stream, y, self._dst_ptr_addr[s], self._dst_strides)
         if self._fused_corrector is not None:
             self._fused_corrector.apply(self._fields[s], stream)
-        if self._out_names_masked:
-            a = self._omask_addr[s]
-            st = self._omask_strides.data_ptr()
-            _check(L.ace_mask_planes(a, st, a, st, self._out_idx.data_ptr(), self._out_hits.data_ptr(), self._out_hits.shape[0],
-                                     self._out_fill.data_ptr(), len(self._out_names_masked), B, HW, stream))
+        self._mask_outputs(L, stream, s)
 
     def _prepare_window(self):
         step = self.stepper._step_obj
@@ -221,7 +189,3 @@ class OceanRolloutEngine(WindowEngine):
             self._captured = CapturedSamudraForward(self.net, self.x)       # warm-up outside capture, then capture
             self.x = self._captured.x
         return key
-
-    def set_labels(self, labels) -> None:
-        if labels is not None:
-            raise TypeError("Labels are not allowed for unconditional models")

@@ -17,7 +17,8 @@ per-sample means of the step's own inputs, the shift added in front of the norma
 the in_names) and 3 by ace_gmr_unpack_denormalize (the shift taken off the listed outputs): csrc/gmr.hip.  Without the option the
 engine issues exactly the calls above.
 
-`WindowEngine` is what every static-buffer engine shares (`OceanRolloutEngine`, ocean_rollout.py, is the other): the buffers,
+`WindowEngine` is what every static-buffer engine shares (`OceanRolloutEngine`, ocean_rollout.py, and `LandRolloutEngine`,
+land_rollout.py, are the others; `MaskedWindowEngine` holds the static-masking tables those two share): the buffers,
 the one statement of the window layout (`in_plane` / `next_plane` / `out_plane`), the tail of a forward, the window graph and
 load / predict / continue_from_last.  An engine supplies its pack and forward (`_enqueue_step`), what its captured graphs depend
 on (`_prepare_window`) and what `predict` carries in `stepper_state`."""
@@ -203,6 +204,74 @@ class WindowEngine:
         """Carry the final prognostic state into the initial-condition slot (next window of a long rollout)."""
         for n in self.prognostic:
             self.ic[n].copy_(self.out[n][:, -1:])
+
+
+class MaskedWindowEngine(WindowEngine):
+    """What the engines of steppers with static spatial masking share (``OceanRolloutEngine``, ``LandRolloutEngine``): the steppers'
+    maskers and their shape check, the device tables of the masking pack (ace_mask_pack_normalize) and of the provider's output
+    masker (ace_mask_planes, in place on out[:, s]), and the two launches."""
+
+    @staticmethod
+    def _static_maskers(stepper: Stepper, refuse):
+        """The stepper's (input masker, output masker), each None when it is no static spatial masking; ``refuse(what)`` builds the
+        engine's exception for a mask that is not a 2-D plane of the grid."""
+        from .masking import StaticSpatialMasking
+        step = stepper._step_obj
+        in_mask = stepper._input_process_func if isinstance(stepper._input_process_func, StaticSpatialMasking) else None
+        out_mask = stepper._output_masking if isinstance(stepper._output_masking, StaticSpatialMasking) else None
+        for m in (in_mask, out_mask):
+            if m is not None:
+                for k, t in m._mask.masks.items():
+                    if tuple(t.shape) != tuple(step._img_shape):
+                        raise refuse(f"the mask '{k}' of shape {tuple(t.shape)} is not a 2-D {tuple(step._img_shape)} plane")
+        return in_mask, out_mask
+
+    def _build_input_mask(self, in_mask, planes) -> None:
+        """mask index, fill and hit planes of ``planes`` (the names the pack walks) for ace_mask_pack_normalize"""
+        dev, n = self.device, len(planes)
+        if in_mask is not None:
+            self._in_idx, self._in_fill = in_mask.device_tables(planes, dev, (self.H, self.W))
+            _, self._in_hits = in_mask.hit_planes(dev, (self.H, self.W))
+        else:
+            self._in_idx = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            self._in_fill = torch.zeros(n, dtype=torch.float32, device=dev)
+            self._in_hits = None
+
+    def _mask_pack_normalize(self, L, stream, srcs, src_strides, stage, stage_strides, nplanes: int) -> None:
+        """One ace_mask_pack_normalize of the table rows at these addresses into self.x (``stage``: None for no staged planes)."""
+        from .masking import _check
+        hits = self._in_hits
+        _check(L.ace_mask_pack_normalize(srcs, src_strides, self._in_idx.data_ptr(), hits.data_ptr() if hits is not None else None,
+                                         hits.shape[0] if hits is not None else 0, self._in_fill.data_ptr(), stage, stage_strides,
+                                         self.in_mean.data_ptr(), self.in_std.data_ptr(), self.x.data_ptr(), len(self.in_names),
+                                         nplanes, self.B, self.HW, stream))
+
+    def _build_output_mask(self, out_mask) -> None:
+        """the output names the provider masks, and their per-step pointer tables"""
+        dev, T, HW = self.device, self.T, self.HW
+        self._out_names_masked = []
+        if out_mask is not None:
+            self._out_names_masked = [o for o, (k, _) in zip(self.out_names, out_mask.plan(self.out_names)) if k is not None]
+        self._out_mask = out_mask
+        if self._out_names_masked:
+            self._out_idx, self._out_fill = out_mask.device_tables(self._out_names_masked, dev, (self.H, self.W))
+            _, self._out_hits = out_mask.hit_planes(dev, (self.H, self.W))
+            self._omask_ptrs, self._omask_addr = self._table([[self.out_plane(o, s).data_ptr() for o in self._out_names_masked]
+                                                              for s in range(T)])
+            self._omask_strides = torch.full((len(self._out_names_masked),), T * HW, dtype=torch.int64, device=dev)
+
+    def _mask_outputs(self, L, stream, s: int) -> None:
+        """The provider's output masker on out[:, s], in place: one ace_mask_planes, none when no output is masked."""
+        from .masking import _check
+        if self._out_names_masked:
+            a = self._omask_addr[s]
+            st = self._omask_strides.data_ptr()
+            _check(L.ace_mask_planes(a, st, a, st, self._out_idx.data_ptr(), self._out_hits.data_ptr(), self._out_hits.shape[0],
+                                     self._out_fill.data_ptr(), len(self._out_names_masked), self.B, self.HW, stream))
+
+    def set_labels(self, labels) -> None:
+        if labels is not None:
+            raise TypeError("Labels are not allowed for unconditional models")
 
 
 class RolloutEngine(WindowEngine):

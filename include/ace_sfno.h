@@ -1272,6 +1272,65 @@ int ace_ice_budget_apply(const ace_ice_fields* fields, double timestep, int batc
 /* Launch counter of this process: flags passes, apply passes and flag clearings enqueued so far (any may be NULL). */
 int ace_ice_budget_launches(long* flags, long* apply, long* clears);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-pixel MLP (csrc/pixel_mlp.hip): a chain of 1 x 1 convolutions - the LandNet family, fme/ace/models/land/land_net.py - as
+ * one launch per forward in exact fp32 (v_mfma_f32_16x16x4_f32), the hidden activations staying in registers.
+ *
+ * create(n_layers, dims[n_layers + 1], w_dev[], bias_dev[], act[], embed_layer, stream, &handle) reads the DEVICE weights
+ * (w_dev[l]: row-major [dims[l + 1]][dims[l]] fp32; bias_dev NULL or bias_dev[l] NULL: no bias; act[l] one of ACE_PIXEL_MLP_ACT_*)
+ * once, synchronising `stream`, into one device blob in the kernel's fragment order; the handle does not refer to the caller's
+ * arrays afterwards (a changed weight needs a new handle).  embed_layer: the layer after whose activation a plane stack
+ * [dims[embed_layer + 1]][hw] is added, -1 for none.
+ * forward(handle, x, embed, y, batch, hw, stream): x [batch][dims[0]][hw], y [batch][dims[n_layers]][hw], embed
+ * [dims[embed_layer + 1]][hw] (ignored without an embedding layer), contiguous fp32, x and y not overlapping.  One launch,
+ * stream-ordered, no allocation, no host synchronisation: capturable.
+ *
+ * The statement (tests/_pixel_mlp_ref.py is this text in numpy).  Per pixel, a = the dims[0] inputs; per layer l with
+ * K = dims[l], O = dims[l + 1], for every o < O:
+ *     acc = bias[l][o] (+0.0f without a bias)
+ *     for t in 0 .. ceil(K / 16) - 1:  for r in 0 .. 3:  for g in 0 .. 3:
+ *         k = 16 t + 4 g + r;  if k < K:  acc = fmaf(w[l][o][k], a[k], acc)
+ *     if act[l] == ACE_PIXEL_MLP_ACT_RELU:  acc = acc < 0 ? +0.0f : acc         (torch.relu: NaN stays NaN, -0.0f stays -0.0f)
+ *     if l == embed_layer:  acc = acc + embed[o][pixel]                         (one fp32 addition)
+ *     a'[o] = acc
+ * Every layer, the first included, uses that k order (the order in which an MFMA accumulator tile is the next MFMA's operand).
+ * fmaf is the single-rounding fused multiply-add; nothing else is fused (contraction is off in the translation unit) and
+ * subnormals are kept.  Channel padding up to the 16-wide tile contributes nothing, also beside Inf or NaN: a padded
+ * activation is forced to +0.0f and meets a padded weight of -0.0f, and x + (-0.0f) == x bit for bit for every x.  A pixel's
+ * result depends on that pixel only.
+ *
+ * Any hw >= 1 and any 4-byte alignment are accepted.  Widths up to ACE_PIXEL_MLP_NARROW_WIDTH: a wave carries
+ * ACE_PIXEL_MLP_NARROW_TILES tiles of ACE_PIXEL_MLP_TILE pixels, with 16-byte accesses when hw % 4 == 0 and x, y and embed are
+ * 16-byte aligned (one decision for the launch), 4-byte ones otherwise; wider chains carry ACE_PIXEL_MLP_WIDE_TILES tile.  A
+ * workgroup is ACE_PIXEL_MLP_WAVES waves, one (sample, run of pixels) unit per wave and pass; at most ACE_PIXEL_MLP_MAX_GRID
+ * workgroups are launched, so a workgroup loops once batch * ceil(hw / (tiles * ACE_PIXEL_MLP_TILE)) exceeds
+ * ACE_PIXEL_MLP_MAX_GRID * ACE_PIXEL_MLP_WAVES.  The weight blob - per layer ceil(O / 16) * 16 bias floats and
+ * ceil(O / 16) * ceil(K / 16) * 256 fragment floats - is copied into LDS once per workgroup when it is at most
+ * ACE_PIXEL_MLP_LDS_BYTES and read from global memory, fragment by fragment, otherwise; both kernels have both forms and the
+ * arithmetic does not depend on the form.
+ *
+ * Refused (ACE_ERR_INVALID, the reason behind ace_pixel_mlp_last_error, nothing launched): a NULL handle, x or y; batch < 1;
+ * hw < 1; embed NULL where the handle has an embedding layer; in create: n_layers outside 1 .. ACE_PIXEL_MLP_MAX_LAYERS, a
+ * width outside 1 .. ACE_PIXEL_MLP_MAX_WIDTH, a NULL weight, an unknown activation, embed_layer outside -1 .. n_layers - 1.
+ * ------------------------------------------------------------------------------------------ */
+#define ACE_PIXEL_MLP_MAX_LAYERS 8
+#define ACE_PIXEL_MLP_MAX_WIDTH 256
+#define ACE_PIXEL_MLP_ACT_NONE 0
+#define ACE_PIXEL_MLP_ACT_RELU 1
+#define ACE_PIXEL_MLP_TILE 16                  /* pixels of one MFMA tile */
+#define ACE_PIXEL_MLP_WAVES 4                  /* waves of a workgroup */
+#define ACE_PIXEL_MLP_NARROW_WIDTH 64          /* every width <= this: the narrow kernel */
+#define ACE_PIXEL_MLP_NARROW_TILES 4           /* pixel tiles per wave, narrow */
+#define ACE_PIXEL_MLP_WIDE_TILES 1             /* pixel tiles per wave, wide */
+#define ACE_PIXEL_MLP_MAX_GRID 512             /* workgroups of a launch */
+#define ACE_PIXEL_MLP_LDS_BYTES 65536          /* a weight blob up to this size is copied into LDS, a larger one streamed from global memory */
+
+const char* ace_pixel_mlp_last_error(void);
+int ace_pixel_mlp_create(int n_layers, const int* dims, const float* const* w_dev, const float* const* bias_dev, const int* act,
+                         int embed_layer, void* stream, void** handle);
+void ace_pixel_mlp_destroy(void* handle);
+int ace_pixel_mlp_forward(void* handle, const float* x, const float* embed, float* y, int batch, long hw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
