@@ -20,6 +20,8 @@ from .global_mean_removal import (  # noqa: F401
 from .rand import RandomState, randn, randn_like, use_cpu_randn, use_generator  # noqa: F401
 from .mlp import ColumnMLP, MLPConfig  # noqa: F401
 from .landnet import LandNet, LandNetBuilder  # noqa: F401
+from .ankur import AnkurLocalNet, AnkurLocalNetBuilder  # noqa: F401
+from .disco import DiscoTable, disco_table  # noqa: F401
 from .checkpoint import LoadedStepper, StepperOverrideConfig, apply_stepper_override, load_stepper  # noqa: F401
 from .csfno import NoiseConditionedSFNO, NoiseConditionedSFNOBuilder  # noqa: F401
 from .healpix import CapturedHEALPixForward, HEALPixUNet, HEALPixUNetBuilder  # noqa: F401

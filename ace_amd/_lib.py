@@ -277,6 +277,17 @@ SIGNATURES = {
     "ace_pixel_mlp_destroy": (None, [c_void_p]),
     # handle, x, embed, y, batch, hw, stream
     "ace_pixel_mlp_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p]),
+    # ... embed_layer, embed_before_act, stream, handle
+    "ace_pixel_mlp_create2": (c_int, [c_int, POINTER(c_int), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int), c_int, c_int, c_void_p,
+                                      POINTER(c_void_p)]),
+    "ace_disco_last_error": (c_char_p, []),
+    # H, W, K, row_off (host), hi (host), wi (host), vals (host), w_dev, in_chans, out_chans, groups, act, has_embed, stream, handle
+    "ace_disco_create": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                 c_int, c_void_p, POINTER(c_void_p)]),
+    "ace_disco_destroy": (None, [c_void_p]),
+    # handle, x, embed, y, batch, stream
+    "ace_disco_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "ace_disco_info": (c_int, [c_void_p, POINTER(c_long)]),
     "ace_gmr_chunks": (c_long, [c_long]),
     # srcs, strides, plane_idx, nsrc, partials, batch, K, hw, stream
     "ace_gmr_partials": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_long, c_void_p]),

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/ace_sfno.h"
+#include "pixel_act.h"
 
 #pragma clang fp contract(off)
 
@@ -51,6 +52,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct PMArgs {
     int n_layers, embed_layer;
+    int embed_first;                           // the embedding is added before the activation of its layer (create2)
     int dims[ACE_PIXEL_MLP_MAX_LAYERS + 1];
     int act[ACE_PIXEL_MLP_MAX_LAYERS];
     int woff[ACE_PIXEL_MLP_MAX_LAYERS];        // floats into the blob: fragments of layer l
@@ -60,6 +62,7 @@ struct PMArgs {
 
 struct PixelMlp {
     PMArgs a;
+    bool soft = false;                         // see pixel_mlp_unit
     float* blob = nullptr;
     int width = 0;                             // the largest of dims
 };
@@ -90,7 +93,9 @@ __device__ __forceinline__ void load_tile(const float* base, long hw, long pix, 
     }
 }
 
-template <int MAXT, int NPT, bool VEC>
+// SOFT: some layer is GELU / SiLU or adds its embedding before the activation (create2).  The chains that none / ReLU with the
+// embedding after the activation describe run the SOFT == false instantiations: the code they ran before those options existed.
+template <int MAXT, int NPT, bool VEC, bool SOFT>
 __device__ __forceinline__ void pixel_mlp_unit(const PMArgs& a, const float* W, const float* xb, const float* embed, float* yb,
                                                long hw, long pix, int lane) {
     const int g = lane >> 4;
@@ -112,7 +117,9 @@ __device__ __forceinline__ void pixel_mlp_unit(const PMArgs& a, const float* W, 
         const int nti = (din + TILE - 1) / TILE, nto = (dout + TILE - 1) / TILE;
         const float* wl = W + a.woff[l] + lane;
         const float* bl = W + a.boff[l] + 4 * g;
-        const bool relu = a.act[l] != 0, emb = l == a.embed_layer;
+        const int act = a.act[l];
+        const bool relu = act != 0, emb = l == a.embed_layer;
+        const bool emb_first = SOFT && emb && a.embed_first;
         f32x4 nxt[MAXT][NPT];
 #pragma unroll
         for (int to = 0; to < MAXT; ++to) {
@@ -140,8 +147,14 @@ __device__ __forceinline__ void pixel_mlp_unit(const PMArgs& a, const float* W, 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float v = nxt[to][j][r];
-                        if (relu) v = v < 0.0f ? 0.0f : v;              // torch.relu: NaN stays NaN, -0 stays -0
-                        if (emb) v = v + ev[j][r];
+                        if (SOFT) {
+                            if (emb_first) v = v + ev[j][r];
+                            v = pixel_act_rt(act, v);
+                            if (emb && !emb_first) v = v + ev[j][r];
+                        } else {
+                            if (relu) v = pixel_act<ACE_PIXEL_MLP_ACT_RELU>(v);   // torch.relu: NaN stays NaN, -0 stays -0
+                            if (emb) v = v + ev[j][r];
+                        }
                         if (TILE * to + 4 * g + r >= dout) v = 0.0f;    // a padded channel is +0, whatever 0 * Inf made of it
                         nxt[to][j][r] = v;
                     }
@@ -180,7 +193,7 @@ __device__ __forceinline__ void pixel_mlp_unit(const PMArgs& a, const float* W, 
 }
 
 // unit u = (sample, run of 16 NPT pixels); wave w of workgroup k takes the units 4 k + w, + 4 gridDim.x, ...
-template <int MAXT, int NPT, bool LDSW>
+template <int MAXT, int NPT, bool LDSW, bool SOFT>
 __global__ __launch_bounds__(NT) void pixel_mlp_kernel(PMArgs a, const float* __restrict__ blob, const float* __restrict__ x,
                                                        const float* __restrict__ embed, float* __restrict__ y, long hw,
                                                        long units_per_image, long nunits) {
@@ -202,13 +215,13 @@ __global__ __launch_bounds__(NT) void pixel_mlp_kernel(PMArgs a, const float* __
         const float* xb = x + b * din * hw;
         float* yb = y + b * dlast * hw;
         if (vec)
-            pixel_mlp_unit<MAXT, NPT, NPT == 4>(a, W, xb, embed, yb, hw, pix, lane);
+            pixel_mlp_unit<MAXT, NPT, NPT == 4, SOFT>(a, W, xb, embed, yb, hw, pix, lane);
         else
-            pixel_mlp_unit<MAXT, NPT, false>(a, W, xb, embed, yb, hw, pix, lane);
+            pixel_mlp_unit<MAXT, NPT, false, SOFT>(a, W, xb, embed, yb, hw, pix, lane);
     }
 }
 
-template <int MAXT, int NPT>
+template <int MAXT, int NPT, bool SOFT>
 int launch(const PixelMlp* h, const float* x, const float* embed, float* y, int batch, long hw, hipStream_t st) {
     const long wp = (long)TILE * NPT;
     const long upi = (hw + wp - 1) / wp;
@@ -217,10 +230,10 @@ int launch(const PixelMlp* h, const float* x, const float* embed, float* y, int 
     if (nwg > ACE_PIXEL_MLP_MAX_GRID) nwg = ACE_PIXEL_MLP_MAX_GRID;
     const size_t bytes = (size_t)h->a.blob_floats * sizeof(float);
     if (bytes <= (size_t)LDS_BYTES)
-        hipLaunchKernelGGL((pixel_mlp_kernel<MAXT, NPT, true>), dim3((unsigned)nwg), dim3(NT), bytes, st, h->a, h->blob, x, embed, y,
+        hipLaunchKernelGGL((pixel_mlp_kernel<MAXT, NPT, true, SOFT>), dim3((unsigned)nwg), dim3(NT), bytes, st, h->a, h->blob, x, embed, y,
                            hw, upi, nunits);
     else
-        hipLaunchKernelGGL((pixel_mlp_kernel<MAXT, NPT, false>), dim3((unsigned)nwg), dim3(NT), 0, st, h->a, h->blob, x, embed, y, hw,
+        hipLaunchKernelGGL((pixel_mlp_kernel<MAXT, NPT, false, SOFT>), dim3((unsigned)nwg), dim3(NT), 0, st, h->a, h->blob, x, embed, y, hw,
                            upi, nunits);
     PM_TRY(hipGetLastError());
     return ACE_OK;
@@ -228,8 +241,8 @@ int launch(const PixelMlp* h, const float* x, const float* embed, float* y, int 
 
 }  // namespace
 
-extern "C" int ace_pixel_mlp_create(int n_layers, const int* dims, const float* const* w_dev, const float* const* bias_dev,
-                                    const int* act, int embed_layer, void* stream, void** handle) {
+extern "C" int ace_pixel_mlp_create2(int n_layers, const int* dims, const float* const* w_dev, const float* const* bias_dev,
+                                     const int* act, int embed_layer, int embed_before_act, void* stream, void** handle) {
     if (!handle) return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: null handle pointer");
     *handle = nullptr;
     if (n_layers < 1 || n_layers > ACE_PIXEL_MLP_MAX_LAYERS)
@@ -242,17 +255,24 @@ extern "C" int ace_pixel_mlp_create(int n_layers, const int* dims, const float* 
                                                std::to_string(ACE_PIXEL_MLP_MAX_WIDTH) + ")");
     for (int l = 0; l < n_layers; ++l) {
         if (!w_dev[l]) return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: null weight");
-        if (act[l] != ACE_PIXEL_MLP_ACT_NONE && act[l] != ACE_PIXEL_MLP_ACT_RELU)
-            return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: act must be ACE_PIXEL_MLP_ACT_NONE or ACE_PIXEL_MLP_ACT_RELU");
+        if (act[l] != ACE_PIXEL_MLP_ACT_NONE && act[l] != ACE_PIXEL_MLP_ACT_RELU && act[l] != ACE_PIXEL_MLP_ACT_GELU &&
+            act[l] != ACE_PIXEL_MLP_ACT_SILU)
+            return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create2: act must be one of ACE_PIXEL_MLP_ACT_*");
     }
     if (embed_layer < -1 || embed_layer >= n_layers)
         return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: need -1 <= embed_layer < n_layers");
+    if (embed_before_act != 0 && embed_before_act != 1)
+        return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create2: embed_before_act must be 0 or 1");
     hipStream_t st = static_cast<hipStream_t>(stream);
     PixelMlp* h = new PixelMlp();
     PMArgs& a = h->a;
     a = PMArgs{};
     a.n_layers = n_layers;
     a.embed_layer = embed_layer;
+    a.embed_first = embed_layer >= 0 ? embed_before_act : 0;
+    h->soft = a.embed_first != 0;
+    for (int l = 0; l < n_layers; ++l)
+        if (act[l] == ACE_PIXEL_MLP_ACT_GELU || act[l] == ACE_PIXEL_MLP_ACT_SILU) h->soft = true;
     long total = 0;
     for (int l = 0; l <= n_layers; ++l) {
         a.dims[l] = dims[l];
@@ -308,6 +328,18 @@ extern "C" int ace_pixel_mlp_create(int n_layers, const int* dims, const float* 
     return ACE_OK;
 }
 
+extern "C" int ace_pixel_mlp_create(int n_layers, const int* dims, const float* const* w_dev, const float* const* bias_dev,
+                                    const int* act, int embed_layer, void* stream, void** handle) {
+    // its contract as it stood: the two activations it knew; GELU and SiLU come through create2
+    if (handle && act && n_layers >= 1 && n_layers <= ACE_PIXEL_MLP_MAX_LAYERS)
+        for (int l = 0; l < n_layers; ++l)
+            if (act[l] != ACE_PIXEL_MLP_ACT_NONE && act[l] != ACE_PIXEL_MLP_ACT_RELU) {
+                *handle = nullptr;
+                return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: act must be ACE_PIXEL_MLP_ACT_NONE or ACE_PIXEL_MLP_ACT_RELU");
+            }
+    return ace_pixel_mlp_create2(n_layers, dims, w_dev, bias_dev, act, embed_layer, 0, stream, handle);
+}
+
 extern "C" void ace_pixel_mlp_destroy(void* handle) {
     PixelMlp* h = static_cast<PixelMlp*>(handle);
     if (!h) return;
@@ -324,7 +356,10 @@ extern "C" int ace_pixel_mlp_forward(void* handle, const float* x, const float* 
         return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_forward: the handle was created with an embedding layer: embed must not be NULL");
     if (h->a.embed_layer < 0) embed = nullptr;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    constexpr int NARROW = ACE_PIXEL_MLP_NARROW_WIDTH / ACE_PIXEL_MLP_TILE, WIDE = ACE_PIXEL_MLP_MAX_WIDTH / ACE_PIXEL_MLP_TILE;
     if (h->width <= ACE_PIXEL_MLP_NARROW_WIDTH)
-        return launch<ACE_PIXEL_MLP_NARROW_WIDTH / ACE_PIXEL_MLP_TILE, ACE_PIXEL_MLP_NARROW_TILES>(h, x, embed, y, batch, hw, st);
-    return launch<ACE_PIXEL_MLP_MAX_WIDTH / ACE_PIXEL_MLP_TILE, ACE_PIXEL_MLP_WIDE_TILES>(h, x, embed, y, batch, hw, st);
+        return h->soft ? launch<NARROW, ACE_PIXEL_MLP_NARROW_TILES, true>(h, x, embed, y, batch, hw, st)
+                       : launch<NARROW, ACE_PIXEL_MLP_NARROW_TILES, false>(h, x, embed, y, batch, hw, st);
+    return h->soft ? launch<WIDE, ACE_PIXEL_MLP_WIDE_TILES, true>(h, x, embed, y, batch, hw, st)
+                   : launch<WIDE, ACE_PIXEL_MLP_WIDE_TILES, false>(h, x, embed, y, batch, hw, st);
 }

@@ -414,8 +414,11 @@ class SingleModuleStep:
         module = dict(state["module"])
         if "module.device_buffer" in module:
             del module["module.device_buffer"]
-        # checkpoints written through DummyWrapper/DDP carry a "module." prefix (non_distributed.py:15-28)
-        if module and all(k.startswith("module.") or k == "label_encoding" for k in module):
+        # checkpoints written through DummyWrapper/DDP carry a "module." prefix (non_distributed.py:15-28); a family whose own keys
+        # begin with "module." (AnkurLocalNet's wrapper) keeps them when the state is already its own (this step's get_state)
+        own = set(self.module.torch_module.state_dict())
+        if module and all(k.startswith("module.") or k == "label_encoding" for k in module) and \
+                not {k for k in module if k != "label_encoding"} <= own:
             module = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in module.items()}
         self.module.load_state(module)
         if self.secondary_decoder is not None and state.get("secondary_decoder") is not None:

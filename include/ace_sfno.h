@@ -1317,6 +1317,8 @@ int ace_ice_budget_launches(long* flags, long* apply, long* clears);
 #define ACE_PIXEL_MLP_MAX_WIDTH 256
 #define ACE_PIXEL_MLP_ACT_NONE 0
 #define ACE_PIXEL_MLP_ACT_RELU 1
+#define ACE_PIXEL_MLP_ACT_GELU 2               /* 0.5 v (1 + erff(v / sqrt 2)): nn.GELU(); held to torch's fp32 error, not to bits */
+#define ACE_PIXEL_MLP_ACT_SILU 3               /* v / (1 + expf(-v)): nn.SiLU(); likewise */
 #define ACE_PIXEL_MLP_TILE 16                  /* pixels of one MFMA tile */
 #define ACE_PIXEL_MLP_WAVES 4                  /* waves of a workgroup */
 #define ACE_PIXEL_MLP_NARROW_WIDTH 64          /* every width <= this: the narrow kernel */
@@ -1330,6 +1332,85 @@ int ace_pixel_mlp_create(int n_layers, const int* dims, const float* const* w_de
                          int embed_layer, void* stream, void** handle);
 void ace_pixel_mlp_destroy(void* handle);
 int ace_pixel_mlp_forward(void* handle, const float* x, const float* embed, float* y, int batch, long hw, void* stream);
+/* create with one more argument: embed_before_act != 0 moves the embedding's addition in front of the activation of layer
+ * embed_layer (acc = act(acc + embed[o][pixel]): AnkurLocalNet's Conv2d -> AddPosEmbed -> activation), and act[l] may also be
+ * ACE_PIXEL_MLP_ACT_GELU or ACE_PIXEL_MLP_ACT_SILU (create goes on refusing them).  On what create accepts, create2(..., 0) is
+ * create: the same blob, the same kernels, the same bytes - a chain of none / ReLU with the embedding after the activation runs the
+ * instantiations it ran before these options existed.  An embed_before_act other than 0 or 1 is refused. */
+int ace_pixel_mlp_create2(int n_layers, const int* dims, const float* const* w_dev, const float* const* bias_dev, const int* act,
+                          int embed_layer, int embed_before_act, void* stream, void** handle);
+
+/* ------------------------------------------------------------------------------------------
+ * DISCO convolution on the sphere (csrc/disco.hip): the first layer of AnkurLocalNet (fme/core/models/conditional_sfno/ankur.py)
+ * and the filter of LocalNet's "disco" blocks (fme/core/disco/_convolution.py) - the contraction of the input with the sparse psi
+ * table, the grouped mix with the weight, an optional positional embedding and the activation - as ONE launch in exact fp32.  The
+ * reference goes through rfft, a banded einsum, irfft and a grouped einsum; the operator itself is a short sum per output pixel.
+ *
+ * create(H, W, K, row_off, hi, wi, vals, w_dev, in_chans, out_chans, groups, act, has_embed, stream, &handle): the psi table
+ * (ace_amd/disco.py) in HOST memory - row_off [H + 1] (long), and per support point the input row hi, the input column wi at
+ * output column 0 (ascending (hi, wi) within an output row) and K fp32 values vals[point][k]; the DEVICE weight w_dev
+ * [out_chans][in_chans / groups][K], read once, synchronising `stream`.  K = ks * ks, ks = 1 .. 5.  groups divides in_chans and
+ * out_chans (the reference passes their gcd).  act: ACE_DISCO_ACT_*.  create builds one device blob (row records, point offsets,
+ * psi, the unit list, the weight in MFMA fragment order) and the unit list (csrc/disco_units.h) once; the handle does not refer
+ * to the caller's arrays afterwards.
+ * forward(handle, x, embed, y, batch, stream): x [batch][in_chans][H][W], y [batch][out_chans][H][W], embed [out_chans][H][W]
+ * (ignored when has_embed == 0), contiguous fp32, any 4-byte alignment, x and y not overlapping.  One launch, stream-ordered, no
+ * allocation, no host synchronisation, no atomics: capturable, and two runs are bitwise identical.
+ * info(handle, out[4]): units of a launch per sample, the heaviest unit's cost, the cost of all units, the launch's LDS bytes.
+ *
+ * The statement (tests/_disco_ref.py is this text in numpy).  Exact fp32; per sample b, output row ho, output column wo, with
+ * gs = in_chans / groups and opg = out_chans / groups:
+ *     for c < in_chans, k < K:
+ *         z[c][k] = +0.0f
+ *         for e over the points of row ho in table order:
+ *             z[c][k] = fmaf(vals[e][k], x[b][c][hi_e][(wi_e + wo) mod W], z[c][k])
+ *     for o < out_chans, with g = o / opg:
+ *         acc = +0.0f
+ *         for j = 0 .. gs * K - 1, in ascending order, j = c' * K + k:
+ *             acc = fmaf(w[o][c'][k], z[g * gs + c'][k], acc)
+ *         if has_embed:  acc = acc + embed[o][ho][wo]                 (before the activation, as AddPosEmbed stands in the net)
+ *         y[b][o][ho][wo] = act(acc)
+ * fmaf is the single-rounding fused multiply-add; nothing else is fused and subnormals are kept.  Activations: NONE; RELU
+ * acc < 0 ? +0.0f : acc (NaN stays NaN, -0.0f stays -0.0f); GELU 0.5 acc (1 + erff(acc / sqrt 2)); SILU acc / (1 + expf(-acc)) -
+ * the last two with this toolchain's erff / expf, held to torch's own fp32 error and not to bits.  A point whose value is exactly
+ * 0 is a term like any other: 0 * Inf is NaN.  A NaN or Inf at x[b][c][p] reaches exactly the outputs of c's group whose support
+ * holds p: groups are contracted one by one (no block-diagonal weight), and the padding of gs * K up to a multiple of 4 meets a
+ * +0.0f z row with a -0.0f weight, an identity of the chain.
+ *
+ * A workgroup (ACE_DISCO_WAVES waves) owns one unit (sample, output row, run of up to ACE_DISCO_RUN output columns, run of
+ * groups): it stages the band rows of its channels in LDS (at most ACE_DISCO_STAGE_BYTES per pass, more channels in further
+ * passes), forms z with psi values that are uniform across the wave - one LDS read per K multiply-adds - into at most
+ * ACE_DISCO_Z_BYTES of LDS, contracts it with the group's weight on v_mfma_f32_16x16x4_f32 and writes y once; z never goes to
+ * memory.  Units are listed on the host, heaviest first; a polar row, whose disk wraps every longitude, is split over groups and
+ * then over shorter pixel runs (down to ACE_DISCO_MIN_RUN) until a unit costs no more than 1 / ACE_DISCO_TARGET_UNITS of a sample
+ * (or ACE_DISCO_MIN_UNIT_COST, if that is more).
+ * Accepted: W below or no multiple of the run, gs * K no multiple of 4, opg from 1 (depthwise) up, groups == 1.
+ *
+ * Refused (ACE_ERR_INVALID, the reason behind ace_disco_last_error, nothing launched): a NULL handle, x or y; batch < 1; embed
+ * NULL where has_embed; batch * units beyond 2^31 - 1; in create: a NULL argument, K not ks * ks with ks in 1 .. 5
+ * (ACE_DISCO_MAX_K), groups not dividing both channel counts, gs * K over ACE_DISCO_MAX_PRODUCTS, an unknown activation, an
+ * output row without a point, a point outside the grid, points out of order, one channel's band over ACE_DISCO_STAGE_BYTES.
+ * ------------------------------------------------------------------------------------------ */
+#define ACE_DISCO_ACT_NONE 0
+#define ACE_DISCO_ACT_RELU 1
+#define ACE_DISCO_ACT_GELU 2
+#define ACE_DISCO_ACT_SILU 3
+#define ACE_DISCO_MAX_K 25                     /* basis functions: kernel_size <= 5 */
+#define ACE_DISCO_MAX_PRODUCTS 512             /* (in_chans / groups) * K */
+#define ACE_DISCO_RUN 16                       /* output columns of a unit: the pixel side of the MFMA tile */
+#define ACE_DISCO_MIN_RUN 4                    /* the shortest run a polar row is split into */
+#define ACE_DISCO_WAVES 4                      /* waves of a workgroup */
+#define ACE_DISCO_STAGE_BYTES 65536            /* LDS of the staged band rows of one pass */
+#define ACE_DISCO_Z_BYTES 32768                /* LDS of a unit's z: groups * roundup4(gs * K) * ACE_DISCO_RUN floats */
+#define ACE_DISCO_TARGET_UNITS 2048            /* a unit costs at most 1 / this of a sample's work, where the split allows ... */
+#define ACE_DISCO_MIN_UNIT_COST 4096           /* ... but a unit at or below this many (point, pixel, channel) products is not split */
+
+const char* ace_disco_last_error(void);
+int ace_disco_create(int H, int W, int K, const long* row_off, const int* hi, const int* wi, const float* vals, const float* w_dev,
+                     int in_chans, int out_chans, int groups, int act, int has_embed, void* stream, void** handle);
+void ace_disco_destroy(void* handle);
+int ace_disco_forward(void* handle, const float* x, const float* embed, float* y, int batch, void* stream);
+int ace_disco_info(void* handle, long* out4);
 
 #ifdef __cplusplus
 }
