@@ -37,6 +37,21 @@ class Plane(ctypes.Structure):
     _fields_ = [("p", c_void_p), ("stride", c_long)]
 
 
+def bind_plane(dst: Plane, t, batch: int, shape, device, who: str, name: str) -> None:
+    """Point ``dst`` at the (batch, H, W) fp32 planes of ``t`` ((batch, 1, H, W) is squeezed): rows contiguous, any sample stride."""
+    import torch
+
+    B, (H, W) = batch, shape
+    if t.dtype != torch.float32 or t.device != device:
+        raise TypeError(f"{who}: '{name}' must be float32 on {device}, got {t.dtype} on {t.device}")
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3 or tuple(t.shape) != (B, H, W) or t.stride(-1) != 1 or t.stride(-2) != W:
+        raise ValueError(f"{who}: '{name}' must be ({B}, {H}, {W}) with contiguous rows, got shape "
+                         f"{tuple(t.shape)} strides {t.stride()}")
+    dst.p, dst.stride = t.data_ptr(), (t.stride(0) if B > 1 else H * W)
+
+
 class PhysConfig(ctypes.Structure):
     """struct ace_phys_config"""
     _fields_ = [("nlat", c_int), ("nlon", c_int), ("nlev", c_int), ("timestep_seconds", c_double),
@@ -378,11 +393,13 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
-def check(rc: int) -> None:
-    """Map the C status to the exception the reference would raise at this boundary."""
+def check(rc: int, family: str = None) -> None:
+    """Map the C status to the exception the reference would raise at this boundary.  The message is read through the getter of
+    the call's family (``ace_<family>_last_error``; None: ``ace_last_error``), looked up on ``lib()`` now: the library answers
+    every getter from one string, an emulation standing in for ``lib()`` in a test has its own family's getter only."""
     if rc == ACE_OK:
         return
-    msg = lib().ace_last_error().decode()
+    msg = getattr(lib(), f"ace_{family}_last_error" if family else "ace_last_error")().decode()
     if rc == ACE_ERR_INVALID:
         raise ValueError(msg)
     raise RuntimeError(msg)

@@ -31,11 +31,14 @@ identical runs give bitwise identical diagnostics.  Peak extra device memory of 
 (B * T * names * ceil(H * W / 1024) * 4 * 24 bytes, 9.8 MB at 1 degree with 40 names and 40 steps) plus one spectrum chunk of at
 most ``spectrum_chunk_bytes`` (default 256 MiB: stacked planes and their coefficients)."""
 import dataclasses
+import functools
 import itertools
 import os
 from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch
+
+from ._lib import check
 
 TensorMapping = Mapping[str, torch.Tensor]
 
@@ -610,8 +613,4 @@ def _upload_planes(names: Sequence[str], gen: TensorMapping, target: Optional[Te
     return at, list(itertools.accumulate([p.nbytes for p in sections[:-1]], initial=at["end"])) if sections else []
 
 
-def _check(rc: int) -> None:
-    if rc != 0:
-        from . import _lib
-        msg = _lib.lib().ace_diag_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
+_check = functools.partial(check, family="diag")

@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libace_sfno.so")
-SOURCES = ["kernels.hip", "fft.hip", "strip.hip", "strip_fold.hip", "conv_ws.hip", "conv_wl.hip", "dhconv_strip.hip", "cln_mfma.hip", "physics.hip", "ocean_phys.hip", "ice_budget.hip", "ocean_derive.hip", "masking.hip", "pixel_mlp.hip", "disco.hip", "gmr.hip", "coupler.hip", "diag.hip", "hist.hip", "regress.hip", "calendar.hip", "ensemble.hip", "fill.hip", "timeseg.hip", "region.hip", "video.hip", "stepdiag.hip", "healpix.hip", "latlon.hip", "capi.hip", "tables.cpp"]
-HEADERS = ["kernels.h", "strip_common.h", "strip_pack.h", "ws_plan.h", "conv_roles.h", "weight_prep.h", "range_exponent.h", "pack_frag.h", "dhconv_units.h", "fft_units.h", "disco_units.h", "pixel_act.h", "tuning_guard.h", "small_fft.h", "tables.h", "diag_common.h", os.path.join("..", "..", "include", "ace_sfno.h")]
+SOURCES = ["kernels.hip", "fft.hip", "strip.hip", "strip_fold.hip", "conv_ws.hip", "conv_wl.hip", "dhconv_strip.hip", "cln_mfma.hip", "physics.hip", "ocean_phys.hip", "ice_budget.hip", "ocean_derive.hip", "masking.hip", "pixel_mlp.hip", "disco.hip", "gmr.hip", "coupler.hip", "diag.hip", "hist.hip", "regress.hip", "calendar.hip", "ensemble.hip", "fill.hip", "timeseg.hip", "region.hip", "video.hip", "stepdiag.hip", "healpix.hip", "latlon.hip", "capi.hip", "tables.cpp", "errors.cpp"]
+HEADERS = ["kernels.h", "strip_common.h", "strip_pack.h", "ws_plan.h", "conv_roles.h", "weight_prep.h", "range_exponent.h", "pack_frag.h", "dhconv_units.h", "fft_units.h", "disco_units.h", "pixel_act.h", "tuning_guard.h", "small_fft.h", "tables.h", "diag_common.h", "errors.h", os.path.join("..", "..", "include", "ace_sfno.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 

@@ -21,6 +21,7 @@ The coupled rollout on static windows with graph capture is ``CoupledRolloutEngi
 (follow-ups): a coupled inference loop, aggregators, training, ensembles."""
 import dataclasses
 import datetime
+import functools
 import pathlib
 import re
 from collections.abc import Generator, Iterable, Mapping
@@ -29,6 +30,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 import torch
 from torch import nn
 
+from ._lib import check
 from .ocean import Prescriber
 from .ocean_corrector import OCEAN_FIELD_NAME_PREFIXES
 from .ocean_derived_variables import OceanDeriveFn
@@ -604,11 +606,7 @@ class Coupler:
         return windows
 
 
-def _check(rc: int) -> None:
-    if rc != 0:
-        from . import _lib
-        msg = _lib.lib().ace_couple_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
+_check = functools.partial(check, family="couple")
 
 
 # ---- the coupled stepper --------------------------------------------------------------------------------------------------

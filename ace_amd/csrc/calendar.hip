@@ -206,29 +206,29 @@ extern "C" int ace_diag_calendar_window(const float* const* gen, const long* gen
                                         const float* weights, int nw, double* partial, double* series, int nrows, int nbins,
                                         int nreg, int nsrows, int n_time, int t0, int t_begin, int nplanes, int batch, int steps,
                                         long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: need 0 <= nplanes <= 65535");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: need 0 <= nplanes <= 65535");
     if (nbins < 0 || nbins > MAX_BINS)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: need 0 <= nbins <= " + std::to_string(MAX_BINS) +
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: need 0 <= nbins <= " + std::to_string(MAX_BINS) +
                                                " (the sums of a pixel stay in registers); split the bins over several calls");
     if (nreg < 0 || nreg > MAX_REG)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: need 0 <= nreg <= " + std::to_string(MAX_REG) +
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: need 0 <= nreg <= " + std::to_string(MAX_REG) +
                                                " (the weights of a pixel stay in registers)");
     if (batch < 1 || steps < 1 || (long)batch * steps > 2147483647L)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: need batch >= 1, steps >= 1, batch * steps < 2^31");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: need batch >= 1, steps >= 1, batch * steps < 2^31");
     if (hw < 1 || nchunk_for(hw) > 2147483647L || nrows < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1");
-    if (t_begin < 0) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: need t_begin >= 0");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1");
+    if (t_begin < 0) return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: need t_begin >= 0");
     const bool ser = series != nullptr;
     if (ser && (nsrows < 1 || t0 < 0 || (long)t0 + steps > n_time))
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: with series need nsrows >= 1, t0 >= 0 and t0 + steps <= "
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: with series need nsrows >= 1, t0 >= 0 and t0 + steps <= "
                                                "n_time");
     if (nplanes == 0) return ACE_OK;
     if (!gen || !gen_strides || !target || !target_strides || !rows)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: null argument");
     if (bins && nbins > 0 && !bin)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: null argument (bin is needed when bins is given)");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: null argument (bin is needed when bins is given)");
     if (ser && (nw < 1 || !wrows || !weights || !partial || (nreg > 0 && (!regions || !srow || !mode))))
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_calendar_window: null argument (regions, srow, mode, wrows, weights and "
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_calendar_window: null argument (regions, srow, mode, wrows, weights and "
                                                "partial are needed when series is given)");
     const bool do_bins = bins != nullptr && nbins > 0, do_ser = ser && nreg > 0;
     if ((!do_bins && !do_ser) || t_begin >= steps) return ACE_OK;
@@ -245,10 +245,10 @@ extern "C" int ace_diag_calendar_window(const float* const* gen, const long* gen
     if (a.nbins == 0) launch<0>(a, do_ser, grid, s);
     else if (a.nbins <= 4) launch<4>(a, do_ser, grid, s);
     else launch<MAX_BINS>(a, do_ser, grid, s);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     if (do_ser) {
         hipLaunchKernelGGL(calendar_series_kernel, dim3(a.nreg, nplanes, 2), dim3(NT), 0, s, a);
-        DIAG_TRY(hipGetLastError());
+        ACE_HIP_TRY(hipGetLastError());
     }
     return ACE_OK;
 }

@@ -14,35 +14,13 @@
 #include <vector>
 
 #include "../../include/ace_sfno.h"
+#include "errors.h"
 #include "kernels.h"
 #include "strip_pack.h"
 #include "tables.h"
 #include "weight_prep.h"
 
-using namespace ace;
-
-// ---------------------------------------------------------------------------------------------
-// error plumbing: never abort, return a code and keep a thread-local message
-// ---------------------------------------------------------------------------------------------
-static thread_local std::string g_err;
-
-static int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-#define HIP_TRY(expr)                                                                                      \
-    do {                                                                                                   \
-        hipError_t e__ = (expr);                                                                           \
-        if (e__ != hipSuccess)                                                                             \
-            return fail(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__));              \
-    } while (0)
-#define ACE_TRY(expr)                \
-    do {                             \
-        int rc__ = (expr);           \
-        if (rc__ != ACE_OK) return rc__; \
-    } while (0)
-
-extern "C" const char* ace_last_error(void) { return g_err.c_str(); }
+using namespace ace;   // fail() below is ace::fail (errors.h)
 
 namespace ace {
 Switches read_switches() {
@@ -122,8 +100,8 @@ struct DevBuf {
 // `count` floats of a device array on the host, once the stream's pending writes to it have finished
 static int host_copy(const float* dev, size_t count, hipStream_t s, std::vector<float>& host) {
     host.resize(count);
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(host.data(), dev, count * sizeof(float), hipMemcpyDeviceToHost));
+    ACE_HIP_TRY(hipStreamSynchronize(s));
+    ACE_HIP_TRY(hipMemcpy(host.data(), dev, count * sizeof(float), hipMemcpyDeviceToHost));
     return ACE_OK;
 }
 static float host_absmax(const std::vector<float>& v) {
@@ -134,8 +112,8 @@ static float host_absmax(const std::vector<float>& v) {
 // a dynamic-range slot (AMAX_SHARDS words, each the bit pattern of a non-negative float) read back as the maximum it holds
 static int read_range_slot(const unsigned* slot, hipStream_t s, float* mx) {
     unsigned bits[AMAX_SHARDS];
-    HIP_TRY(hipMemcpyAsync(bits, slot, sizeof(bits), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    ACE_HIP_TRY(hipMemcpyAsync(bits, slot, sizeof(bits), hipMemcpyDeviceToHost, s));
+    ACE_HIP_TRY(hipStreamSynchronize(s));
     *mx = 0.f;
     for (unsigned b : bits) { float f; std::memcpy(&f, &b, 4); *mx = std::max(*mx, f); }
     return ACE_OK;
@@ -143,8 +121,8 @@ static int read_range_slot(const unsigned* slot, hipStream_t s, float* mx) {
 // max |x| of a device array, reduced on the device (a maximum rounds nothing: the value a host loop over a copy gives)
 static int device_absmax(const float* x, long count, hipStream_t s, float* mx) {
     DevBuf slot;
-    HIP_TRY(slot.alloc(AMAX_SHARDS));
-    HIP_TRY(launch_absmax(x, count, reinterpret_cast<unsigned*>(slot.p), s));
+    ACE_HIP_TRY(slot.alloc(AMAX_SHARDS));
+    ACE_HIP_TRY(launch_absmax(x, count, reinterpret_cast<unsigned*>(slot.p), s));
     return read_range_slot(reinterpret_cast<const unsigned*>(slot.p), s, mx);
 }
 
@@ -191,12 +169,12 @@ static int plan_build(int nlat, int nlon, int lmax, int mmax, Grid g, std::uniqu
     p->sw = read_switches();
     p->nlat = t.nlat; p->nlon = t.nlon; p->lmax = t.lmax; p->mmax = t.mmax;
     p->Hp = t.Hp; p->Lp = t.Lp; p->Kfp = t.Kfp; p->grid = g;
-    HIP_TRY(p->wt.upload(t.wt));
-    HIP_TRY(p->pt.upload(t.pt));
-    HIP_TRY(p->fc.upload(t.fc));
-    HIP_TRY(p->fs.upload(t.fs));
-    HIP_TRY(p->gc.upload(t.gc));
-    HIP_TRY(p->gs.upload(t.gs));
+    ACE_HIP_TRY(p->wt.upload(t.wt));
+    ACE_HIP_TRY(p->pt.upload(t.pt));
+    ACE_HIP_TRY(p->fc.upload(t.fc));
+    ACE_HIP_TRY(p->fs.upload(t.fs));
+    ACE_HIP_TRY(p->gc.upload(t.gc));
+    ACE_HIP_TRY(p->gs.upload(t.gs));
     if (f16) {
         p->f16 = true;
         p->wt_scale = pow2_scale_for(t.wt);
@@ -207,11 +185,11 @@ static int plan_build(int nlat, int nlon, int lmax, int mmax, Grid g, std::uniqu
         }
         p->pt_scale = pow2_scale_for(t.pt);
         const size_t hw = (t.wt.size() + 1) / 2, hp = (t.pt.size() + 1) / 2;
-        HIP_TRY(p->wt_hi.alloc(hw, false)); HIP_TRY(p->wt_lo.alloc(hw, false));
-        HIP_TRY(p->pt_hi.alloc(hp, false)); HIP_TRY(p->pt_lo.alloc(hp, false));
-        HIP_TRY(launch_split_f16(p->wt.p, t.Hp, p->wt_hi.p, p->wt_lo.p, t.Hp, (long)t.mmax * t.lmax, t.Hp, p->wt_scale, nullptr));
-        HIP_TRY(launch_split_f16(p->pt.p, t.Lp, p->pt_hi.p, p->pt_lo.p, t.Lp, (long)t.mmax * t.nlat, t.Lp, p->pt_scale, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
+        ACE_HIP_TRY(p->wt_hi.alloc(hw, false)); ACE_HIP_TRY(p->wt_lo.alloc(hw, false));
+        ACE_HIP_TRY(p->pt_hi.alloc(hp, false)); ACE_HIP_TRY(p->pt_lo.alloc(hp, false));
+        ACE_HIP_TRY(launch_split_f16(p->wt.p, t.Hp, p->wt_hi.p, p->wt_lo.p, t.Hp, (long)t.mmax * t.lmax, t.Hp, p->wt_scale, nullptr));
+        ACE_HIP_TRY(launch_split_f16(p->pt.p, t.Lp, p->pt_hi.p, p->pt_lo.p, t.Lp, (long)t.mmax * t.nlat, t.Lp, p->pt_scale, nullptr));
+        ACE_HIP_TRY(hipDeviceSynchronize());
         auto up = [](const StripPack& sp, DevBuf& frag, DevBuf& off) -> hipError_t {
             hipError_t e = frag.alloc((sp.frags.size() + 1) / 2, false);   // halves -> floats
             if (e != hipSuccess) return e;
@@ -224,9 +202,9 @@ static int plan_build(int nlat, int nlon, int lmax, int mmax, Grid g, std::uniqu
         if (t.nlat <= 192 && t.lmax <= 192) {
             StripPack sp;
             pack_legendre_strip(t.wt.data(), t.mmax, t.lmax, t.nlat, t.Hp, 0, p->wt_scale, sp);
-            HIP_TRY(up(sp, p->wt_frag, p->wt_off));
+            ACE_HIP_TRY(up(sp, p->wt_frag, p->wt_off));
             pack_legendre_strip(t.pt.data(), t.mmax, t.nlat, t.lmax, t.Lp, 1, p->pt_scale, sp);
-            HIP_TRY(up(sp, p->pt_frag, p->pt_off));
+            ACE_HIP_TRY(up(sp, p->pt_frag, p->pt_off));
             p->strip = true;
         }
         // P_l^m(-x) = (-1)^(l+m) P_l^m(x) on a grid that is symmetric about the equator (all three quadratures are): checked
@@ -246,8 +224,8 @@ static int plan_build(int nlat, int nlon, int lmax, int mmax, Grid g, std::uniqu
                         const hipError_t e = d.alloc(v.size(), false);
                         return e != hipSuccess ? e : hipMemcpy(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice);
                     };
-                    HIP_TRY(upi(pc.r0, p->cut_r0));
-                    HIP_TRY(upi(pc.mcut, p->cut_mcut));
+                    ACE_HIP_TRY(upi(pc.r0, p->cut_r0));
+                    ACE_HIP_TRY(upi(pc.mcut, p->cut_mcut));
                     p->cut = true;
                     p->cut_share = pc.dead_share;
                     if (fold_geom(0, 0, t.lmax, t.nlat).nkp2 <= FOLD_NKP_SMALL) {   // small form: the wholly dead leading k16-steps leave the table
@@ -258,8 +236,8 @@ static int plan_build(int nlat, int nlon, int lmax, int mmax, Grid g, std::uniqu
                     }
                 }
             }
-            HIP_TRY(up(sp, p->wt_ffrag, p->wt_foff));
-            HIP_TRY(up(spi, p->pt_ffrag, p->pt_foff));
+            ACE_HIP_TRY(up(sp, p->wt_ffrag, p->wt_foff));
+            ACE_HIP_TRY(up(spi, p->pt_ffrag, p->pt_foff));
             p->fold = true;
         }
     }
@@ -280,7 +258,7 @@ static int run_dft_forward(const ace_sht_plan& pl, const float* x, const float* 
     a.xhi = xhi; a.xlo = xlo; a.sxp = sxp; a.xslot = xslot;   // the field as P-format planes instead of fp32 (FFT form only)
     a.x = xhi ? nullptr : x; a.spec_out = X; a.tc = pl.fc.p; a.ts = pl.fs.p; a.ldt = pl.Kfp; a.sc = sc; a.sh = sh;
     a.Bt = Bt; a.C = C; a.H = pl.nlat; a.W = pl.nlon; a.Mm = pl.mmax; a.no_fft = pl.sw.no_fft;
-    HIP_TRY(launch_dft_forward(a, s));
+    ACE_HIP_TRY(launch_dft_forward(a, s));
     return ACE_OK;
 }
 static DftArgs dft_inverse_args(const ace_sht_plan& pl, const float* X, const float* bias, float* y, int Bt, int C, unsigned* ymax) {
@@ -294,7 +272,7 @@ static int run_dft_inverse(const ace_sht_plan& pl, const float* X, const float* 
                            hipStream_t s, unsigned* ymax = nullptr, const int* mcut = nullptr) {
     DftArgs a = dft_inverse_args(pl, X, bias, y, Bt, C, ymax);
     a.mcut = mcut;   // inverse_pair: only behind the folded Legendre kernel
-    HIP_TRY(launch_dft_inverse(a, s));
+    ACE_HIP_TRY(launch_dft_inverse(a, s));
     return ACE_OK;
 }
 // D[l][m][n2] = sum_k wt[m][l][k] X[m][k][n2]   (sht_fix.py:134-138), batched over m, rows l >= m only
@@ -327,13 +305,13 @@ static int run_legendre_forward(const ace_sht_plan& pl, const float* X, float* D
             f.A = reinterpret_cast<const _Float16*>(pl.wt_ffrag.p); f.tile_off = reinterpret_cast<const int*>(pl.wt_foff.p);
             if (pl.cut) { f.r0 = reinterpret_cast<const int*>(pl.cut_r0.p); f.kdrop = pl.kdrop; }   // the window is safe behind any producer
             if (legendre_fold_eligible(f)) {
-                if (!dry) HIP_TRY(launch_legendre_fold(f, s));
+                if (!dry) ACE_HIP_TRY(launch_legendre_fold(f, s));
                 pl.route[0] = fold_route(f);
                 return ACE_OK;
             }
         }
         if (pl.strip && legendre_strip_eligible(a)) {
-            if (!dry) HIP_TRY(launch_legendre_strip(a, s));
+            if (!dry) ACE_HIP_TRY(launch_legendre_strip(a, s));
             pl.route[0] = 1;
             return ACE_OK;
         }
@@ -346,14 +324,14 @@ static int run_legendre_forward(const ace_sht_plan& pl, const float* X, float* D
         if (!(pl.f16 && xmax && dmax && gemm_f16x3_eligible(g))) return fail(ACE_ERR_STATE, "legendre planes path not eligible");
         _Float16* Dh = reinterpret_cast<_Float16*>(D);
         _Float16* Dl = Dh + (size_t)pl.lmax * pl.mmax * N2;
-        HIP_TRY(launch_gemm_f16x3_planes(g, pl.wt_hi.p, pl.wt_lo.p, pl.wt_scale, xmax, Dh, Dl, pl.wt_winf, dmax, s));
+        ACE_HIP_TRY(launch_gemm_f16x3_planes(g, pl.wt_hi.p, pl.wt_lo.p, pl.wt_scale, xmax, Dh, Dl, pl.wt_winf, dmax, s));
         return ACE_OK;
     }
     if (pl.f16 && xmax && gemm_f16x3_eligible(g)) {
-        HIP_TRY(launch_gemm_f16x3(g, pl.wt_hi.p, pl.wt_lo.p, pl.wt_scale, 1.f, s, xmax, dmax));
+        ACE_HIP_TRY(launch_gemm_f16x3(g, pl.wt_hi.p, pl.wt_lo.p, pl.wt_scale, 1.f, s, xmax, dmax));
         return ACE_OK;
     }
-    HIP_TRY(launch_gemm(g, s));
+    ACE_HIP_TRY(launch_gemm(g, s));
     return ACE_OK;
 }
 // X[m][k][n2] = sum_{l>=m} pt[m][k][l] E[l][m][n2]   (sht_fix.py:208-219), batched over m
@@ -379,13 +357,13 @@ static int run_legendre_inverse(const ace_sht_plan& pl, const float* E, float* X
             f.A = reinterpret_cast<const _Float16*>(pl.pt_ffrag.p); f.tile_off = reinterpret_cast<const int*>(pl.pt_foff.p);
             if (pl.cut && skip_dead) f.r0 = reinterpret_cast<const int*>(pl.cut_r0.p);
             if (legendre_fold_eligible(f)) {
-                if (!dry) HIP_TRY(launch_legendre_fold(f, s));
+                if (!dry) ACE_HIP_TRY(launch_legendre_fold(f, s));
                 pl.route[1] = fold_route(f);
                 return ACE_OK;
             }
         }
         if (pl.strip && legendre_strip_eligible(a)) {
-            if (!dry) HIP_TRY(launch_legendre_strip(a, s));
+            if (!dry) ACE_HIP_TRY(launch_legendre_strip(a, s));
             pl.route[1] = 1;
             return ACE_OK;
         }
@@ -393,10 +371,10 @@ static int run_legendre_inverse(const ace_sht_plan& pl, const float* E, float* X
     pl.route[1] = 0;
     if (dry) return ACE_OK;
     if (pl.f16 && emax && gemm_f16x3_eligible(g)) {
-        HIP_TRY(launch_gemm_f16x3(g, pl.pt_hi.p, pl.pt_lo.p, pl.pt_scale, 1.f, s, emax, nullptr));
+        ACE_HIP_TRY(launch_gemm_f16x3(g, pl.pt_hi.p, pl.pt_lo.p, pl.pt_scale, 1.f, s, emax, nullptr));
         return ACE_OK;
     }
-    HIP_TRY(launch_gemm(g, s));
+    ACE_HIP_TRY(launch_gemm(g, s));
     return ACE_OK;
 }
 
@@ -441,7 +419,7 @@ extern "C" int ace_sht_plan_create_ex(int nlat, int nlon, int lmax, int mmax, co
     if (!parse_grid(grid, &g)) return fail(ACE_ERR_INVALID, "Unknown quadrature mode");
     std::unique_ptr<ace_sht_plan> p;
     ACE_TRY(plan_build(nlat, nlon, lmax, mmax, g, p, precision == 1));
-    if (precision == 1) HIP_TRY(p->slots.alloc((size_t)2 * AMAX_SHARDS));
+    if (precision == 1) ACE_HIP_TRY(p->slots.alloc((size_t)2 * AMAX_SHARDS));
     *plan = p.release();
     return ACE_OK;
 }
@@ -476,36 +454,36 @@ extern "C" int ace_sht_forward(ace_sht_plan* p, const float* x, float* coeffs, i
     if (!p || !x || !coeffs || n <= 0) return fail(ACE_ERR_INVALID, "ace_sht_forward: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long N2 = 2L * n;
-    HIP_TRY(p->X.ensure_x(((size_t)p->mmax * p->nlat + LEG_STRIP_SLACK_ROWS) * N2, p->sw.polar_poison));
-    HIP_TRY(p->D.ensure(((size_t)p->lmax + LEG_STRIP_SLACK_ROWS) * p->mmax * N2));
+    ACE_HIP_TRY(p->X.ensure_x(((size_t)p->mmax * p->nlat + LEG_STRIP_SLACK_ROWS) * N2, p->sw.polar_poison));
+    ACE_HIP_TRY(p->D.ensure(((size_t)p->lmax + LEG_STRIP_SLACK_ROWS) * p->mmax * N2));
     // coefficients with l < m are never written by the triangular Legendre stage: the layout converter writes their zeros
     // without reading the scratch (no memset)
     unsigned* xmax = nullptr;
     if (p->f16 && p->slots.p) {
         xmax = reinterpret_cast<unsigned*>(p->slots.p);
-        HIP_TRY(launch_zero_u32(xmax, 2 * AMAX_SHARDS, s));
+        ACE_HIP_TRY(launch_zero_u32(xmax, 2 * AMAX_SHARDS, s));
     }
     unsigned* dmax = xmax ? xmax + AMAX_SHARDS : nullptr;
     const int* mcut = forward_pair_mcut(*p, p->X.p, p->D.p, N2, xmax, dmax, false);
     ACE_TRY(run_dft_forward(*p, x, nullptr, nullptr, p->X.p, 1, n, s, xmax, nullptr, nullptr, 0, nullptr, nullptr, nullptr, mcut));
     ACE_TRY(run_legendre_forward(*p, p->X.p, p->D.p, N2, s, xmax, dmax));
-    HIP_TRY(launch_spec_to_ref(p->D.p, coeffs, 1, n, p->lmax, p->mmax, s));
+    ACE_HIP_TRY(launch_spec_to_ref(p->D.p, coeffs, 1, n, p->lmax, p->mmax, s));
     return ACE_OK;
 }
 extern "C" int ace_sht_inverse(ace_sht_plan* p, const float* coeffs, float* x, int n, void* stream) {
     if (!p || !x || !coeffs || n <= 0) return fail(ACE_ERR_INVALID, "ace_sht_inverse: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long N2 = 2L * n;
-    HIP_TRY(p->X.ensure_x(((size_t)p->mmax * p->nlat + LEG_STRIP_SLACK_ROWS) * N2, p->sw.polar_poison));
-    HIP_TRY(p->D.ensure(((size_t)p->lmax + LEG_STRIP_SLACK_ROWS) * p->mmax * N2));
+    ACE_HIP_TRY(p->X.ensure_x(((size_t)p->mmax * p->nlat + LEG_STRIP_SLACK_ROWS) * N2, p->sw.polar_poison));
+    ACE_HIP_TRY(p->D.ensure(((size_t)p->lmax + LEG_STRIP_SLACK_ROWS) * p->mmax * N2));
     unsigned* emax = nullptr;
     if (p->f16 && p->slots.p) {   // f16x3: range of the coefficients, taken by the layout converter as it reads them (round 5: a pass
         emax = reinterpret_cast<unsigned*>(p->slots.p);   // of its own over the converted tensor, 45 us at the reference's benchmark size)
-        HIP_TRY(launch_zero_u32(emax, 2 * AMAX_SHARDS, s));
+        ACE_HIP_TRY(launch_zero_u32(emax, 2 * AMAX_SHARDS, s));
     }
     // the strip kernels are exactly triangular: the converter then neither reads nor writes the entries with m > l (half the tensor)
     ACE_TRY(run_legendre_inverse(*p, p->D.p, p->X.p, N2, s, emax, true));
-    HIP_TRY(launch_ref_to_spec(coeffs, p->D.p, 1, n, p->lmax, p->mmax, s, emax, p->route[1] != 0));
+    ACE_HIP_TRY(launch_ref_to_spec(coeffs, p->D.p, 1, n, p->lmax, p->mmax, s, emax, p->route[1] != 0));
     const InversePair pr = inverse_pair(*p, p->D.p, p->X.p, N2, emax, x, 1, n);
     ACE_TRY(run_legendre_inverse(*p, p->D.p, p->X.p, N2, s, emax, false, pr.skip_dead));
     ACE_TRY(run_dft_inverse(*p, p->X.p, nullptr, x, 1, n, s, nullptr, pr.mcut));
@@ -563,14 +541,14 @@ static int prepare_conv_operand(const float* w, int rows, int cols, long ld, int
     o.pitch = (cols + 31) & ~31;
     const size_t halves = (size_t)((rows + 15) / 16 * 16) * o.pitch;
     if (forms & PLANES_ROWS) {
-        if (!o.hi.p) HIP_TRY(o.hi.alloc((halves + 1) / 2, false));
-        if (!o.lo.p) HIP_TRY(o.lo.alloc((halves + 1) / 2, false));
-        HIP_TRY(launch_split_f16(w, ld, o.hi.p, o.lo.p, o.pitch, rows, cols, o.ascale, s));
+        if (!o.hi.p) ACE_HIP_TRY(o.hi.alloc((halves + 1) / 2, false));
+        if (!o.lo.p) ACE_HIP_TRY(o.lo.alloc((halves + 1) / 2, false));
+        ACE_HIP_TRY(launch_split_f16(w, ld, o.hi.p, o.lo.p, o.pitch, rows, cols, o.ascale, s));
     }
     if (forms & PLANES_TILED) {
-        if (!o.thi.p) HIP_TRY(o.thi.alloc((halves + 1) / 2, false));
-        if (!o.tlo.p) HIP_TRY(o.tlo.alloc((halves + 1) / 2, false));
-        HIP_TRY(launch_split_f16_tiled(w, ld, o.thi.p, o.tlo.p, o.pitch, rows, cols, o.ascale, s));
+        if (!o.thi.p) ACE_HIP_TRY(o.thi.alloc((halves + 1) / 2, false));
+        if (!o.tlo.p) ACE_HIP_TRY(o.tlo.alloc((halves + 1) / 2, false));
+        ACE_HIP_TRY(launch_split_f16_tiled(w, ld, o.thi.p, o.tlo.p, o.pitch, rows, cols, o.ascale, s));
     }
     return ACE_OK;
 }
@@ -583,8 +561,8 @@ static int prepare_cln_frags(const float* w, int C, int J, hipStream_t s, DevBuf
     *ascale = cln_frag_scale(norms->absmax);
     std::vector<uint16_t> frags(cln_frag_halves(C, J));
     pack_cln_frags(host.data(), C, J, *ascale, frags.data());
-    if (!frag.p) HIP_TRY(frag.alloc((frags.size() + 1) / 2, false));
-    HIP_TRY(hipMemcpy(frag.p, frags.data(), frags.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if (!frag.p) ACE_HIP_TRY(frag.alloc((frags.size() + 1) / 2, false));
+    ACE_HIP_TRY(hipMemcpy(frag.p, frags.data(), frags.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return ACE_OK;
 }
 
@@ -601,7 +579,7 @@ extern "C" int ace_conv1x1(const float* x, const float* weight, const float* bia
     g.C = y; g.ldc = hw; g.sC = (long)cout * hw;
     g.bias = bias; g.M = cout; g.N = (int)hw; g.K = cin; g.nbatch = n; g.act = act;
     g.a_kpad = cin;  // caller's weight is unpadded: only K % stage-depth == 0 qualifies for the direct-to-LDS engine
-    HIP_TRY(launch_gemm(g, static_cast<hipStream_t>(stream)));
+    ACE_HIP_TRY(launch_gemm(g, static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
 
@@ -620,11 +598,11 @@ extern "C" int ace_conv1x1_f16x3(const float* x, const float* weight, const floa
     if (!gemm_f16x3_eligible(g)) return fail(ACE_ERR_INVALID, "ace_conv1x1_f16x3: needs 16-byte aligned x and hw % 4 == 0");
     if (g.act == ACT_GELU) g.act = ACT_GELU_FAST;
     DevBuf slotbuf;
-    HIP_TRY(slotbuf.alloc(AMAX_SHARDS));
+    ACE_HIP_TRY(slotbuf.alloc(AMAX_SHARDS));
     unsigned* xslot = reinterpret_cast<unsigned*>(slotbuf.p);
-    HIP_TRY(launch_absmax(x, (long)n * cin * hw, xslot, s));
-    HIP_TRY(launch_gemm_f16x3(g, w.hi.p, w.lo.p, w.ascale, 1.0f, s, xslot, nullptr));
-    HIP_TRY(hipStreamSynchronize(s));  // temporaries are freed on return
+    ACE_HIP_TRY(launch_absmax(x, (long)n * cin * hw, xslot, s));
+    ACE_HIP_TRY(launch_gemm_f16x3(g, w.hi.p, w.lo.p, w.ascale, 1.0f, s, xslot, nullptr));
+    ACE_HIP_TRY(hipStreamSynchronize(s));  // temporaries are freed on return
     return ACE_OK;
 }
 
@@ -633,7 +611,7 @@ extern "C" int ace_conv1x1_f16x3(const float* x, const float* weight, const floa
 // each plane from its minimum and maximum, with the rounding slack of instnorm_stats_kernel.
 static int fused_source_bound(const float* x, long pitch, long hw, long planes, const float* sc, const float* sh, float* bound) {
     std::vector<float> h((size_t)planes * hw);
-    HIP_TRY(hipMemcpy2D(h.data(), hw * sizeof(float), x, pitch * sizeof(float), hw * sizeof(float), planes, hipMemcpyDeviceToHost));
+    ACE_HIP_TRY(hipMemcpy2D(h.data(), hw * sizeof(float), x, pitch * sizeof(float), hw * sizeof(float), planes, hipMemcpyDeviceToHost));
     float b = 0.f;
     for (long p = 0; p < planes; ++p) {
         float lo = 3.0e38f, hi = -3.0e38f;
@@ -677,22 +655,22 @@ extern "C" int ace_conv1x1_fused(const ace_conv1x1_fused_desc* d, ace_gemm_route
     g.osc = d->out_scale; g.osh = d->out_shift;
     g.M = d->cout; g.N = (int)d->hw; g.K = K; g.nbatch = d->n; g.act = d->act; g.cap = d->cap;
     g.omax = d->out_absmax;
-    if (d->out_absmax) HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
+    if (d->out_absmax) ACE_HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
     DevBuf wpad, slots;
     ConvOperand w;
     GemmRoute r;
     if (d->engine == 0) {
         g.A = d->weight; g.lda = K; g.a_kpad = 0;   // a caller's unpadded weight: never the direct-to-LDS kernel
         r = gemm_route(g, false);
-        HIP_TRY(launch_gemm(g, s));
+        ACE_HIP_TRY(launch_gemm(g, s));
     } else if (d->engine == 1) {
-        HIP_TRY(wpad.alloc((size_t)d->cout * kp, true));
-        HIP_TRY(hipMemcpy2DAsync(wpad.p, kp * sizeof(float), d->weight, K * sizeof(float), K * sizeof(float), d->cout,
+        ACE_HIP_TRY(wpad.alloc((size_t)d->cout * kp, true));
+        ACE_HIP_TRY(hipMemcpy2DAsync(wpad.p, kp * sizeof(float), d->weight, K * sizeof(float), K * sizeof(float), d->cout,
                                  hipMemcpyDeviceToDevice, s));
         g.A = wpad.p; g.lda = kp; g.a_kpad = kp;
         r = gemm_route(g, false);
         if (r.family != 2) return fail(ACE_ERR_INVALID, "ace_conv1x1_fused: the launch does not qualify for the direct-to-LDS engine");
-        HIP_TRY(launch_gemm(g, s));
+        ACE_HIP_TRY(launch_gemm(g, s));
     } else {
         ACE_TRY(prepare_conv_operand(d->weight, d->cout, K, K, PLANES_ROWS, s, w));
         g.lda = kp; g.sA = 0; g.a_kpad = kp;
@@ -701,8 +679,8 @@ extern "C" int ace_conv1x1_fused(const ace_conv1x1_fused_desc* d, ace_gemm_route
         std::vector<float> sc, sh;
         if (d->in_scale) {
             sc.resize((size_t)d->n * K); sh.resize(sc.size());
-            HIP_TRY(hipMemcpy(sc.data(), d->in_scale, sc.size() * sizeof(float), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(sh.data(), d->in_shift, sh.size() * sizeof(float), hipMemcpyDeviceToHost));
+            ACE_HIP_TRY(hipMemcpy(sc.data(), d->in_scale, sc.size() * sizeof(float), hipMemcpyDeviceToHost));
+            ACE_HIP_TRY(hipMemcpy(sh.data(), d->in_shift, sh.size() * sizeof(float), hipMemcpyDeviceToHost));
         }
         float bound[2] = {0.f, 0.f};
         for (int b = 0; b < d->n; ++b) {   // per sample: the affine's rows of a source are not contiguous over samples
@@ -715,17 +693,17 @@ extern "C" int ace_conv1x1_fused(const ace_conv1x1_fused_desc* d, ace_gemm_route
                 bound[src] = std::max(bound[src], bb);
             }
         }
-        HIP_TRY(slots.alloc(2 * AMAX_SHARDS, true));
+        ACE_HIP_TRY(slots.alloc(2 * AMAX_SHARDS, true));
         unsigned* xslot = reinterpret_cast<unsigned*>(slots.p);
-        HIP_TRY(hipMemcpy(xslot, &bound[0], sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(xslot + AMAX_SHARDS, &bound[1], sizeof(float), hipMemcpyHostToDevice));
+        ACE_HIP_TRY(hipMemcpy(xslot, &bound[0], sizeof(float), hipMemcpyHostToDevice));
+        ACE_HIP_TRY(hipMemcpy(xslot + AMAX_SHARDS, &bound[1], sizeof(float), hipMemcpyHostToDevice));
         if (g.act == ACT_GELU) g.act = ACT_GELU_FAST;   // as the network runs this engine
         r = gemm_route(g, true);
         g.omax = nullptr;
-        HIP_TRY(launch_gemm_f16x3(g, w.hi.p, w.lo.p, w.ascale, 1.0f, s, xslot, d->out_absmax, d->x2 ? xslot + AMAX_SHARDS : nullptr));
+        ACE_HIP_TRY(launch_gemm_f16x3(g, w.hi.p, w.lo.p, w.ascale, 1.0f, s, xslot, d->out_absmax, d->x2 ? xslot + AMAX_SHARDS : nullptr));
     }
     if (route) { route->family = r.family; route->tile = r.tile; }
-    HIP_TRY(hipStreamSynchronize(s));  // temporaries are freed on return
+    ACE_HIP_TRY(hipStreamSynchronize(s));  // temporaries are freed on return
     return ACE_OK;
 }
 
@@ -781,11 +759,11 @@ extern "C" int ace_dft_stage(ace_sht_plan* plan, const ace_dft_stage_desc* d, ac
             q.scale_static = d->ride_scale; q.dst = static_cast<_Float16*>(d->ride_dst); q.nsamples = 1;
             if (d->ride_o <= 0 || d->ride_i <= 0 || !pack_frag_args_ok(q)) return fail(ACE_ERR_INVALID, "ace_dft_stage: the rider job needs ride_o % 32 == 0 and ride_i % 16 == 0 (order 1: % 32)");
             a.ride = q; a.nride = pack_frag_blocks(q); a.rode = &rode;
-            HIP_TRY(launch_pack_conv_frag(q.W, q.ldw, q.O, q.I, q.order, nullptr, 0.f, q.scale_static, nullptr, d->ride_dst_alone, 0, 1, s));
+            ACE_HIP_TRY(launch_pack_conv_frag(q.W, q.ldw, q.O, q.I, q.order, nullptr, 0.f, q.scale_static, nullptr, d->ride_dst_alone, 0, 1, s));
         }
     }
-    if (d->out_absmax) HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
-    HIP_TRY(d->inverse ? launch_dft_inverse(a, s) : launch_dft_forward(a, s));
+    if (d->out_absmax) ACE_HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
+    ACE_HIP_TRY(d->inverse ? launch_dft_inverse(a, s) : launch_dft_forward(a, s));
     if (route) {
         const long cols = (long)a.H * a.Bt * a.C;
         if (d->engine == 1) {
@@ -801,7 +779,7 @@ extern "C" int ace_dft_stage(ace_sht_plan* plan, const ace_dft_stage_desc* d, ac
         }
         route->rode = rode ? 1 : 0;
     }
-    HIP_TRY(hipStreamSynchronize(s));
+    ACE_HIP_TRY(hipStreamSynchronize(s));
     return ACE_OK;
 }
 
@@ -825,17 +803,17 @@ extern "C" int ace_mlp_f16x3(const float* x, const float* w1, const float* b1, c
         b1max = host_absmax(hb);
     }
     DevBuf slots, xp, up;
-    HIP_TRY(slots.alloc(2 * AMAX_SHARDS, true));
-    HIP_TRY(xp.alloc((size_t)n * cin * hw, true));   // two fp16 planes = one fp32 tensor's bytes
-    HIP_TRY(up.alloc((size_t)n * hid * hw, true));
+    ACE_HIP_TRY(slots.alloc(2 * AMAX_SHARDS, true));
+    ACE_HIP_TRY(xp.alloc((size_t)n * cin * hw, true));   // two fp16 planes = one fp32 tensor's bytes
+    ACE_HIP_TRY(up.alloc((size_t)n * hid * hw, true));
     unsigned* xslot = reinterpret_cast<unsigned*>(slots.p);
     unsigned* uslot = xslot + AMAX_SHARDS;
     _Float16* xh = reinterpret_cast<_Float16*>(xp.p);
     _Float16* xl = xh + (size_t)n * cin * hw;
     _Float16* uh = reinterpret_cast<_Float16*>(up.p);
     _Float16* ul = uh + (size_t)n * hid * hw;
-    HIP_TRY(launch_absmax(x, (long)n * cin * hw, xslot, s));
-    HIP_TRY(launch_pack_pformat(x, hw, (long)cin * hw, cin, (int)hw, n, nullptr, nullptr, 0, xslot, xh, xl, hw,
+    ACE_HIP_TRY(launch_absmax(x, (long)n * cin * hw, xslot, s));
+    ACE_HIP_TRY(launch_pack_pformat(x, hw, (long)cin * hw, cin, (int)hw, n, nullptr, nullptr, 0, xslot, xh, xl, hw,
                                 (long)cin * hw, s));
     Gemm4Args a;
     a.Ahi = reinterpret_cast<const _Float16*>(p1.thi.p); a.Alo = reinterpret_cast<const _Float16*>(p1.tlo.p);
@@ -844,15 +822,15 @@ extern "C" int ace_mlp_f16x3(const float* x, const float* w1, const float* b1, c
     a.Chi = uh; a.Clo = ul; a.ldnc = hw; a.sCp = (long)hid * hw; a.cw = p1.winf; a.cb = b1max; a.cslot = uslot;
     a.bias = b1; a.M = hid; a.N = (int)hw; a.K = cin; a.nbatch = n;
     a.act = act == ACT_GELU ? ACT_GELU_FAST : act;
-    HIP_TRY(launch_gemm_f16x3_packed(a, s));
+    ACE_HIP_TRY(launch_gemm_f16x3_packed(a, s));
     Gemm4Args b;
     b.Ahi = reinterpret_cast<const _Float16*>(p2.thi.p); b.Alo = reinterpret_cast<const _Float16*>(p2.tlo.p);
     b.lda = p2.pitch; b.ascale = p2.ascale; b.a_tiled = 1;
     b.Bhi = uh; b.Blo = ul; b.ldn = hw; b.sB = (long)hid * hw; b.bmax = uslot;
     b.C = y; b.ldc = hw; b.sC = (long)cout * hw;
     b.bias = b2; b.M = cout; b.N = (int)hw; b.K = hid; b.nbatch = n; b.act = ACT_NONE;
-    HIP_TRY(launch_gemm_f16x3_packed(b, s));
-    HIP_TRY(hipStreamSynchronize(s));  // temporaries are freed on return
+    ACE_HIP_TRY(launch_gemm_f16x3_packed(b, s));
+    ACE_HIP_TRY(hipStreamSynchronize(s));  // temporaries are freed on return
     return ACE_OK;
 }
 
@@ -896,24 +874,24 @@ extern "C" int ace_dhconv_strip_op(const ace_dhconv_desc* d, ace_dhconv_route* r
     const size_t spec = (size_t)L * Mm * N2;
     const long wnumel = native || G > 1 ? (long)G * L * cg * cg * 2 : (long)c * c * L * 2;   // the caller's tensor
     DevBuf D, Dp, E, Wd, Wh, Wl, slots;
-    HIP_TRY(D.alloc(spec, true));
-    HIP_TRY(Dp.alloc(spec, true));          // hi | lo planes: two halves per element = one float
-    HIP_TRY(E.alloc(spec, d->e_fill == 0.f));   // rows m > l are never written: they keep e_fill
+    ACE_HIP_TRY(D.alloc(spec, true));
+    ACE_HIP_TRY(Dp.alloc(spec, true));          // hi | lo planes: two halves per element = one float
+    ACE_HIP_TRY(E.alloc(spec, d->e_fill == 0.f));   // rows m > l are never written: they keep e_fill
     if (d->e_fill != 0.f) {
         unsigned bits;
         std::memcpy(&bits, &d->e_fill, 4);
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(E.p), (int)bits, spec, s));
+        ACE_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(E.p), (int)bits, spec, s));
     }
-    HIP_TRY(slots.alloc(2 * AMAX_SHARDS, true));
+    ACE_HIP_TRY(slots.alloc(2 * AMAX_SHARDS, true));
     const int kstore = native ? cg : c;
     const size_t wh = (size_t)L * 2 * kstore * c;
-    HIP_TRY(Wh.alloc((wh + 1) / 2, false));
-    HIP_TRY(Wl.alloc((wh + 1) / 2, false));
+    ACE_HIP_TRY(Wh.alloc((wh + 1) / 2, false));
+    ACE_HIP_TRY(Wl.alloc((wh + 1) / 2, false));
     unsigned* dslot = reinterpret_cast<unsigned*>(slots.p);
     unsigned* wslot = dslot + AMAX_SHARDS;
-    HIP_TRY(launch_ref_to_spec(d->coeffs, D.p, n, c, L, Mm, s));
-    HIP_TRY(launch_absmax(D.p, (long)spec, dslot, s));
-    HIP_TRY(launch_absmax(d->weight, wnumel, wslot, s));
+    ACE_HIP_TRY(launch_ref_to_spec(d->coeffs, D.p, n, c, L, Mm, s));
+    ACE_HIP_TRY(launch_absmax(D.p, (long)spec, dslot, s));
+    ACE_HIP_TRY(launch_absmax(d->weight, wnumel, wslot, s));
     float dmx = 0.f, wmx = 0.f;
     ACE_TRY(read_range_slot(dslot, s, &dmx));
     ACE_TRY(read_range_slot(wslot, s, &wmx));
@@ -924,15 +902,15 @@ extern "C" int ace_dhconv_strip_op(const ace_dhconv_desc* d, ace_dhconv_route* r
     bool clamped = false;
     const float dscale = std::ldexp(1.0f, range_exponent(dmx, &clamped)), wscale = pow2_scale(wmx, 10);
     if (clamped) return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: max |coeffs| outside [2^-89, 2^112): the planes' power-of-two scale is clamped there");
-    HIP_TRY(launch_split_f16(D.p, N2, Dp.p, reinterpret_cast<_Float16*>(Dp.p) + spec, N2, (long)L * Mm, (int)N2, dscale, s));
+    ACE_HIP_TRY(launch_split_f16(D.p, N2, Dp.p, reinterpret_cast<_Float16*>(Dp.p) + spec, N2, (long)L * Mm, (int)N2, dscale, s));
     if (native) {
-        HIP_TRY(launch_pack_dhconv_f16g(d->weight, Wh.p, Wl.p, c, G, L, wscale, s));
+        ACE_HIP_TRY(launch_pack_dhconv_f16g(d->weight, Wh.p, Wl.p, c, G, L, wscale, s));
     } else if (G > 1) {
-        HIP_TRY(Wd.alloc((size_t)c * c * L * 2, false));
-        HIP_TRY(launch_csfno_weight_to_dense(d->weight, Wd.p, c, G, L, s));
-        HIP_TRY(launch_pack_dhconv_f16c(Wd.p, Wh.p, Wl.p, c, c, L, wscale, s));
+        ACE_HIP_TRY(Wd.alloc((size_t)c * c * L * 2, false));
+        ACE_HIP_TRY(launch_csfno_weight_to_dense(d->weight, Wd.p, c, G, L, s));
+        ACE_HIP_TRY(launch_pack_dhconv_f16c(Wd.p, Wh.p, Wl.p, c, c, L, wscale, s));
     } else {
-        HIP_TRY(launch_pack_dhconv_f16c(d->weight, Wh.p, Wl.p, c, c, L, wscale, s));
+        ACE_HIP_TRY(launch_pack_dhconv_f16c(d->weight, Wh.p, Wl.p, c, c, L, wscale, s));
     }
     DhconvStripArgs ds;
     ds.Dhi = reinterpret_cast<const _Float16*>(Dp.p); ds.Dlo = ds.Dhi + spec;
@@ -946,13 +924,13 @@ extern "C" int ace_dhconv_strip_op(const ace_dhconv_desc* d, ace_dhconv_route* r
     std::vector<int> u;
     ds.units_per_xcd = dhconv_build_units(L, Mm * n, n, c, u);
     DevBuf units;
-    HIP_TRY(units.alloc(u.size(), false));
-    HIP_TRY(hipMemcpy(units.p, u.data(), u.size() * sizeof(int), hipMemcpyHostToDevice));
+    ACE_HIP_TRY(units.alloc(u.size(), false));
+    ACE_HIP_TRY(hipMemcpy(units.p, u.data(), u.size() * sizeof(int), hipMemcpyHostToDevice));
     ds.units = reinterpret_cast<const int*>(units.p);
     if (!dhconv_strip_eligible(ds)) return fail(ACE_ERR_INVALID, "ace_dhconv_strip_op: shape not covered by dhconv_strip.hip");
-    if (d->out_absmax) HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
-    HIP_TRY(launch_dhconv_strip(ds, s));
-    HIP_TRY(launch_spec_to_ref(E.p, d->out, n, c, L, Mm, s, true));   // entries with m > l: what E held, i.e. e_fill unless the kernel stored there
+    if (d->out_absmax) ACE_HIP_TRY(launch_zero_u32(d->out_absmax, AMAX_SHARDS, s));
+    ACE_HIP_TRY(launch_dhconv_strip(ds, s));
+    ACE_HIP_TRY(launch_spec_to_ref(E.p, d->out, n, c, L, Mm, s, true));   // entries with m > l: what E held, i.e. e_fill unless the kernel stored there
     if (route) {
         const bool skip = G > 1 && (cg % 128 == 0 || 128 % cg == 0);
         *route = ace_dhconv_route{};
@@ -967,7 +945,7 @@ extern "C" int ace_dhconv_strip_op(const ace_dhconv_desc* d, ace_dhconv_route* r
             route->max_chunks = std::max(route->max_chunks, ++chunks[{u[k], u[k + 1]}]);
         }
     }
-    HIP_TRY(hipStreamSynchronize(s));
+    ACE_HIP_TRY(hipStreamSynchronize(s));
     return ACE_OK;
 }
 
@@ -976,12 +954,12 @@ extern "C" int ace_instance_norm(const float* x, const float* gamma, const float
     if (!x || !y || n <= 0 || c <= 0 || hw <= 0) return fail(ACE_ERR_INVALID, "ace_instance_norm: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* st = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st), sizeof(float) * 2 * n * c));
+    ACE_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st), sizeof(float) * 2 * n * c));
     hipError_t e = launch_instnorm_stats(x, gamma, beta, eps, n, c, hw, st, st + (size_t)n * c, s);
     if (e == hipSuccess) e = launch_rowaffine_add(x, st, st + (size_t)n * c, nullptr, nullptr, nullptr, y, (long)n * c, hw, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(st);
-    HIP_TRY(e);
+    ACE_HIP_TRY(e);
     return ACE_OK;
 }
 
@@ -992,9 +970,9 @@ extern "C" int ace_conditional_layer_norm(const float* x, const float* noise, co
         return fail(ACE_ERR_INVALID, "ace_conditional_layer_norm: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     DevBuf stats;
-    HIP_TRY(stats.alloc((size_t)2 * n * hw, false));
-    HIP_TRY(launch_cond_layer_norm(x, noise, gamma, beta, w_scale, w_bias, eps, stats.p, y, n, c, noise_dim, hw, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    ACE_HIP_TRY(stats.alloc((size_t)2 * n * hw, false));
+    ACE_HIP_TRY(launch_cond_layer_norm(x, noise, gamma, beta, w_scale, w_bias, eps, stats.p, y, n, c, noise_dim, hw, s));
+    ACE_HIP_TRY(hipStreamSynchronize(s));
     return ACE_OK;
 }
 
@@ -1021,29 +999,29 @@ extern "C" int ace_conditional_layer_norm_f16x3(const float* x, const float* noi
         WeightNorms nm;
         ACE_TRY(prepare_cln_frags(w_scale, c, noise_dim, s, fs, &a.ascale_s, &nm));
         ACE_TRY(prepare_cln_frags(w_bias, c, noise_dim, s, fb, &a.ascale_b, &nm));
-        HIP_TRY(cslot.alloc(AMAX_SHARDS));
-        HIP_TRY(launch_absmax(noise, (long)n * noise_dim * hw, reinterpret_cast<unsigned*>(cslot.p), s));
+        ACE_HIP_TRY(cslot.alloc(AMAX_SHARDS));
+        ACE_HIP_TRY(launch_absmax(noise, (long)n * noise_dim * hw, reinterpret_cast<unsigned*>(cslot.p), s));
         a.cond = noise; a.scond = (long)noise_dim * hw; a.J = noise_dim; a.cslot = reinterpret_cast<const unsigned*>(cslot.p);
         a.As = reinterpret_cast<const _Float16*>(fs.p); a.Ab = reinterpret_cast<const _Float16*>(fb.p);
     }
     if (!cln_mfma_eligible(a))
         return fail(ACE_ERR_INVALID, "ace_conditional_layer_norm_f16x3: needs c % 256 == 0 (c <= 1024), hw % 4 == 0 (c > 512: hw % 32 == 0), noise_dim <= 128");
-    HIP_TRY(launch_cln_mfma(a, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    ACE_HIP_TRY(launch_cln_mfma(a, s));
+    ACE_HIP_TRY(hipStreamSynchronize(s));
     return ACE_OK;
 }
 
 extern "C" int ace_pack_normalize(const float* const* srcs, const long* strides, const float* mean, const float* std_,
                                   float* dst, int batch, int nch, long hw, void* stream) {
     if (!srcs || !strides || !mean || !std_ || !dst) return fail(ACE_ERR_INVALID, "ace_pack_normalize: null argument");
-    HIP_TRY(launch_pack_normalize(srcs, strides, mean, std_, dst, batch, nch, hw, static_cast<hipStream_t>(stream)));
+    ACE_HIP_TRY(launch_pack_normalize(srcs, strides, mean, std_, dst, batch, nch, hw, static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
 extern "C" int ace_unpack_denormalize(const float* src, const float* mean, const float* std_, float* const* dsts,
                                       const long* strides, int batch, int nch, long hw, void* stream) {
     if (!src || !strides || !mean || !std_ || !dsts)
         return fail(ACE_ERR_INVALID, "ace_unpack_denormalize: null argument");
-    HIP_TRY(launch_unpack_denormalize(src, mean, std_, dsts, strides, batch, nch, hw, static_cast<hipStream_t>(stream)));
+    ACE_HIP_TRY(launch_unpack_denormalize(src, mean, std_, dsts, strides, batch, nch, hw, static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
 
@@ -1056,7 +1034,7 @@ extern "C" int ace_gmr_partials(const float* const* srcs, const long* strides, c
                                 int batch, int K, long hw, void* stream) {
     if (gmr_bad_shape(batch, nsrc, K, hw)) return fail(ACE_ERR_INVALID, "ace_gmr_partials: bad shape");
     if (!srcs || !strides || !plane_idx || !partials) return fail(ACE_ERR_INVALID, "ace_gmr_partials: null argument");
-    HIP_TRY(launch_gmr_partials(srcs, strides, plane_idx, nsrc, partials, batch, K, hw, static_cast<hipStream_t>(stream)));
+    ACE_HIP_TRY(launch_gmr_partials(srcs, strides, plane_idx, nsrc, partials, batch, K, hw, static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
 extern "C" int ace_gmr_sample_means(const float* const* srcs, const long* strides, const int* plane_idx, int nsrc,
@@ -1064,8 +1042,8 @@ extern "C" int ace_gmr_sample_means(const float* const* srcs, const long* stride
     if (gmr_bad_shape(batch, nsrc, K, hw)) return fail(ACE_ERR_INVALID, "ace_gmr_sample_means: bad shape");
     if (!srcs || !strides || !plane_idx || !partials || !means)
         return fail(ACE_ERR_INVALID, "ace_gmr_sample_means: null argument");
-    HIP_TRY(launch_gmr_partials(srcs, strides, plane_idx, nsrc, partials, batch, K, hw, static_cast<hipStream_t>(stream)));
-    HIP_TRY(launch_gmr_sample_means(partials, means, batch, K, hw, static_cast<hipStream_t>(stream)));
+    ACE_HIP_TRY(launch_gmr_partials(srcs, strides, plane_idx, nsrc, partials, batch, K, hw, static_cast<hipStream_t>(stream)));
+    ACE_HIP_TRY(launch_gmr_sample_means(partials, means, batch, K, hw, static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
 extern "C" int ace_gmr_pack_normalize(const float* const* srcs, const long* strides, const float* mean, const float* std_,
@@ -1077,7 +1055,7 @@ extern "C" int ace_gmr_pack_normalize(const float* const* srcs, const long* stri
     if (!srcs || !strides || !mean || !std_ || !shift_idx || !partials || !clim_mean || !dst || !shift ||
         (nextra > 0 && (!extra_idx || !extra_std)))
         return fail(ACE_ERR_INVALID, "ace_gmr_pack_normalize: null argument");
-    HIP_TRY(launch_gmr_pack_normalize(srcs, strides, mean, std_, shift_idx, partials, clim_mean, extra_idx, extra_std, dst, shift,
+    ACE_HIP_TRY(launch_gmr_pack_normalize(srcs, strides, mean, std_, shift_idx, partials, clim_mean, extra_idx, extra_std, dst, shift,
                                       batch, nin, nextra, K, hw, static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
@@ -1087,7 +1065,7 @@ extern "C" int ace_gmr_unpack_denormalize(const float* src, const float* mean, c
     if (gmr_bad_shape(batch, nch, K, hw)) return fail(ACE_ERR_INVALID, "ace_gmr_unpack_denormalize: bad shape");
     if (!src || !mean || !std_ || !dsts || !strides || !shift_idx || !shift)
         return fail(ACE_ERR_INVALID, "ace_gmr_unpack_denormalize: null argument");
-    HIP_TRY(launch_gmr_unpack_denormalize(src, mean, std_, dsts, strides, shift_idx, shift, batch, nch, K, hw,
+    ACE_HIP_TRY(launch_gmr_unpack_denormalize(src, mean, std_, dsts, strides, shift_idx, shift, batch, nch, K, hw,
                                           static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
@@ -1266,9 +1244,9 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
         if (rl < 1 || rm < 1) return fail(ACE_ERR_INVALID, "residual_filter_factor leaves no modes");
         ACE_TRY(plan_build(c.nlat, c.nlon, rl, rm, (Grid)c.data_grid, n->plan_res, false));
         const size_t n2 = (size_t)n->Bmax * 2 * c.in_chans;
-        HIP_TRY(n->resX.alloc_x(((size_t)rm * c.nlat + LEG_STRIP_SLACK_ROWS) * n2, n->sw.polar_poison));
-        HIP_TRY(n->resD.alloc(((size_t)rl + LEG_STRIP_SLACK_ROWS) * rm * n2));
-        HIP_TRY(n->inF.alloc((size_t)n->Bmax * c.in_chans * n->HW));
+        ACE_HIP_TRY(n->resX.alloc_x(((size_t)rm * c.nlat + LEG_STRIP_SLACK_ROWS) * n2, n->sw.polar_poison));
+        ACE_HIP_TRY(n->resD.alloc(((size_t)rl + LEG_STRIP_SLACK_ROWS) * rm * n2));
+        ACE_HIP_TRY(n->inF.alloc((size_t)n->Bmax * c.in_chans * n->HW));
     }
 
     // parameters in the reference's state_dict order
@@ -1351,50 +1329,50 @@ extern "C" int ace_sfno_create(const ace_sfno_config* cfg, ace_sfno** out) {
         n->dh_units.resize(n->Bmax);
         n->dh_units_per_xcd.assign(n->Bmax, 0);
         for (int b = 1; b <= n->Bmax; ++b)
-            HIP_TRY(upload_dhconv_units(n->L, n->Mm * b, b, n->C, n->dh_units[b - 1], &n->dh_units_per_xcd[b - 1]));
+            ACE_HIP_TRY(upload_dhconv_units(n->L, n->Mm * b, b, n->C, n->dh_units[b - 1], &n->dh_units_per_xcd[b - 1]));
     }
     const size_t act = (size_t)n->Bmax * C * HW;
     // + slack rows read (never used) by the strip Legendre kernels past the last contraction row
     const size_t spec_x = ((size_t)n->Mm * n->H + LEG_STRIP_SLACK_ROWS) * n->Bmax * 2 * C;
     const size_t spec_d = ((size_t)n->L + LEG_STRIP_SLACK_ROWS) * n->Mm * n->Bmax * 2 * C;
-    HIP_TRY(n->h0.alloc(act));
-    HIP_TRY(n->h1.alloc(act));
-    HIP_TRY(n->Y.alloc(act));
-    HIP_TRY(n->T.alloc(act));
-    if (n->plan_data != n->plan_lg.get()) HIP_TRY(n->R.alloc(act));
-    if (c.use_mlp) HIP_TRY(n->U.alloc((size_t)n->Bmax * n->hid * HW, true));
+    ACE_HIP_TRY(n->h0.alloc(act));
+    ACE_HIP_TRY(n->h1.alloc(act));
+    ACE_HIP_TRY(n->Y.alloc(act));
+    ACE_HIP_TRY(n->T.alloc(act));
+    if (n->plan_data != n->plan_lg.get()) ACE_HIP_TRY(n->R.alloc(act));
+    if (c.use_mlp) ACE_HIP_TRY(n->U.alloc((size_t)n->Bmax * n->hid * HW, true));
     if (c.precision == 1) {
-        HIP_TRY(n->P.alloc(act, true));
+        ACE_HIP_TRY(n->P.alloc(act, true));
         if (c.normalization_layer == 1 && c.use_mlp) {
-            HIP_TRY(n->P2.alloc(act, true));
+            ACE_HIP_TRY(n->P2.alloc(act, true));
             n->nstrips = (int)((HW + 31) / 32) + 8;     // >= tilesN * WN of either tile shape and conv_ws's 32-pixel tiles
             // the per-sample fold buffers: needed when ANY block of this net runs that role on conv_ws.hip / conv_wl.hip
             auto any = [&](auto q) { return any_block(c.num_layers, HW, n->HWs, q); };
             if (any([&](long hw) { return fc1_on_conv_ws(n->sw.conv_ws_roles, (int)C, n->hid, hw) || fc1_on_conv_wl(n->sw.conv_wl, (int)C, n->hid, hw); }))
-                HIP_TRY(n->Wq1.alloc((size_t)n->Bmax * n->hid * C, true));   // hi + lo halves = one float per element
-            if (any([&](long hw) { return skip_on_conv_ws(n->sw.conv_ws_roles, (int)C, (int)C, hw); })) HIP_TRY(n->Wq0.alloc((size_t)n->Bmax * C * C, true));
-            HIP_TRY(n->zero_c.alloc((size_t)C, true));
-            HIP_TRY(n->inP.alloc((size_t)n->Bmax * ((c.in_chans + 7) / 8 * 8) * n->HW, true));   // two planes of halves = one float per element
-            HIP_TRY(n->pe_slot.alloc(64, true));
-            HIP_TRY(n->part.alloc((size_t)2 * n->Bmax * n->nstrips * C * 4, true));
+                ACE_HIP_TRY(n->Wq1.alloc((size_t)n->Bmax * n->hid * C, true));   // hi + lo halves = one float per element
+            if (any([&](long hw) { return skip_on_conv_ws(n->sw.conv_ws_roles, (int)C, (int)C, hw); })) ACE_HIP_TRY(n->Wq0.alloc((size_t)n->Bmax * C * C, true));
+            ACE_HIP_TRY(n->zero_c.alloc((size_t)C, true));
+            ACE_HIP_TRY(n->inP.alloc((size_t)n->Bmax * ((c.in_chans + 7) / 8 * 8) * n->HW, true));   // two planes of halves = one float per element
+            ACE_HIP_TRY(n->pe_slot.alloc(64, true));
+            ACE_HIP_TRY(n->part.alloc((size_t)2 * n->Bmax * n->nstrips * C * 4, true));
             const size_t cp = (size_t)((C + 31) & ~31);
-            HIP_TRY(n->Wp0.alloc((size_t)n->Bmax * ((C + 15) / 16 * 16) * cp, true));       // 2 planes of halves = 1 float per element
-            HIP_TRY(n->Wp1.alloc((size_t)n->Bmax * ((n->hid + 15) / 16 * 16) * cp, true));
+            ACE_HIP_TRY(n->Wp0.alloc((size_t)n->Bmax * ((C + 15) / 16 * 16) * cp, true));       // 2 planes of halves = 1 float per element
+            ACE_HIP_TRY(n->Wp1.alloc((size_t)n->Bmax * ((n->hid + 15) / 16 * 16) * cp, true));
         }
     }
-    HIP_TRY(n->X.alloc_x(spec_x, n->sw.polar_poison));
-    HIP_TRY(n->D.alloc(spec_d));
-    HIP_TRY(n->E.alloc(spec_d));
-    HIP_TRY(n->stats.alloc((size_t)4 * n->Bmax * C));
+    ACE_HIP_TRY(n->X.alloc_x(spec_x, n->sw.polar_poison));
+    ACE_HIP_TRY(n->D.alloc(spec_d));
+    ACE_HIP_TRY(n->E.alloc(spec_d));
+    ACE_HIP_TRY(n->stats.alloc((size_t)4 * n->Bmax * C));
     if (cln) {
-        HIP_TRY(n->cln_stats.alloc((size_t)2 * n->Bmax * HW));
-        if (c.normalize_big_skip && c.big_skip) HIP_TRY(n->inN.alloc((size_t)n->Bmax * c.in_chans * HW));
+        ACE_HIP_TRY(n->cln_stats.alloc((size_t)2 * n->Bmax * HW));
+        if (c.normalize_big_skip && c.big_skip) ACE_HIP_TRY(n->inN.alloc((size_t)n->Bmax * c.in_chans * HW));
     }
-    HIP_TRY(n->amax.alloc((size_t)(16 + 12 * c.num_layers + 1) * AMAX_SHARDS));   // + the conditioning field's slot
+    ACE_HIP_TRY(n->amax.alloc((size_t)(16 + 12 * c.num_layers + 1) * AMAX_SHARDS));   // + the conditioning field's slot
     if (c.normalization_layer == 1) {
-        HIP_TRY(n->bf0.alloc((size_t)n->Bmax * C));
+        ACE_HIP_TRY(n->bf0.alloc((size_t)n->Bmax * C));
         if (c.use_mlp) {
-            HIP_TRY(n->bf1.alloc((size_t)n->Bmax * n->hid));
+            ACE_HIP_TRY(n->bf1.alloc((size_t)n->Bmax * n->hid));
         }
     }
     *out = n.release();
@@ -1457,16 +1435,16 @@ extern "C" long ace_sfno_weight_numel(const ace_sfno* n, int i) {
 // (wx_native) or expanded to the dense form
 static int store_library_copy(ace_sfno* n, Weight& w, const float* src, hipStream_t s) {
     if (w.rows > 0) {
-        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)w.rows * w.pitch, true));  // zero padding columns
-        HIP_TRY(hipMemcpy2DAsync(w.buf.p, sizeof(float) * w.pitch, src, sizeof(float) * w.cols, sizeof(float) * w.cols,
+        if (!w.buf.p) ACE_HIP_TRY(w.buf.alloc((size_t)w.rows * w.pitch, true));  // zero padding columns
+        ACE_HIP_TRY(hipMemcpy2DAsync(w.buf.p, sizeof(float) * w.pitch, src, sizeof(float) * w.cols, sizeof(float) * w.cols,
                                  w.rows, hipMemcpyDeviceToDevice, s));
     } else if (w.ext_numel && !n->wx_native[w.block]) {   // (G, L, C/G, C/G, 2) -> dense (Cin, Cout, L, 2), then as any dhconv weight
-        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)w.numel, false));
-        HIP_TRY(launch_csfno_weight_to_dense(src, w.buf.p, n->C, n->cfg.filter_num_groups, n->L, s));
+        if (!w.buf.p) ACE_HIP_TRY(w.buf.alloc((size_t)w.numel, false));
+        ACE_HIP_TRY(launch_csfno_weight_to_dense(src, w.buf.p, n->C, n->cfg.filter_num_groups, n->L, s));
     } else {
         const long numel = w.ext_numel ? w.ext_numel : w.numel;
-        if (!w.buf.p) HIP_TRY(w.buf.alloc((size_t)numel, false));
-        HIP_TRY(hipMemcpyAsync(w.buf.p, src, sizeof(float) * numel, hipMemcpyDeviceToDevice, s));
+        if (!w.buf.p) ACE_HIP_TRY(w.buf.alloc((size_t)numel, false));
+        ACE_HIP_TRY(hipMemcpyAsync(w.buf.p, src, sizeof(float) * numel, hipMemcpyDeviceToDevice, s));
     }
     return ACE_OK;
 }
@@ -1477,8 +1455,8 @@ static int store_filter_operand(ace_sfno* n, Weight& w, hipStream_t s) {
     const int b = w.block, C = n->C, G = n->cfg.filter_num_groups;
     const size_t cnt = (size_t)n->L * 2 * C * 2 * C;
     if (n->cfg.precision != 1 || (2 * C) % 32 != 0) {
-        if (!n->wx[b].p) HIP_TRY(n->wx[b].alloc(cnt, false));
-        HIP_TRY(launch_expand_dhconv_weight(w.buf.p, n->wx[b].p, C, C, n->L, s));
+        if (!n->wx[b].p) ACE_HIP_TRY(n->wx[b].alloc(cnt, false));
+        ACE_HIP_TRY(launch_expand_dhconv_weight(w.buf.p, n->wx[b].p, C, C, n->L, s));
         return ACE_OK;
     }
     const bool native = n->wx_native[b] != 0, compact = n->wx_compact[b] != 0;
@@ -1486,11 +1464,11 @@ static int store_filter_operand(ace_sfno* n, Weight& w, hipStream_t s) {
     ACE_TRY(device_absmax(w.buf.p, native ? w.ext_numel : w.numel, s, &mx));
     const float sc = n->wx_scale[b] = pow2_scale(mx, 10);
     const size_t halves = native ? cnt / 2 / G : (compact ? cnt / 2 : cnt);
-    if (!n->wx_hi[b].p) HIP_TRY(n->wx_hi[b].alloc((halves + 1) / 2, false));
-    if (!n->wx_lo[b].p) HIP_TRY(n->wx_lo[b].alloc((halves + 1) / 2, false));
-    if (native) HIP_TRY(launch_pack_dhconv_f16g(w.buf.p, n->wx_hi[b].p, n->wx_lo[b].p, C, G, n->L, sc, s));
-    else if (compact) HIP_TRY(launch_pack_dhconv_f16c(w.buf.p, n->wx_hi[b].p, n->wx_lo[b].p, C, C, n->L, sc, s));
-    else HIP_TRY(launch_pack_dhconv_f16(w.buf.p, n->wx_hi[b].p, n->wx_lo[b].p, C, C, n->L, sc, s));
+    if (!n->wx_hi[b].p) ACE_HIP_TRY(n->wx_hi[b].alloc((halves + 1) / 2, false));
+    if (!n->wx_lo[b].p) ACE_HIP_TRY(n->wx_lo[b].alloc((halves + 1) / 2, false));
+    if (native) ACE_HIP_TRY(launch_pack_dhconv_f16g(w.buf.p, n->wx_hi[b].p, n->wx_lo[b].p, C, G, n->L, sc, s));
+    else if (compact) ACE_HIP_TRY(launch_pack_dhconv_f16c(w.buf.p, n->wx_hi[b].p, n->wx_lo[b].p, C, C, n->L, sc, s));
+    else ACE_HIP_TRY(launch_pack_dhconv_f16(w.buf.p, n->wx_hi[b].p, n->wx_lo[b].p, C, C, n->L, sc, s));
     return ACE_OK;
 }
 // f16x3 conv weights: planes + norms in both orders, and the static fragments of the roles conv_ws.hip / conv_wl.hip serve
@@ -1498,8 +1476,8 @@ static int store_conv_operand(ace_sfno* n, Weight& w, hipStream_t s) {
     if (n->cfg.precision != 1) return ACE_OK;
     ACE_TRY(prepare_conv_operand(w.buf.p, w.rows, w.cols, w.pitch, PLANES_ROWS | PLANES_TILED, s, w));
     if (keeps_static_frags(n, w)) {
-        if (!w.frag0.p) HIP_TRY(w.frag0.alloc((size_t)w.rows * w.cols, false));
-        HIP_TRY(launch_pack_conv_frag(w.buf.p, w.pitch, w.rows, w.cols, 0, nullptr, 0.f, w.ascale, nullptr, w.frag0.p, 0, 1, s));
+        if (!w.frag0.p) ACE_HIP_TRY(w.frag0.alloc((size_t)w.rows * w.cols, false));
+        ACE_HIP_TRY(launch_pack_conv_frag(w.buf.p, w.pitch, w.rows, w.cols, 0, nullptr, 0.f, w.ascale, nullptr, w.frag0.p, 0, 1, s));
     }
     return ACE_OK;
 }
@@ -1518,7 +1496,7 @@ static int store_pos_embed_slot(ace_sfno* n, Weight& w, hipStream_t s) {
     float mx = 0.f;
     ACE_TRY(device_absmax(w.buf.p, w.numel, s, &mx));   // (C x H x W values: reduced where they are, not through a host copy)
     const std::vector<float> rep(64, mx);
-    HIP_TRY(hipMemcpy(n->pe_slot.p, rep.data(), rep.size() * sizeof(float), hipMemcpyHostToDevice));
+    ACE_HIP_TRY(hipMemcpy(n->pe_slot.p, rep.data(), rep.size() * sizeof(float), hipMemcpyHostToDevice));
     return ACE_OK;
 }
 // biases and norm affines: the bound used by the P-format producers
@@ -1548,7 +1526,7 @@ extern "C" int ace_sfno_set_weight(ace_sfno* n, const char* name, const float* s
         case ROLE_CLN_COND: ACE_TRY(store_cln_frags(n, w, s)); break;
         default: ACE_TRY(store_conv_operand(n, w, s)); break;   // the convolutions
     }
-    HIP_TRY(hipStreamSynchronize(s));
+    ACE_HIP_TRY(hipStreamSynchronize(s));
     w.set = true;
     // Captured graphs keep pointing at the same library buffers, but the host-side scalars derived from the weights
     // (ascale, winf, wabs, bias bounds, filter scale) are baked into their kernel arguments by value: drop the graphs so
@@ -1866,10 +1844,10 @@ static int conv(const Fwd& f, const ConvW& cw, const float* in, long in_bstride,
     if (f.n->cfg.precision == 1 && cw.hi && cw.sw == 0 && bmax && gemm_f16x3_eligible(g)) {
         // compensated fp16 with the B scale derived in-kernel from max|B| (slot written by B's producer)
         if (g.act == ACT_GELU) g.act = ACT_GELU_FAST;  // the epilogue is on the critical path of this engine
-        HIP_TRY(launch_gemm_f16x3(g, cw.hi, cw.lo, cw.ascale, 1.0f, f.s, bmax, omax, (in2 ? bmax2 : nullptr)));
+        ACE_HIP_TRY(launch_gemm_f16x3(g, cw.hi, cw.lo, cw.ascale, 1.0f, f.s, bmax, omax, (in2 ? bmax2 : nullptr)));
         return ACE_OK;
     }
-    HIP_TRY(launch_gemm(g, f.s));
+    ACE_HIP_TRY(launch_gemm(g, f.s));
     return ACE_OK;
 }
 
@@ -1877,7 +1855,7 @@ static int conv(const Fwd& f, const ConvW& cw, const float* in, long in_bstride,
 // from the bound in `in_slot`).  Output: fp32 (+ omax) and/or P-format planes for the next convolution.
 static int pack_act(const Fwd& f, const float* x, long x_bs, int cin, const float* sc, const float* sh, const unsigned* slot,
                     void* hi, void* lo) {
-    HIP_TRY(launch_pack_pformat(x, f.HW, x_bs, cin, (int)f.HW, f.B, sc, sh, sc ? cin : 0, slot, hi, lo, f.HW, (long)cin * f.HW, f.s));
+    ACE_HIP_TRY(launch_pack_pformat(x, f.HW, x_bs, cin, (int)f.HW, f.B, sc, sh, sc ? cin : 0, slot, hi, lo, f.HW, (long)cin * f.HW, f.s));
     return ACE_OK;
 }
 struct PkOpts {
@@ -1913,7 +1891,7 @@ static int conv_packed(const Fwd& f, const PkOpts& o) {
     a.R = o.R; a.ldr = f.HW; a.sR = o.r_bs; a.rsc = o.rsc; a.rsh = o.rsh; a.srs = o.rsc ? o.cout : 0;
     a.M = o.cout; a.N = (int)f.HW; a.K = o.cin; a.nbatch = f.B;
     a.act = o.act == ACT_GELU ? ACT_GELU_FAST : o.act;
-    HIP_TRY(launch_gemm_f16x3_packed(a, f.s));
+    ACE_HIP_TRY(launch_gemm_f16x3_packed(a, f.s));
     return ACE_OK;
 }
 // conv_ws.hip / conv_wl.hip: what every launch shares - a cin-channel input as planes at the resolution being enqueued
@@ -1956,13 +1934,13 @@ static int cond_norm(const Fwd& f, const float* x, float* y, const std::string& 
             if (!fp32_needed) a.y = nullptr;
         }
         if (cln_mfma_eligible(a)) {
-            HIP_TRY(launch_cln_mfma(a, f.s));
+            ACE_HIP_TRY(launch_cln_mfma(a, f.s));
             if (planes_done) *planes_done = a.Phi != nullptr;
             return ACE_OK;
         }
         a.Phi = a.Plo = nullptr; a.y = y;
     }
-    HIP_TRY(launch_cond_layer_norm(x, f.noise, a.gamma, a.beta, f.W(q + "W_scale_2d.weight"), f.W(q + "W_bias_2d.weight"), 1e-5f,
+    ACE_HIP_TRY(launch_cond_layer_norm(x, f.noise, a.gamma, a.beta, f.W(q + "W_scale_2d.weight"), f.W(q + "W_bias_2d.weight"), 1e-5f,
                                    n->cln_stats.p, y, f.B, Cc, J, f.HW, f.s, omax));
     return ACE_OK;
 }
@@ -1975,8 +1953,8 @@ static int enqueue_encoder(Fwd& f, const float* in) {
     const int C = n->C, Cin = c.in_chans, act = c.activation_function;
     const long HW = f.HW, actB = f.actB();
     if (c.precision == 1) {
-        HIP_TRY(launch_zero_u32(f.slot(0), (long)n->amax.n, f.s));
-        HIP_TRY(launch_absmax(in, (long)f.B * Cin * HW, f.slot(0), f.s));
+        ACE_HIP_TRY(launch_zero_u32(f.slot(0), (long)n->amax.n, f.s));
+        ACE_HIP_TRY(launch_absmax(in, (long)f.B * Cin * HW, f.slot(0), f.s));
     }
     const float* cur = in;
     long cur_bs = (long)Cin * HW;
@@ -1987,7 +1965,7 @@ static int enqueue_encoder(Fwd& f, const float* in) {
         const int cin8 = (Cin + 7) / 8 * 8;
         _Float16* Ih = reinterpret_cast<_Float16*>(n->inP.p);
         _Float16* Il = Ih + (size_t)n->Bmax * cin8 * HW;
-        HIP_TRY(launch_pack_pformat(in, HW, (long)Cin * HW, Cin, (int)HW, f.B, nullptr, nullptr, 0, f.slot(0), Ih, Il, HW, (long)cin8 * HW, f.s));
+        ACE_HIP_TRY(launch_pack_pformat(in, HW, (long)Cin * HW, Cin, (int)HW, f.B, nullptr, nullptr, 0, f.slot(0), Ih, Il, HW, (long)cin8 * HW, f.s));
         PkOpts o;
         o.w = &f.wt("encoder.0.weight"); o.bias = b0.buf.p;
         o.bhi = Ih; o.blo = Il; o.cin = cin8; o.in_slot = f.slot(0);
@@ -2013,13 +1991,13 @@ static int enqueue_encoder(Fwd& f, const float* in) {
         k.Chi = f.PBh; k.Clo = f.PBl; k.sCp = (long)C * HW; k.cslot = f.hslot(0);
         k.cw = we.winf; k.cb = 0.f; k.rmax = reinterpret_cast<const unsigned*>(n->pe_slot.p);
         k.part = reinterpret_cast<float4*>(f.part_h); k.nstrips32 = r.enc_nparts;
-        HIP_TRY(launch_conv_ws(k, f.s));
+        ACE_HIP_TRY(launch_conv_ws(k, f.s));
     } else {
         ACE_TRY(conv(f, conv_weight(n, last, ""), cur, cur_bs, curC, nullptr, 0, -1, f.h, C, c.pos_embed ? f.W("pos_embed") : nullptr, 0,
                      nullptr, nullptr, ACT_NONE, nullptr, nullptr, f.slot(c.encoder_layers), nullptr, f.hslot(0)));
     }
     MARK(ST_ENCODER);
-    if (n->taps_on) HIP_TRY(hipMemcpyAsync(n->taps[0].p, f.h, sizeof(float) * f.B * actB, hipMemcpyDeviceToDevice, f.s));
+    if (n->taps_on) ACE_HIP_TRY(hipMemcpyAsync(n->taps[0].p, f.h, sizeof(float) * f.B * actB, hipMemcpyDeviceToDevice, f.s));
     return ACE_OK;
 }
 
@@ -2031,7 +2009,7 @@ static int enqueue_big_skip_source(Fwd& f, const float* in) {
     f.skip_in = in;
     f.skip_in_slot = f.slot(0);
     if (f.route->noise_range)
-        HIP_TRY(launch_absmax(f.noise, (long)f.B * c.noise_embed_dim * f.HW, f.slot(16 + 12 * c.num_layers), f.s));
+        ACE_HIP_TRY(launch_absmax(f.noise, (long)f.B * c.noise_embed_dim * f.HW, f.slot(16 + 12 * c.num_layers), f.s));
     if (n->plan_res) {   // residual = residual_filter_up(residual_filter_down(x)) (sfnonet.py:715-716), exact fp32; its range into slot 7
         const long NR = (long)f.B * 2 * Cin;
         // (an fp32 plan: no folded kernels, so neither pair takes the polar cut - asked all the same, in the one place that decides)
@@ -2059,7 +2037,7 @@ static int enqueue_norm0(Fwd& f, int i, const BlockRoute& b) {
     const ace_sfno* n = f.n;
     const int C = n->C, sb = 16 + 12 * i, kind = n->cfg.normalization_layer;
     const std::string p = "blocks." + std::to_string(i) + ".";
-    if (n->cfg.precision == 1 && i + 1 >= 8) HIP_TRY(launch_zero_u32(f.hslot(i + 1), AMAX_SHARDS, f.s));
+    if (n->cfg.precision == 1 && i + 1 >= 8) ACE_HIP_TRY(launch_zero_u32(f.hslot(i + 1), AMAX_SHARDS, f.s));
     f.a0 = f.b0 = nullptr;
     f.n0_planes = false;
     if (kind == 0) return ACE_OK;
@@ -2067,13 +2045,13 @@ static int enqueue_norm0(Fwd& f, int i, const BlockRoute& b) {
         ACE_TRY(cond_norm(f, f.h, f.h, p + "norm0.", C, f.slot(sb + 3), b.n0_to_planes ? f.PAh : nullptr,
                           b.n0_to_planes ? f.Pl() : nullptr, true, &f.n0_planes));
     } else if (kind == 3) {   // x_norm = LayerNorm_(H, W)(h), in place
-        HIP_TRY(launch_spatial_layer_norm(f.h, f.W(p + "norm0.weight"), f.W(p + "norm0.bias"), 1e-6f, (long)f.B * C, f.HW, f.h, f.slot(sb + 3), f.s));
+        ACE_HIP_TRY(launch_spatial_layer_norm(f.h, f.W(p + "norm0.weight"), f.W(p + "norm0.bias"), 1e-6f, (long)f.B * C, f.HW, f.h, f.slot(sb + 3), f.s));
     } else {
         if (b.in_planes)   // statistics of h came out of the producer's epilogue
-            HIP_TRY(launch_instnorm_finalize(reinterpret_cast<const float4*>(f.part_h), b.in_nparts, f.B, C, f.HW,
+            ACE_HIP_TRY(launch_instnorm_finalize(reinterpret_cast<const float4*>(f.part_h), b.in_nparts, f.B, C, f.HW,
                                              f.W(p + "norm0.weight"), f.W(p + "norm0.bias"), 1e-6f, f.sc0, f.sh0, f.slot(sb + 3), f.s));
         else
-            HIP_TRY(launch_instnorm_stats(f.h, f.W(p + "norm0.weight"), f.W(p + "norm0.bias"), 1e-6f, f.B, C, f.HW, f.sc0, f.sh0, f.s,
+            ACE_HIP_TRY(launch_instnorm_stats(f.h, f.W(p + "norm0.weight"), f.W(p + "norm0.bias"), 1e-6f, f.B, C, f.HW, f.sc0, f.sh0, f.s,
                                           f.slot(sb + 3)));
         f.a0 = f.sc0; f.b0 = f.sh0;
     }
@@ -2129,7 +2107,7 @@ static int enqueue_contraction(Fwd& f, int i, const BlockRoute& b) {
     unsigned *dmax = f.slot(sb + 1), *emax = f.slot(sb + 2);
     switch (b.filter) {
     case FLT_DHCONV_STRIP:
-        HIP_TRY(launch_dhconv_strip(dhconv_strip_args(n, i, B, dmax, emax), f.s));
+        ACE_HIP_TRY(launch_dhconv_strip(dhconv_strip_args(n, i, B, dmax, emax), f.s));
         break;
     case FLT_PACKED_TILE: {
         Gemm4Args a;
@@ -2143,7 +2121,7 @@ static int enqueue_contraction(Fwd& f, int i, const BlockRoute& b) {
         a.C = n->E.p; a.ldc = 2 * C; a.sC = (long)n->Mm * N2; a.omax = emax;
         a.M = n->Mm * B; a.N = 2 * C; a.K = 2 * C; a.nbatch = n->L;
         a.tri = TRI_ROWS_LE_BATCH; a.trimul = B;
-        HIP_TRY(launch_gemm_f16x3_packed(a, f.s));
+        ACE_HIP_TRY(launch_gemm_f16x3_packed(a, f.s));
         break;
     }
     case FLT_ADYN_F16X3:
@@ -2156,13 +2134,13 @@ static int enqueue_contraction(Fwd& f, int i, const BlockRoute& b) {
         g.tri = TRI_ROWS_LE_BATCH; g.trimul = B;
         g.omax = emax;
         if (b.filter == FLT_ADYN_F16X3)
-            HIP_TRY(launch_gemm_f16x3_adyn(g, n->wx_hi[i].p, n->wx_lo[i].p, 2 * C, (long)2 * C * 2 * C, n->wx_scale[i], dmax, emax, f.s));
+            ACE_HIP_TRY(launch_gemm_f16x3_adyn(g, n->wx_hi[i].p, n->wx_lo[i].p, 2 * C, (long)2 * C * 2 * C, n->wx_scale[i], dmax, emax, f.s));
         else
-            HIP_TRY(launch_gemm(g, f.s));
+            ACE_HIP_TRY(launch_gemm(g, f.s));
         break;
     }
     case FLT_DIAGONAL:
-        HIP_TRY(launch_contract_diagonal(n->D.p, f.W("blocks." + std::to_string(i) + ".filter.filter.weight"), n->E.p, B, C, C, n->L, n->Mm, f.s, emax));
+        ACE_HIP_TRY(launch_contract_diagonal(n->D.p, f.W("blocks." + std::to_string(i) + ".filter.filter.weight"), n->E.p, B, C, C, n->L, n->Mm, f.s, emax));
         break;
     }
     MARK(ST_CONTRACT);
@@ -2209,7 +2187,7 @@ static int enqueue_fused_body(Fwd& f, int i, const BlockRoute& b) {
     const unsigned* in_slot = f.slot(b.skip_slot);
     if (b.in_planes) {   // h planes from the producer; the affine goes into the weights
         if (b.skip != CONV_WS)
-            HIP_TRY(launch_fold_affine_f16(ws.buf.p, ws.pitch, ws.wabs, f.ra, f.rb, bsw.buf.p, F0h, F0l, n->bf0.p, B, C, C, cp, f0s, f.slot(sb + 8), s));
+            ACE_HIP_TRY(launch_fold_affine_f16(ws.buf.p, ws.pitch, ws.wabs, f.ra, f.rb, bsw.buf.p, F0h, F0l, n->bf0.p, B, C, C, cp, f0s, f.slot(sb + 8), s));
         skip_bias = n->bf0.p; skip_sbias = C; in_slot = f.hslot(i);
     } else {             // first block: normalise + split h in one pass
         ACE_TRY(pack_act(f, f.res, actB, C, f.ra, f.rb, in_slot, f.PBh, f.PBl));
@@ -2219,7 +2197,7 @@ static int enqueue_fused_body(Fwd& f, int i, const BlockRoute& b) {
         if (b.in_planes) {
             _Float16* Q0 = reinterpret_cast<_Float16*>(n->Wq0.p);
             if (!f.skip_pack_rode)   // (packed by rider workgroups of this block's forward FFT otherwise)
-                HIP_TRY(launch_pack_conv_frag(ws.buf.p, ws.pitch, C, C, 0, f.ra, ws.wabs, 1.f, f.slot(sb + 8), Q0, (long)C * C * 2, B, s,
+                ACE_HIP_TRY(launch_pack_conv_frag(ws.buf.p, ws.pitch, C, C, 0, f.ra, ws.wabs, 1.f, f.slot(sb + 8), Q0, (long)C * C * 2, B, s,
                                               f.rb, bsw.buf.p, n->bf0.p));
             k.A = Q0; k.sA = (long)C * C * 2; k.aslot = f.slot(sb + 8);
         } else {
@@ -2230,7 +2208,7 @@ static int enqueue_fused_body(Fwd& f, int i, const BlockRoute& b) {
         k.cw = ws.winf; k.cb = bsw.absmax; k.cinb = f.slot(sb + 3); k.rmax = f.slot(sb + 7);
         k.Chi = f.PAh; k.Clo = f.PAl; k.sCp = (long)C * HW; k.cslot = f.slot(sb + 4);
         k.part = reinterpret_cast<float4*>(f.part_t); k.nstrips32 = b.t_nparts;   // one partial per pixel group (accumulated in registers)
-        HIP_TRY(launch_conv_ws(k, s));
+        ACE_HIP_TRY(launch_conv_ws(k, s));
     } else {
         PkOpts o;
         o.w = &ws; o.cin = C; o.cout = C; o.act = act;
@@ -2245,14 +2223,14 @@ static int enqueue_fused_body(Fwd& f, int i, const BlockRoute& b) {
     MARK(ST_INNER_SKIP);
 
     // norm1 statistics -> affine -> folded fc1 weights; fc1 writes U = act(.) as planes
-    HIP_TRY(launch_instnorm_finalize(reinterpret_cast<const float4*>(f.part_t), b.t_nparts, B, C, HW, f.W(p + "norm1.weight"),
+    ACE_HIP_TRY(launch_instnorm_finalize(reinterpret_cast<const float4*>(f.part_t), b.t_nparts, B, C, HW, f.W(p + "norm1.weight"),
                                      f.W(p + "norm1.bias"), 1e-6f, f.sc1, f.sh1, f.slot(sb + 5), s));
     if (b.fc1 == CONV_WS || b.fc1 == CONV_WL) {
         _Float16* Q1 = reinterpret_cast<_Float16*>(n->Wq1.p);
         const long q1s = (long)hid * C * 2;
         // (pfold: W1 diag(a1), b1 + W1 b1' folded in the convolution's own prologue: +1.4 us against a 6.7 us launch)
         if (!b.pfold)
-            HIP_TRY(launch_pack_conv_frag(w1.buf.p, w1.pitch, hid, C, 0, f.sc1, w1.wabs, 1.f, f.slot(sb + 9), Q1, q1s, B, s, f.sh1,
+            ACE_HIP_TRY(launch_pack_conv_frag(w1.buf.p, w1.pitch, hid, C, 0, f.sc1, w1.wabs, 1.f, f.slot(sb + 9), Q1, q1s, B, s, f.sh1,
                                           b1w.buf.p, n->bf1.p));
         MARK(ST_NORM1);
         ConvStripArgs k = strip_args(f, f.PAh, f.PAl, f.slot(sb + 4), C, hid, ACT_GELU);
@@ -2265,9 +2243,9 @@ static int enqueue_fused_body(Fwd& f, int i, const BlockRoute& b) {
         }
         k.cw = w1.winf; k.cb = b1w.absmax; k.cinb = f.slot(sb + 5);
         k.Chi = Uh; k.Clo = Ul; k.sCp = (long)hid * HW; k.cslot = f.slot(sb + 6);
-        HIP_TRY(b.fc1 == CONV_WL ? launch_conv_wl(k, s) : launch_conv_ws(k, s));
+        ACE_HIP_TRY(b.fc1 == CONV_WL ? launch_conv_wl(k, s) : launch_conv_ws(k, s));
     } else {
-        HIP_TRY(launch_fold_affine_f16(w1.buf.p, w1.pitch, w1.wabs, f.sc1, f.sh1, b1w.buf.p, F1h, F1l, n->bf1.p, B, hid, C, cp, f1s,
+        ACE_HIP_TRY(launch_fold_affine_f16(w1.buf.p, w1.pitch, w1.wabs, f.sc1, f.sh1, b1w.buf.p, F1h, F1l, n->bf1.p, B, hid, C, cp, f1s,
                                        f.slot(sb + 9), s));
         MARK(ST_NORM1);
         PkOpts f1;
@@ -2296,7 +2274,7 @@ static int enqueue_fused_body(Fwd& f, int i, const BlockRoute& b) {
         } else {
             k.omax = f.hslot(i + 1);
         }
-        HIP_TRY(launch_conv_ws(k, s));
+        ACE_HIP_TRY(launch_conv_ws(k, s));
     } else {
         PkOpts f2;
         f2.w = &w2; f2.bias = b2w.buf.p;
@@ -2327,9 +2305,9 @@ static int enqueue_norm1(Fwd& f, int i, const BlockRoute& b, const float** a1, c
         ACE_TRY(cond_norm(f, n->T.p, n->T.p, p + "norm1.", C, f.slot(sb + 5), b.n1_to_planes ? f.PAh : nullptr,
                           b.n1_to_planes ? f.Pl() : nullptr, false, planes));
     } else if (kind == 3) {
-        HIP_TRY(launch_spatial_layer_norm(n->T.p, f.W(p + "norm1.weight"), f.W(p + "norm1.bias"), 1e-6f, (long)f.B * C, f.HW, n->T.p, f.slot(sb + 5), f.s));
+        ACE_HIP_TRY(launch_spatial_layer_norm(n->T.p, f.W(p + "norm1.weight"), f.W(p + "norm1.bias"), 1e-6f, (long)f.B * C, f.HW, n->T.p, f.slot(sb + 5), f.s));
     } else {
-        HIP_TRY(launch_instnorm_stats(n->T.p, f.W(p + "norm1.weight"), f.W(p + "norm1.bias"), 1e-6f, f.B, C, f.HW, f.sc1, f.sh1, f.s,
+        ACE_HIP_TRY(launch_instnorm_stats(n->T.p, f.W(p + "norm1.weight"), f.W(p + "norm1.bias"), 1e-6f, f.B, C, f.HW, f.sc1, f.sh1, f.s,
                                       f.slot(sb + 5)));
         *a1 = f.sc1; *b1 = f.sh1;
     }
@@ -2354,7 +2332,7 @@ static int enqueue_packed_body(Fwd& f, int i, const BlockRoute& b) {
         static_frags(k, ws, f.W(p + "inner_skip.bias"));
         k.R = n->Y.p; k.sR = actB;
         k.Cf = n->T.p; k.sCf = actB; k.omax = f.slot(sb + 4);
-        HIP_TRY(launch_conv_ws(k, f.s));
+        ACE_HIP_TRY(launch_conv_ws(k, f.s));
     } else {
         PkOpts o;
         o.w = &ws; o.bias = f.W(p + "inner_skip.bias");
@@ -2368,7 +2346,7 @@ static int enqueue_packed_body(Fwd& f, int i, const BlockRoute& b) {
     bool n1_planes;
     ACE_TRY(enqueue_norm1(f, i, b, &a1, &b1, &n1_planes));
     if (b.fc1 == CONV_NONE) {
-        HIP_TRY(launch_rowaffine_add(n->T.p, a1, b1, f.res, f.ra, f.rb, f.hn, (long)f.B * C, HW, f.s));
+        ACE_HIP_TRY(launch_rowaffine_add(n->T.p, a1, b1, f.res, f.ra, f.rb, f.hn, (long)f.B * C, HW, f.s));
         return ACE_OK;
     }
     const Weight &w1 = f.wt(p + "mlp.fwd.0.weight"), &b1w = f.wt(p + "mlp.fwd.0.bias");
@@ -2380,7 +2358,7 @@ static int enqueue_packed_body(Fwd& f, int i, const BlockRoute& b) {
         static_frags(k, w1, b1w.buf.p);
         k.cw = w1.winf; k.cb = b1w.absmax;
         k.Chi = Uh; k.Clo = Ul; k.sCp = (long)hid * HW; k.cslot = f.slot(sb + 6);
-        HIP_TRY(launch_conv_wl(k, f.s));
+        ACE_HIP_TRY(launch_conv_wl(k, f.s));
     } else {
         PkOpts o;
         o.w = &w1; o.bias = b1w.buf.p;
@@ -2416,7 +2394,7 @@ static int enqueue_plain_body(Fwd& f, int i, const BlockRoute& b) {
     bool n1_planes;
     ACE_TRY(enqueue_norm1(f, i, b, &a1, &b1, &n1_planes));
     if (b.fc1 == CONV_NONE) {
-        HIP_TRY(launch_rowaffine_add(n->T.p, a1, b1, f.res, f.ra, f.rb, f.hn, (long)f.B * C, f.HW, f.s));
+        ACE_HIP_TRY(launch_rowaffine_add(n->T.p, a1, b1, f.res, f.ra, f.rb, f.hn, (long)f.B * C, f.HW, f.s));
         return ACE_OK;
     }
     ConvW wfc1 = conv_weight(n, p + "mlp.fwd.0.weight", p + "mlp.fwd.0.bias");
@@ -2483,7 +2461,7 @@ static int forward_impl(const ace_sfno* n, const float* in, float* out, int B, h
         MARK(ST_MLP_FC2);
         std::swap(f.h, f.hn);
         if (n->taps_on)
-            HIP_TRY(hipMemcpyAsync(n->taps[i + 1].p, f.h, sizeof(float) * B * f.actB(), hipMemcpyDeviceToDevice, s));
+            ACE_HIP_TRY(hipMemcpyAsync(n->taps[i + 1].p, f.h, sizeof(float) * B * f.actB(), hipMemcpyDeviceToDevice, s));
     }
     if (n->cfg.normalization_layer == 1 && n->cfg.num_layers > 0) { n->norm_batch = B; n->norm_stream = s; }
     return enqueue_decoder(f, out);
@@ -2541,15 +2519,15 @@ extern "C" int ace_sfno_sht_cut(const ace_sfno* n, double* dead_share, int* kdro
 extern "C" int ace_sfno_norm_affine(const ace_sfno* n, int which, float* scale, float* shift, float* bound) {
     if (!n || !scale || !shift || !bound || which < 0 || which > 1) return fail(ACE_ERR_INVALID, "null argument / which outside {0, 1}");
     if (n->norm_batch <= 0 || !n->stats.p) return fail(ACE_ERR_INVALID, "no instance-norm forward has run on this handle");
-    HIP_TRY(hipStreamSynchronize(n->norm_stream));
+    ACE_HIP_TRY(hipStreamSynchronize(n->norm_stream));
     const size_t bc = (size_t)n->Bmax * n->C, nb = sizeof(float) * n->norm_batch * n->C;
     const float* sc = n->stats.p + (which ? 2 * bc : 0);
-    HIP_TRY(hipMemcpy(scale, sc, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(shift, sc + bc, nb, hipMemcpyDeviceToHost));
+    ACE_HIP_TRY(hipMemcpy(scale, sc, nb, hipMemcpyDeviceToHost));
+    ACE_HIP_TRY(hipMemcpy(shift, sc + bc, nb, hipMemcpyDeviceToHost));
     *bound = -1.f;
     if (const unsigned* slot = range_slot(n, 16 + 12 * (n->cfg.num_layers - 1) + (which ? 5 : 3))) {
         unsigned words[AMAX_SHARDS];
-        HIP_TRY(hipMemcpy(words, slot, sizeof(words), hipMemcpyDeviceToHost));
+        ACE_HIP_TRY(hipMemcpy(words, slot, sizeof(words), hipMemcpyDeviceToHost));
         unsigned m = 0;   // bit patterns of non-negative floats order like the floats
         for (unsigned wd : words) m = wd > m ? wd : m;
         std::memcpy(bound, &m, sizeof(float));
@@ -2566,7 +2544,7 @@ extern "C" int ace_sfno_forward_timed(ace_sfno* n, const float* in, float* out, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     StageTimer tm(s);
     ACE_TRY(forward_impl(n, in, out, batch, s, &tm));
-    HIP_TRY(tm.finish(ms_host, calls_host));
+    ACE_HIP_TRY(tm.finish(ms_host, calls_host));
     return ACE_OK;
 }
 
@@ -2579,7 +2557,7 @@ extern "C" int ace_sfno_forward_conditioned_timed(ace_sfno* n, const float* in, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     StageTimer tm(s);
     ACE_TRY(forward_impl(n, in, out, batch, s, &tm, noise));
-    HIP_TRY(tm.finish(ms_host, calls_host));
+    ACE_HIP_TRY(tm.finish(ms_host, calls_host));
     return ACE_OK;
 }
 
@@ -2589,7 +2567,7 @@ extern "C" int ace_sfno_set_taps(ace_sfno* n, int enable) {
         return fail(ACE_ERR_STATE, "per-block taps are not available for scale_factor != 1");
     if (enable && n->taps.empty()) {
         n->taps = std::vector<DevBuf>(n->cfg.num_layers + 1);
-        for (auto& t : n->taps) HIP_TRY(t.alloc((size_t)n->Bmax * n->C * n->HW));
+        for (auto& t : n->taps) ACE_HIP_TRY(t.alloc((size_t)n->Bmax * n->C * n->HW));
     }
     n->taps_on = enable != 0;
     return ACE_OK;
@@ -2597,7 +2575,7 @@ extern "C" int ace_sfno_set_taps(ace_sfno* n, int enable) {
 extern "C" int ace_sfno_get_tap(ace_sfno* n, int i, float* dst, int batch, void* stream) {
     if (!n || !dst) return fail(ACE_ERR_INVALID, "null argument");
     if (n->taps.empty() || i < -1 || i >= n->cfg.num_layers) return fail(ACE_ERR_STATE, "taps not enabled / bad index");
-    HIP_TRY(hipMemcpyAsync(dst, n->taps[i + 1].p, sizeof(float) * batch * n->C * n->HW, hipMemcpyDeviceToDevice,
+    ACE_HIP_TRY(hipMemcpyAsync(dst, n->taps[i + 1].p, sizeof(float) * batch * n->C * n->HW, hipMemcpyDeviceToDevice,
                            static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
@@ -2608,7 +2586,7 @@ extern "C" int ace_sfno_forward_graph(ace_sfno* n, const float* in, float* out, 
     if (n->taps_on) return fail(ACE_ERR_STATE, "disable taps before using the graph path");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n->graphs_stale) {   // parameters changed since capture: the scalars baked into the kernel arguments are out of date
-        HIP_TRY(hipStreamSynchronize(s));   // no exec of this handle may be in flight when it is destroyed
+        ACE_HIP_TRY(hipStreamSynchronize(s));   // no exec of this handle may be in flight when it is destroyed
         for (auto& kv : n->graphs) (void)hipGraphExecDestroy(kv.second);
         n->graphs.clear();
         n->graphs_stale = false;
@@ -2616,20 +2594,20 @@ extern "C" int ace_sfno_forward_graph(ace_sfno* n, const float* in, float* out, 
     GraphKey key{in, out, batch};
     auto it = n->graphs.find(key);
     if (it == n->graphs.end()) {
-        if (!n->capture_stream) HIP_TRY(hipStreamCreateWithFlags(&n->capture_stream, hipStreamNonBlocking));
+        if (!n->capture_stream) ACE_HIP_TRY(hipStreamCreateWithFlags(&n->capture_stream, hipStreamNonBlocking));
         // everything queued on the caller's stream must be visible to the first replay; capture itself runs nothing
         hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(n->capture_stream, hipStreamCaptureModeThreadLocal));
+        ACE_HIP_TRY(hipStreamBeginCapture(n->capture_stream, hipStreamCaptureModeThreadLocal));
         int rc = forward_impl(n, in, out, batch, n->capture_stream);
         hipError_t e = hipStreamEndCapture(n->capture_stream, &graph);
         if (rc != ACE_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        HIP_TRY(e);
+        ACE_HIP_TRY(e);
         hipGraphExec_t exec = nullptr;
         e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
-        HIP_TRY(e);
+        ACE_HIP_TRY(e);
         it = n->graphs.emplace(key, exec).first;
     }
-    HIP_TRY(hipGraphLaunch(it->second, s));
+    ACE_HIP_TRY(hipGraphLaunch(it->second, s));
     return ACE_OK;
 }

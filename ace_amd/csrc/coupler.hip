@@ -20,15 +20,6 @@
 
 #pragma clang fp contract(off)
 
-static thread_local std::string g_cerr;
-static int cfail(int code, const std::string& m) { g_cerr = m; return code; }
-extern "C" const char* ace_couple_last_error(void) { return g_cerr.c_str(); }
-#define COUPLE_TRY(expr)                                                                                    \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess) return cfail(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 namespace {
 
 constexpr long MAX_PIXELS = 65536;      // per (job, sample) and grid-stride trip
@@ -198,20 +189,20 @@ unsigned grid_x(long hw, long chunk) {
 template <bool WINDOW>
 int launch_o2a(const std::string& name, const float* const* srcs, const long* src_strides, float* const* dsts, const long* dst_strides,
                const float* const* masks, int npass, int mode, int interpolate, int n_inner, int batch, long hw, void* stream) {
-    if (npass < 0 || npass > ACE_COUPLE_MAX_NAMES) return cfail(ACE_ERR_INVALID, name + ": npass outside 0 .. ACE_COUPLE_MAX_NAMES");
+    if (npass < 0 || npass > ACE_COUPLE_MAX_NAMES) return ace::fail(ACE_ERR_INVALID, name + ": npass outside 0 .. ACE_COUPLE_MAX_NAMES");
     if (mode < ACE_COUPLE_OFRAC_CARRIED || mode > ACE_COUPLE_OFRAC_FROM_OCEAN_SIF)
-        return cfail(ACE_ERR_INVALID, name + ": unknown mode");
-    if (interpolate != 0 && interpolate != 1) return cfail(ACE_ERR_INVALID, name + ": interpolate must be 0 or 1");
+        return ace::fail(ACE_ERR_INVALID, name + ": unknown mode");
+    if (interpolate != 0 && interpolate != 1) return ace::fail(ACE_ERR_INVALID, name + ": interpolate must be 0 or 1");
     if (n_inner <= 0 || n_inner > ACE_COUPLE_MAX_INNER)
-        return cfail(ACE_ERR_INVALID, name + ": n_inner outside 1 .. ACE_COUPLE_MAX_INNER");
-    if (batch < 1 || batch > 65535) return cfail(ACE_ERR_INVALID, name + ": batch outside 1 .. 65535");
-    if (hw <= 0) return cfail(ACE_ERR_INVALID, name + ": hw must be positive");
-    if (!srcs || !src_strides || !dsts || !dst_strides || !masks) return cfail(ACE_ERR_INVALID, name + ": null argument");
+        return ace::fail(ACE_ERR_INVALID, name + ": n_inner outside 1 .. ACE_COUPLE_MAX_INNER");
+    if (batch < 1 || batch > 65535) return ace::fail(ACE_ERR_INVALID, name + ": batch outside 1 .. 65535");
+    if (hw <= 0) return ace::fail(ACE_ERR_INVALID, name + ": hw must be positive");
+    if (!srcs || !src_strides || !dsts || !dst_strides || !masks) return ace::fail(ACE_ERR_INVALID, name + ": null argument");
     const int first = mode == ACE_COUPLE_OFRAC_CARRIED ? 3 : 5;
     hipLaunchKernelGGL(o2a_kernel<WINDOW>, dim3(grid_x(hw, O2A_NT * PIX), 1 + npass, batch), dim3(O2A_NT), 0,
                        static_cast<hipStream_t>(stream), srcs, src_strides, dsts, dst_strides, masks, first, mode, interpolate,
                        n_inner + 1, hw);
-    COUPLE_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -235,16 +226,16 @@ extern "C" int ace_couple_atmosphere_to_ocean(const float* const* srcs, const lo
                                               const long* dst_strides, const int* slot, int nnames, int n_inner, int batch,
                                               long hw, void* stream) {
     if (nnames < 0 || nnames > ACE_COUPLE_MAX_NAMES)
-        return cfail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: nnames outside 0 .. ACE_COUPLE_MAX_NAMES");
+        return ace::fail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: nnames outside 0 .. ACE_COUPLE_MAX_NAMES");
     if (n_inner <= 0 || n_inner > ACE_COUPLE_MAX_INNER)
-        return cfail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: n_inner outside 1 .. ACE_COUPLE_MAX_INNER");
-    if (batch < 1 || batch > 65535) return cfail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: batch outside 1 .. 65535");
-    if (hw <= 0) return cfail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: hw must be positive");
+        return ace::fail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: n_inner outside 1 .. ACE_COUPLE_MAX_INNER");
+    if (batch < 1 || batch > 65535) return ace::fail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: batch outside 1 .. 65535");
+    if (hw <= 0) return ace::fail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: hw must be positive");
     if (nnames == 0) return ACE_OK;
     if (!srcs || !src_strides || !dsts || !dst_strides || !slot)
-        return cfail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_couple_atmosphere_to_ocean: null argument");
     hipLaunchKernelGGL(a2o_kernel, dim3(grid_x(hw, CHUNK), nnames, batch), dim3(NT), 0, static_cast<hipStream_t>(stream), srcs,
                        src_strides, dsts, dst_strides, slot, n_inner, hw);
-    COUPLE_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

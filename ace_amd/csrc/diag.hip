@@ -19,11 +19,6 @@
 
 #include "diag_common.h"
 
-static thread_local std::string g_derr;
-static int dfail(int code, const std::string& m) { g_derr = m; return code; }
-extern "C" const char* ace_diag_last_error(void) { return g_derr.c_str(); }
-int ace_diag_fail_(int code, const std::string& m) { return dfail(code, m); }      // hist.hip, regress.hip and DIAG_TRY report here
-
 namespace {
 
 constexpr int NMOM = 3;              // sum of weights, weighted mean, second central moment
@@ -393,37 +388,37 @@ extern "C" long ace_diag_partial_doubles(int nplanes, int batch, int steps, long
 extern "C" int ace_diag_window(const float* const* srcs, const long* strides, const int* rows, const int* wrows,
                                const float* weights, int nw, double* partial, double* tsum, double* series, int nrows, int n_time,
                                int t0, int t_begin, int do_tsum, int nplanes, int batch, int steps, long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return dfail(ACE_ERR_INVALID, "ace_diag_window: need 0 <= nplanes <= 65535");
-    if (steps < 1 || steps > 65535) return dfail(ACE_ERR_INVALID, "ace_diag_window: need 1 <= steps <= 65535");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_window: need 0 <= nplanes <= 65535");
+    if (steps < 1 || steps > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_window: need 1 <= steps <= 65535");
     if (batch < 1 || hw < 1 || nw < 1 || nrows < 1)
-        return dfail(ACE_ERR_INVALID, "ace_diag_window: need batch >= 1, hw >= 1, nw >= 1, nrows >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_window: need batch >= 1, hw >= 1, nw >= 1, nrows >= 1");
     if (t0 < 0 || t0 + (long)steps > n_time || t_begin < 0)
-        return dfail(ACE_ERR_INVALID, "ace_diag_window: need 0 <= t0, t0 + steps <= n_time, 0 <= t_begin");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_window: need 0 <= t0, t0 + steps <= n_time, 0 <= t_begin");
     if (nplanes == 0) return ACE_OK;
     if (!srcs || !strides || !rows || !wrows || !weights || !partial || !series || (do_tsum && !tsum))
-        return dfail(ACE_ERR_INVALID, "ace_diag_window: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_window: null argument");
     const long nchunk = nchunk_for(hw);
-    if (nchunk > 2147483647L) return dfail(ACE_ERR_INVALID, "ace_diag_window: plane too large");
+    if (nchunk > 2147483647L) return ace::fail(ACE_ERR_INVALID, "ace_diag_window: plane too large");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(diag_window_kernel, dim3((unsigned)nchunk, nplanes), dim3(NT), 0, s, srcs, strides, rows, wrows, weights, nw,
                        partial, tsum, nrows, batch, steps, t_begin, do_tsum, hw, (int)nchunk);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(diag_combine_kernel, dim3(steps, nplanes), dim3(64), 0, s, partial, rows, wrows, nw, series, nrows, n_time, batch,
                        steps, t0, nchunk * WAVES);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
 extern "C" int ace_diag_spectrum(const void* coeffs, const int* rows, double* spec, int nrows, int nnames, long planes, int lmax,
                                  int mmax, void* stream) {
-    if (nnames < 0 || nnames > 65535) return dfail(ACE_ERR_INVALID, "ace_diag_spectrum: need 0 <= nnames <= 65535");
+    if (nnames < 0 || nnames > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_spectrum: need 0 <= nnames <= 65535");
     if (planes < 1 || lmax < 1 || mmax < 1 || nrows < 1)
-        return dfail(ACE_ERR_INVALID, "ace_diag_spectrum: need planes >= 1, lmax >= 1, mmax >= 1, nrows >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_spectrum: need planes >= 1, lmax >= 1, mmax >= 1, nrows >= 1");
     if (nnames == 0) return ACE_OK;
-    if (!coeffs || !rows || !spec) return dfail(ACE_ERR_INVALID, "ace_diag_spectrum: null argument");
+    if (!coeffs || !rows || !spec) return ace::fail(ACE_ERR_INVALID, "ace_diag_spectrum: null argument");
     hipLaunchKernelGGL(diag_spectrum_kernel, dim3(lmax, nnames), dim3(NT), 0, static_cast<hipStream_t>(stream),
                        static_cast<const float2*>(coeffs), rows, spec, nrows, planes, lmax, mmax);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -437,21 +432,21 @@ extern "C" int ace_diag_paired_window(const float* const* gen, const long* gen_s
                                       double* partial, double* tsum, double* zonal, double* series, int nrows, int n_time, int t0,
                                       int t_begin, int do_maps, int zt0, int factor, int nslots, int nplanes, int batch, int steps,
                                       int nlat, int nlon, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return dfail(ACE_ERR_INVALID, "ace_diag_paired_window: need 0 <= nplanes <= 65535");
-    if (steps < 1 || steps > 65535) return dfail(ACE_ERR_INVALID, "ace_diag_paired_window: need 1 <= steps <= 65535");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_paired_window: need 0 <= nplanes <= 65535");
+    if (steps < 1 || steps > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_paired_window: need 1 <= steps <= 65535");
     if (batch < 1 || nw < 1 || nrows < 1)
-        return dfail(ACE_ERR_INVALID, "ace_diag_paired_window: need batch >= 1, nw >= 1, nrows >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_paired_window: need batch >= 1, nw >= 1, nrows >= 1");
     if (!paired_shape_ok(nlat, nlon))
-        return dfail(ACE_ERR_INVALID, "ace_diag_paired_window: need nlat >= 2 and 2 <= nlon <= 2730 (the gradient's stencils; three "
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_paired_window: need nlat >= 2 and 2 <= nlon <= 2730 (the gradient's stencils; three "
                                       "rows of both fields in 64 KiB of LDS)");
     if (t0 < 0 || t0 + (long)steps > n_time || t_begin < 0)
-        return dfail(ACE_ERR_INVALID, "ace_diag_paired_window: need 0 <= t0, t0 + steps <= n_time, 0 <= t_begin");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_paired_window: need 0 <= t0, t0 + steps <= n_time, 0 <= t_begin");
     if (do_maps && (factor < 1 || nslots < 1 || zt0 < 0))
-        return dfail(ACE_ERR_INVALID, "ace_diag_paired_window: need factor >= 1, nslots >= 1, zt0 >= 0 with do_maps");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_paired_window: need factor >= 1, nslots >= 1, zt0 >= 0 with do_maps");
     if (nplanes == 0) return ACE_OK;
     if (!gen || !gen_strides || !target || !target_strides || !rows || !wrows || !weights || !partial || !series ||
         (do_maps && (!tsum || !zonal)))
-        return dfail(ACE_ERR_INVALID, "ace_diag_paired_window: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_paired_window: null argument");
     PairedArgs a{gen, gen_strides, target, target_strides, rows, wrows, weights, nw, partial, tsum, zonal, nrows, batch, steps, t_begin,
                  do_maps, zt0, do_maps ? factor : 1, nslots, nlat, nlon, paired_rows_for(nlat, nlon), (int)paired_nband(nlat, nlon)};
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -461,9 +456,9 @@ extern "C" int ace_diag_paired_window(const float* const* gen, const long* gen_s
         hipLaunchKernelGGL(diag_paired_kernel<PAIRED_K_SMALL>, grid, dim3(NT), lds, s, a);
     else
         hipLaunchKernelGGL(diag_paired_kernel<PAIRED_K_LARGE>, grid, dim3(NT), lds, s, a);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(paired_combine_kernel, dim3(steps, nplanes), dim3(64), 0, s, partial, target, rows, wrows, nw, series, nrows,
                        n_time, batch, steps, t0, (long)a.nband * WAVES);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

@@ -1,5 +1,5 @@
 // What the diagnostics kernels (diag.hip, hist.hip, regress.hip, calendar.hip, ensemble.hip, timeseg.hip, region.hip, video.hip) share: the pixel partition of a plane, the guarded 4-pixel load,
-// the wave reductions and the error report behind ace_diag_last_error.  A new diag kernel starts from here.
+// the wave reductions, and the library's error report (errors.h).  A new diag kernel starts from here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,13 +7,7 @@
 #include <string>
 
 #include "../../include/ace_sfno.h"
-
-int ace_diag_fail_(int code, const std::string& m);      // csrc/diag.hip: sets the string behind ace_diag_last_error, returns code
-#define DIAG_TRY(expr)                                                                                               \
-    do {                                                                                                             \
-        hipError_t e__ = (expr);                                                                                     \
-        if (e__ != hipSuccess) return ace_diag_fail_(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
+#include "errors.h"
 
 // Whether load4 may read 16 bytes at once: a row of HW pixels, or every plane of a field with sample stride sb and step stride st,
 // starts 16-byte aligned.  Macros, not inline functions: the function form changed the generated code of all three files.

@@ -23,13 +23,10 @@
 
 #include "../../include/ace_sfno.h"
 #include "disco_units.h"
+#include "errors.h"
 #include "pixel_act.h"
 
 #pragma clang fp contract(off)
-
-static thread_local std::string g_dcerr;
-static int dcfail(int code, const std::string& m) { g_dcerr = m; return code; }
-extern "C" const char* ace_disco_last_error(void) { return g_dcerr.c_str(); }
 
 namespace {
 
@@ -156,17 +153,17 @@ size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 extern "C" int ace_disco_create(int H, int W, int K, const long* row_off, const int* hi, const int* wi, const float* vals,
                                 const float* w_dev, int in_chans, int out_chans, int groups, int act, int has_embed, void* stream,
                                 void** handle) {
-    if (!handle) return dcfail(ACE_ERR_INVALID, "ace_disco_create: null handle pointer");
+    if (!handle) return ace::fail(ACE_ERR_INVALID, "ace_disco_create: null handle pointer");
     *handle = nullptr;
-    if (!row_off || !hi || !wi || !vals || !w_dev) return dcfail(ACE_ERR_INVALID, "ace_disco_create: null argument");
+    if (!row_off || !hi || !wi || !vals || !w_dev) return ace::fail(ACE_ERR_INVALID, "ace_disco_create: null argument");
     if (!kernel_of(K))
-        return dcfail(ACE_ERR_INVALID, "ace_disco_create: K must be kernel_size^2 with kernel_size in 1 .. 5 (ACE_DISCO_MAX_K = " +
+        return ace::fail(ACE_ERR_INVALID, "ace_disco_create: K must be kernel_size^2 with kernel_size in 1 .. 5 (ACE_DISCO_MAX_K = " +
                                            std::to_string(ACE_DISCO_MAX_K) + "), got " + std::to_string(K));
     if (act != ACE_DISCO_ACT_NONE && act != ACE_DISCO_ACT_RELU && act != ACE_DISCO_ACT_GELU && act != ACE_DISCO_ACT_SILU)
-        return dcfail(ACE_ERR_INVALID, "ace_disco_create: act must be one of ACE_DISCO_ACT_*");
+        return ace::fail(ACE_ERR_INVALID, "ace_disco_create: act must be one of ACE_DISCO_ACT_*");
     ace_disco::Plan plan;
     const std::string why = ace_disco::make_plan(H, W, K, in_chans, out_chans, groups, row_off, hi, wi, plan);
-    if (!why.empty()) return dcfail(ACE_ERR_INVALID, "ace_disco_create: " + why);
+    if (!why.empty()) return ace::fail(ACE_ERR_INVALID, "ace_disco_create: " + why);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int gs = plan.gs, opg = plan.opg, J = plan.J, nto = (opg + RUN - 1) / RUN, nj4 = plan.Jp / 4;
     const long P = row_off[H];
@@ -175,7 +172,7 @@ extern "C" int ace_disco_create(int H, int W, int K, const long* row_off, const 
     std::vector<float> w((size_t)out_chans * gs * K);
     hipError_t e = hipMemcpyAsync(w.data(), w_dev, w.size() * sizeof(float), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return dcfail(ACE_ERR_RUNTIME, std::string("ace_disco_create: reading the weight: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, std::string("ace_disco_create: reading the weight: ") + hipGetErrorString(e));
     const size_t o_rows = 0, o_off = align16(o_rows + (size_t)H * 8 * 4), o_units = align16(o_off + (size_t)P * 4),
                  o_psi = align16(o_units + plan.units.size() * 8 * 4), o_w = align16(o_psi + (size_t)P * KP * 4),
                  total = align16(o_w + (size_t)groups * nto * nj4 * 64 * 4);
@@ -212,7 +209,7 @@ extern "C" int ace_disco_create(int H, int W, int K, const long* row_off, const 
     if (e != hipSuccess) {
         if (h->blob) (void)hipFree(h->blob);
         delete h;
-        return dcfail(ACE_ERR_RUNTIME, std::string("ace_disco_create: uploading the tables: ") + hipGetErrorString(e));
+        return ace::fail(ACE_ERR_RUNTIME, std::string("ace_disco_create: uploading the tables: ") + hipGetErrorString(e));
     }
     const char* d = static_cast<const char*>(h->blob);
     DArgs& a = h->a;
@@ -239,24 +236,24 @@ extern "C" void ace_disco_destroy(void* handle) {
 
 extern "C" int ace_disco_info(void* handle, long* out4) {
     const Disco* h = static_cast<const Disco*>(handle);
-    if (!h || !out4) return dcfail(ACE_ERR_INVALID, "ace_disco_info: null argument");
+    if (!h || !out4) return ace::fail(ACE_ERR_INVALID, "ace_disco_info: null argument");
     out4[0] = h->nunits; out4[1] = h->cost_max; out4[2] = h->cost_total; out4[3] = h->lds_bytes;
     return ACE_OK;
 }
 
 extern "C" int ace_disco_forward(void* handle, const float* x, const float* embed, float* y, int batch, void* stream) {
     const Disco* h = static_cast<const Disco*>(handle);
-    if (!h) return dcfail(ACE_ERR_INVALID, "ace_disco_forward: null handle");
-    if (!x || !y) return dcfail(ACE_ERR_INVALID, "ace_disco_forward: null argument");
-    if (batch < 1) return dcfail(ACE_ERR_INVALID, "ace_disco_forward: need batch >= 1");
+    if (!h) return ace::fail(ACE_ERR_INVALID, "ace_disco_forward: null handle");
+    if (!x || !y) return ace::fail(ACE_ERR_INVALID, "ace_disco_forward: null argument");
+    if (batch < 1) return ace::fail(ACE_ERR_INVALID, "ace_disco_forward: need batch >= 1");
     if (h->a.has_embed && !embed)
-        return dcfail(ACE_ERR_INVALID, "ace_disco_forward: the handle was created with an embedding: embed must not be NULL");
+        return ace::fail(ACE_ERR_INVALID, "ace_disco_forward: the handle was created with an embedding: embed must not be NULL");
     if (h->nunits * batch > 2147483647L)
-        return dcfail(ACE_ERR_INVALID, "ace_disco_forward: batch * units exceeds 2^31 - 1 workgroups");
+        return ace::fail(ACE_ERR_INVALID, "ace_disco_forward: batch * units exceeds 2^31 - 1 workgroups");
     if (!h->a.has_embed) embed = nullptr;
     hipLaunchKernelGGL(kernel_of(h->a.K), dim3((unsigned)(h->nunits * batch)), dim3(NT), (size_t)h->lds_bytes,
                        static_cast<hipStream_t>(stream), h->a, x, embed, y, batch);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dcfail(ACE_ERR_RUNTIME, std::string("ace_disco_forward: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, std::string("ace_disco_forward: ") + hipGetErrorString(e));
     return ACE_OK;
 }

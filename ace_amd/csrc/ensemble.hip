@@ -163,19 +163,19 @@ extern "C" int ace_diag_ensemble_step(const float* const* gen, const long* gen_s
                                       const long* target_strides, const int* rows, double* maps, int* seen, int nrows, int slot,
                                       int nslots, double pair_weight, int t, int nplanes, int n_ic, int n_members, int steps, long hw,
                                       void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 0 <= nplanes <= 65535");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 0 <= nplanes <= 65535");
     if (n_members < 2 || n_members > MAX_MEMBERS)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 2 <= n_members <= " + std::to_string(MAX_MEMBERS) +
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 2 <= n_members <= " + std::to_string(MAX_MEMBERS) +
                                                " (the members of a pixel stay in registers)");
-    if (steps < 1 || t < 0 || t >= steps) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 0 <= t < steps");
+    if (steps < 1 || t < 0 || t >= steps) return ace::fail(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 0 <= t < steps");
     if (nslots < 1 || slot < 0 || slot >= nslots)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 0 <= slot < nslots");
-    if (n_ic < 1) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_ensemble_step: need n_ic >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 0 <= slot < nslots");
+    if (n_ic < 1) return ace::fail(ACE_ERR_INVALID, "ace_diag_ensemble_step: need n_ic >= 1");
     if (hw < 1 || (hw + 2L * NT - 1) / (2L * NT) > 2147483647L || nrows < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 1 <= hw <= 512 * (2^31 - 1), nrows >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_ensemble_step: need 1 <= hw <= 512 * (2^31 - 1), nrows >= 1");
     if (nplanes == 0) return ACE_OK;
     if (!gen || !gen_strides || !target || !target_strides || !rows || !maps || !seen)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_ensemble_step: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_ensemble_step: null argument");
     EnsArgs a;
     a.gen = gen; a.gen_strides = gen_strides; a.target = target; a.target_strides = target_strides; a.rows = rows;
     a.maps = maps + (long)slot * 4 * nrows * hw;
@@ -187,6 +187,6 @@ extern "C" int ace_diag_ensemble_step(const float* const* gen, const long* gen_s
     else if (n_members <= 8) launch<8, 4>(a, nplanes, s);
     else if (n_members <= 16) launch<16, 4>(a, nplanes, s);
     else launch<MAX_MEMBERS, 2>(a, nplanes, s);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

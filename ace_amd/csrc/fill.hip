@@ -259,13 +259,13 @@ extern "C" int ace_diag_fill_planes(const float* const* srcs, const long* stride
                                     const float* blurred, int nmasks, double* scratch, float* dst, int nnames, int batch, int steps,
                                     int nlat, int nlon, void* stream) {
     if (const char* why = fill_refusal(nmasks, nnames, batch, steps, nlat, nlon))
-        return ace_diag_fail_(ACE_ERR_INVALID, std::string("ace_diag_fill_planes: ") + why);
+        return ace::fail(ACE_ERR_INVALID, std::string("ace_diag_fill_planes: ") + why);
     if (nnames == 0) return ACE_OK;
     if (!srcs || !strides || !tab || !dst || (nmasks > 0 && (!layers || !blurred || !scratch)))
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_fill_planes: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_fill_planes: null argument");
     if ((reinterpret_cast<uintptr_t>(dst) & 3u) || (reinterpret_cast<uintptr_t>(scratch) & 7u) ||
         (reinterpret_cast<uintptr_t>(blurred) & 3u))
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_fill_planes: dst and blurred must be 4-byte, scratch 8-byte aligned");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_fill_planes: dst and blurred must be 4-byte, scratch 8-byte aligned");
     FillArgs a;
     a.srcs = srcs; a.strides = strides; a.tab = tab; a.layers = layers; a.blurred = blurred; a.mean = scratch; a.dst = dst;
     const double e1 = std::exp(-0.5), e2 = std::exp(-2.0), norm = 1.0 + 2.0 * e1 + 2.0 * e2;      // sigma 1
@@ -279,9 +279,9 @@ extern "C" int ace_diag_fill_planes(const float* const* srcs, const long* stride
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (nmasks > 0) {
         hipLaunchKernelGGL(fill_mean_kernel, dim3((unsigned)planes), dim3(NT), 0, s, a);
-        DIAG_TRY(hipGetLastError());
+        ACE_HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(fill_tile_kernel, dim3((unsigned)(planes * a.ntiles)), dim3(NT), 0, s, a);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

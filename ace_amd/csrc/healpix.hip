@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/ace_sfno.h"
+#include "errors.h"
 #include "kernels.h"
 #include "strip_common.h"
 #include "weight_prep.h"
@@ -34,15 +35,6 @@
 using namespace ace;
 
 #define ACE_HPX_SLACK 16   // floats the caller keeps behind a padded tensor (read, never used, by the last taps of the last row)
-
-static thread_local std::string g_herr;
-static int hfail(int code, const std::string& m) { g_herr = m; return code; }
-extern "C" const char* ace_hpx_last_error(void) { return g_herr.c_str(); }
-#define HPX_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess) return hfail(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // gather table: for every cell (face f, row y, column x) of the padded mesh [12][H + 2p][H + 2p] two source cells of the
@@ -163,7 +155,7 @@ Padded corner_br(const Face& b, const Face& r, int p) {
 
 extern "C" int ace_hpx_pad_table_host(int nside, int p, int* idx_a_host, int* idx_b_host) {
     if (nside < 1 || nside > 4095 || p < 1 || p > nside || !idx_a_host || !idx_b_host)
-        return hfail(ACE_ERR_INVALID, "ace_hpx_pad_table_host: need 1 <= padding <= nside <= 4095");
+        return fail(ACE_ERR_INVALID, "ace_hpx_pad_table_host: need 1 <= padding <= nside <= 4095");
     std::vector<Face> f;
     for (int k = 0; k < 12; ++k) f.push_back(source_face(k, nside));
     // neighbour tables of healpix_paddings.py:299-367, in the order (t, tl, l, bl, b, br, r, tr)
@@ -447,17 +439,17 @@ extern "C" int ace_hpx_pad(const float* x, long x_img_stride, long x_chan_stride
                            void* stream) {
     const int m = nside + 2 * p;
     if (!x || !y || !idx_a_dev || !idx_b_dev || items < 1 || c < 1 || c0 < 0 || c0 + c > y_chans || nside < 1 || p < 1 || y_pitch < m)
-        return hfail(ACE_ERR_INVALID, "ace_hpx_pad: bad argument");
+        return fail(ACE_ERR_INVALID, "ace_hpx_pad: bad argument");
     const long total = (long)items * 12 * c * m * y_pitch;
     hipLaunchKernelGGL(hpx_pad_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), x, x_img_stride,
                        x_chan_stride, x_pitch, y, y_chans, c0, c, m, y_pitch, idx_a_dev, idx_b_dev, items, amax, ACE_HPX_SLACK);
-    HPX_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
 extern "C" int ace_hpx_absmax(const float* x, long n, unsigned* amax, void* stream) {
-    if (!x || n < 1 || !amax) return hfail(ACE_ERR_INVALID, "ace_hpx_absmax: bad argument");
-    HPX_TRY(launch_absmax(x, n, amax, static_cast<hipStream_t>(stream)));
+    if (!x || n < 1 || !amax) return fail(ACE_ERR_INVALID, "ace_hpx_absmax: bad argument");
+    ACE_HIP_TRY(launch_absmax(x, n, amax, static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
 
@@ -478,13 +470,13 @@ extern "C" void ace_hpx_weight_destroy(ace_hpx_weight* w) {
     delete w;
 }
 extern "C" int ace_hpx_weight_create(const float* w_dev, int rows, int cols, void* stream, ace_hpx_weight** out) {
-    if (!w_dev || rows < 1 || cols < 1 || !out) return hfail(ACE_ERR_INVALID, "ace_hpx_weight_create: bad argument");
+    if (!w_dev || rows < 1 || cols < 1 || !out) return fail(ACE_ERR_INVALID, "ace_hpx_weight_create: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::vector<float> host((size_t)rows * cols);
-    HPX_TRY(hipStreamSynchronize(s));
-    HPX_TRY(hipMemcpy(host.data(), w_dev, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+    ACE_HIP_TRY(hipStreamSynchronize(s));
+    ACE_HIP_TRY(hipMemcpy(host.data(), w_dev, host.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (float v : host)
-        if (!std::isfinite(v)) return hfail(ACE_ERR_INVALID, "ace_hpx_weight_create: non-finite weight");
+        if (!std::isfinite(v)) return fail(ACE_ERR_INVALID, "ace_hpx_weight_create: non-finite weight");
     const WeightNorms nm = weight_norms(host.data(), rows, cols, cols);
     ace_hpx_weight* w = new ace_hpx_weight;
     w->rows = rows; w->cols = cols; w->pitch = (cols + 31) & ~31;
@@ -493,7 +485,7 @@ extern "C" int ace_hpx_weight_create(const float* w_dev, int rows, int cols, voi
     const size_t halves = (size_t)((rows + 15) / 16 * 16) * w->pitch;
     if (hipMalloc(reinterpret_cast<void**>(&w->hi), halves * 2) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&w->lo), halves * 2) != hipSuccess) {
         ace_hpx_weight_destroy(w);
-        return hfail(ACE_ERR_RUNTIME, "ace_hpx_weight_create: out of device memory");
+        return fail(ACE_ERR_RUNTIME, "ace_hpx_weight_create: out of device memory");
     }
     hipError_t er = hipMemsetAsync(w->hi, 0, halves * 2, s);
     if (er == hipSuccess) er = hipMemsetAsync(w->lo, 0, halves * 2, s);
@@ -501,14 +493,14 @@ extern "C" int ace_hpx_weight_create(const float* w_dev, int rows, int cols, voi
     if (er == hipSuccess && cols % 8 == 0) {   // a (tap, padded channel) ordered matrix: also as tiles for the packed engine
         if (hipMalloc(reinterpret_cast<void**>(&w->thi), halves * 2) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&w->tlo), halves * 2) != hipSuccess) {
             ace_hpx_weight_destroy(w);
-            return hfail(ACE_ERR_RUNTIME, "ace_hpx_weight_create: out of device memory");
+            return fail(ACE_ERR_RUNTIME, "ace_hpx_weight_create: out of device memory");
         }
         er = hipMemsetAsync(w->thi, 0, halves * 2, s);
         if (er == hipSuccess) er = hipMemsetAsync(w->tlo, 0, halves * 2, s);
         if (er == hipSuccess) er = launch_split_f16_tiled(w_dev, cols, w->thi, w->tlo, w->pitch, rows, cols, w->ascale, s);
     }
     if (er == hipSuccess) er = hipStreamSynchronize(s);
-    if (er != hipSuccess) { ace_hpx_weight_destroy(w); return hfail(ACE_ERR_RUNTIME, std::string("ace_hpx_weight_create: ") + hipGetErrorString(er)); }
+    if (er != hipSuccess) { ace_hpx_weight_destroy(w); return fail(ACE_ERR_RUNTIME, std::string("ace_hpx_weight_create: ") + hipGetErrorString(er)); }
     *out = w;
     return ACE_OK;
 }
@@ -523,10 +515,10 @@ extern "C" int ace_hpx_conv(const float* x, const float* x2, int cin, int cin2, 
                             int act, float cap, const unsigned* xmax, const unsigned* x2max, unsigned* ymax, void* stream) {
     if (!x || !w || !y || !xmax || imgs < 1 || cin < 1 || cout < 1 || H < 1 || W < 1 || pitch < W + (k - 1) * dil || (pitch & 3) || k < 1 ||
         dil < 1 || cin2 < 0 || (cin2 > 0 && (!x2 || !x2max || k != 1)) || (R && k != 1) || (k > 1 && !row_off))
-        return hfail(ACE_ERR_INVALID, "ace_hpx_conv: bad argument (two sources and a residual only with k = 1; pitch % 4 == 0)");
-    if (!(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU)) return hfail(ACE_ERR_INVALID, "ace_hpx_conv: activation must be none, gelu or relu");
+        return fail(ACE_ERR_INVALID, "ace_hpx_conv: bad argument (two sources and a residual only with k = 1; pitch % 4 == 0)");
+    if (!(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU)) return fail(ACE_ERR_INVALID, "ace_hpx_conv: activation must be none, gelu or relu");
     const int K = (cin + cin2) * k * k;
-    if (w->rows != cout || w->cols != K) return hfail(ACE_ERR_INVALID, "ace_hpx_conv: prepared weight is " + std::to_string(w->rows) + " x " +
+    if (w->rows != cout || w->cols != K) return fail(ACE_ERR_INVALID, "ace_hpx_conv: prepared weight is " + std::to_string(w->rows) + " x " +
                                                       std::to_string(w->cols) + ", expected " + std::to_string(cout) + " x " + std::to_string(K));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int rows_in = H + (k - 1) * dil;
@@ -540,8 +532,8 @@ extern "C" int ace_hpx_conv(const float* x, const float* x2, int cin, int cin2, 
     if (R) { g.R = R; g.ldr = g.ldc; g.sR = g.sC; }
     g.M = cout; g.N = H * pitch; g.K = K; g.nbatch = imgs;
     g.act = act; g.cap = cap;
-    if (!gemm_f16x3_eligible(g)) return hfail(ACE_ERR_INVALID, "ace_hpx_conv: operands must be 16-byte aligned");
-    HPX_TRY(launch_gemm_f16x3(g, w->hi, w->lo, w->ascale, 1.0f, s, xmax, ymax, cin2 > 0 ? x2max : nullptr));
+    if (!gemm_f16x3_eligible(g)) return fail(ACE_ERR_INVALID, "ace_hpx_conv: operands must be 16-byte aligned");
+    ACE_HIP_TRY(launch_gemm_f16x3(g, w->hi, w->lo, w->ascale, 1.0f, s, xmax, ymax, cin2 > 0 ? x2max : nullptr));
     return ACE_OK;
 }
 
@@ -560,11 +552,11 @@ extern "C" int ace_hpx_conv_packed(const void* xhi, const void* xlo, int cpad, l
         H < 1 || W < 1 || pitch < W + (k - 1) * dil || (pitch & 3) || k < 1 || dil < 1 || (k - 1) * dil > ACE_HPX_SLACK || !(bias_max >= 0.f) ||
         x_plane_cells < 0 || y_plane_cells < 0 || (x_plane_cells > 0 && x_plane_cells < (long)(H + (k - 1) * dil) * pitch) ||
         (y_plane_cells > 0 && y_plane_cells < (long)H * pitch))
-        return hfail(ACE_ERR_INVALID, "ace_hpx_conv_packed: bad argument (channels padded to 8, pitch % 4 == 0; planes out: cout % 8 == 0 and a slot)");
-    if (!(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU)) return hfail(ACE_ERR_INVALID, "ace_hpx_conv_packed: activation must be none, gelu or relu");
+        return fail(ACE_ERR_INVALID, "ace_hpx_conv_packed: bad argument (channels padded to 8, pitch % 4 == 0; planes out: cout % 8 == 0 and a slot)");
+    if (!(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU)) return fail(ACE_ERR_INVALID, "ace_hpx_conv_packed: activation must be none, gelu or relu");
     const int K = cpad * k * k;
     if (w->rows != cout || w->cols != K || !w->thi)
-        return hfail(ACE_ERR_INVALID, "ace_hpx_conv_packed: prepared weight is " + std::to_string(w->rows) + " x " + std::to_string(w->cols) +
+        return fail(ACE_ERR_INVALID, "ace_hpx_conv_packed: prepared weight is " + std::to_string(w->rows) + " x " + std::to_string(w->cols) +
                                           ", expected " + std::to_string(cout) + " x " + std::to_string(K) + " (tap, padded channel) columns");
     const int rows_in = H + (k - 1) * dil;
     const long cells = x_plane_cells > 0 ? x_plane_cells : (long)rows_in * pitch;   // entries per channel-group plane of x
@@ -585,7 +577,7 @@ extern "C" int ace_hpx_conv_packed(const void* xhi, const void* xlo, int cpad, l
     // 128 x 128 tiles unless they waste over 20 % more rows than 64 x 256 ones: the launcher's own rule (least padding) picks 64-row
     // tiles for cout = 544 (576 against 640 rows), the 128-row tile is the faster engine (same box, nside 64: 4.47 -> 4.08 ms per forward)
     if (5 * ((cout + 127) / 128 * 128) <= 6 * ((cout + 63) / 64 * 64)) a.tile = 1;
-    HPX_TRY(launch_gemm_f16x3_packed(a, static_cast<hipStream_t>(stream)));
+    ACE_HIP_TRY(launch_gemm_f16x3_packed(a, static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
 
@@ -594,10 +586,10 @@ extern "C" int ace_hpx_conv_packed(const void* xhi, const void* xlo, int cpad, l
 extern "C" int ace_hpx_conv1_packed(const void* xhi, const void* xlo, int cin, const ace_hpx_weight* w, const float* bias, const float* R, float* y,
                                     int imgs, int cout, int H, int W, int pitch, int act, const unsigned* xslot, unsigned* ymax, void* stream) {
     if (!xhi || !xlo || !w || !y || !xslot || imgs < 1 || cin < 8 || (cin & 7) || cout < 1 || H < 1 || W < 1 || pitch < W || (pitch & 3))
-        return hfail(ACE_ERR_INVALID, "ace_hpx_conv1_packed: bad argument (cin % 8 == 0, pitch % 4 == 0)");
-    if (!(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU)) return hfail(ACE_ERR_INVALID, "ace_hpx_conv1_packed: activation must be none, gelu or relu");
+        return fail(ACE_ERR_INVALID, "ace_hpx_conv1_packed: bad argument (cin % 8 == 0, pitch % 4 == 0)");
+    if (!(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU)) return fail(ACE_ERR_INVALID, "ace_hpx_conv1_packed: activation must be none, gelu or relu");
     if (w->rows != cout || w->cols != cin || !w->thi)
-        return hfail(ACE_ERR_INVALID, "ace_hpx_conv1_packed: prepared weight is " + std::to_string(w->rows) + " x " + std::to_string(w->cols) +
+        return fail(ACE_ERR_INVALID, "ace_hpx_conv1_packed: prepared weight is " + std::to_string(w->rows) + " x " + std::to_string(w->cols) +
                                           ", expected " + std::to_string(cout) + " x " + std::to_string(cin));
     const long N = (long)H * pitch;
     Gemm4Args a;
@@ -608,7 +600,7 @@ extern "C" int ace_hpx_conv1_packed(const void* xhi, const void* xlo, int cin, c
     if (R) { a.R = R; a.ldr = N; a.sR = (long)cout * N; }
     a.M = cout; a.N = (int)N; a.K = cin; a.nbatch = imgs;
     a.act = act;
-    HPX_TRY(launch_gemm_f16x3_packed(a, static_cast<hipStream_t>(stream)));
+    ACE_HIP_TRY(launch_gemm_f16x3_packed(a, static_cast<hipStream_t>(stream)));
     return ACE_OK;
 }
 
@@ -619,12 +611,12 @@ extern "C" int ace_hpx_pad_planes(const float* x, long x_img_stride, long x_chan
     const int m = nside + 2 * p;
     if (!x || !hi || !lo || !idx_a_dev || !idx_b_dev || items < 1 || cin < 1 || cin2 < 0 || (cin2 > 0 && (!x2 || !x2max)) || nside < 1 || p < 1 ||
         y_pitch < m || !xmax || !pmax)
-        return hfail(ACE_ERR_INVALID, "ace_hpx_pad_planes: bad argument");
+        return fail(ACE_ERR_INVALID, "ace_hpx_pad_planes: bad argument");
     const long total = (long)items * 12 * ((cin + cin2 + 7) / 8) * m * y_pitch;
     hipLaunchKernelGGL(hpx_pad_planes_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), x, x_img_stride, x_chan_stride,
                        x_pitch, cin2 > 0 ? x2 : x, x2_img_stride, x2_chan_stride, x2_pitch, cin, cin2, static_cast<_Float16*>(hi),
                        static_cast<_Float16*>(lo), m, y_pitch, idx_a_dev, idx_b_dev, items, xmax, cin2 > 0 ? x2max : nullptr, pmax, ACE_HPX_SLACK);
-    HPX_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -632,33 +624,33 @@ extern "C" int ace_hpx_halo_planes(void* hi, void* lo, int cpad, const int* idx_
                                    void* stream) {
     const int m = nside + 2 * p;
     if (!hi || !lo || !idx_a_dev || !idx_b_dev || items < 1 || cpad < 8 || (cpad & 7) || nside < 1 || p < 1 || y_pitch < m)
-        return hfail(ACE_ERR_INVALID, "ace_hpx_halo_planes: bad argument");
+        return fail(ACE_ERR_INVALID, "ace_hpx_halo_planes: bad argument");
     const long total = (long)items * 12 * (cpad / 8) * m * y_pitch;
     hipLaunchKernelGGL(hpx_halo_planes_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<_Float16*>(hi),
                        static_cast<_Float16*>(lo), cpad / 8, nside, p, y_pitch, idx_a_dev, idx_b_dev, items, ACE_HPX_SLACK);
-    HPX_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
 extern "C" int ace_hpx_pool2(const float* x, float* y, long planes, int H, int W, int pitch_in, long plane_stride_in, int pitch_out,
                              long plane_stride_out, int is_max, void* stream) {
-    if (!x || !y || planes < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return hfail(ACE_ERR_INVALID, "ace_hpx_pool2: bad argument");
+    if (!x || !y || planes < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(ACE_ERR_INVALID, "ace_hpx_pool2: bad argument");
     const long total = planes * (H / 2) * (W / 2);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (is_max) hipLaunchKernelGGL(hpx_pool2_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, x, y, planes, H, W, pitch_in, plane_stride_in, pitch_out, plane_stride_out);
     else hipLaunchKernelGGL(hpx_pool2_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, x, y, planes, H, W, pitch_in, plane_stride_in, pitch_out, plane_stride_out);
-    HPX_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
 extern "C" int ace_hpx_upsample2(const float* x, float* y, long planes, int H, int W, int pitch_in, long plane_stride_in, int pitch_out,
                                  long plane_stride_out, int mode, int align_corners, void* stream) {
-    if (!x || !y || planes < 1 || H < 1 || W < 1 || (mode != 0 && mode != 1)) return hfail(ACE_ERR_INVALID, "ace_hpx_upsample2: bad argument");
+    if (!x || !y || planes < 1 || H < 1 || W < 1 || (mode != 0 && mode != 1)) return fail(ACE_ERR_INVALID, "ace_hpx_upsample2: bad argument");
     const long total = planes * (2L * H) * (2L * W);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (mode == 0) hipLaunchKernelGGL(hpx_upsample2_kernel<0>, dim3(grid_for(total)), dim3(256), 0, s, x, y, planes, H, W, pitch_in, plane_stride_in, pitch_out, plane_stride_out, 0);
     else hipLaunchKernelGGL(hpx_upsample2_kernel<1>, dim3(grid_for(total)), dim3(256), 0, s, x, y, planes, H, W, pitch_in, plane_stride_in, pitch_out, plane_stride_out, align_corners);
-    HPX_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -668,19 +660,19 @@ extern "C" int ace_hpx_tconv2(const float* x, const ace_hpx_weight* w, const flo
                               int H, int W, int pitch_in, int pitch_out, long plane_stride_out, int act, float cap, const unsigned* xmax,
                               unsigned* ymax, void* stream) {
     if (!x || !w || !tmp || !y || !xmax || imgs < 1 || cin < 1 || cout < 1 || H < 1 || W < 1 || (pitch_in & 3))
-        return hfail(ACE_ERR_INVALID, "ace_hpx_tconv2: bad argument");
-    if (w->rows != 4 * cout || w->cols != cin) return hfail(ACE_ERR_INVALID, "ace_hpx_tconv2: prepared weight has the wrong shape");
+        return fail(ACE_ERR_INVALID, "ace_hpx_tconv2: bad argument");
+    if (w->rows != 4 * cout || w->cols != cin) return fail(ACE_ERR_INVALID, "ace_hpx_tconv2: prepared weight has the wrong shape");
     hipStream_t s = static_cast<hipStream_t>(stream);
     GemmArgs g;
     g.lda = w->pitch; g.sA = 0; g.a_kpad = w->pitch;
     g.B = x; g.ldb = (long)H * pitch_in; g.sB = (long)cin * H * pitch_in;
     g.C = tmp; g.ldc = (long)H * pitch_in; g.sC = (long)4 * cout * H * pitch_in;
     g.M = 4 * cout; g.N = H * pitch_in; g.K = cin; g.nbatch = imgs;
-    if (!gemm_f16x3_eligible(g)) return hfail(ACE_ERR_INVALID, "ace_hpx_tconv2: operands must be 16-byte aligned");
-    HPX_TRY(launch_gemm_f16x3(g, w->hi, w->lo, w->ascale, 1.0f, s, xmax, nullptr, nullptr));
+    if (!gemm_f16x3_eligible(g)) return fail(ACE_ERR_INVALID, "ace_hpx_tconv2: operands must be 16-byte aligned");
+    ACE_HIP_TRY(launch_gemm_f16x3(g, w->hi, w->lo, w->ascale, 1.0f, s, xmax, nullptr, nullptr));
     const long total = (long)imgs * cout * 4 * H * W;
     hipLaunchKernelGGL(hpx_tconv_scatter_kernel, dim3(grid_for(total)), dim3(256), 0, s, tmp, bias, y, (long)imgs, cout, H, W, pitch_in,
                        pitch_out, plane_stride_out, act, cap, ymax);
-    HPX_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

@@ -237,19 +237,19 @@ extern "C" int ace_diag_hist_window(const float* const* gen, const long* gen_str
                                     const long* target_strides, const int* rows, const unsigned char* const* masks, void* scratch,
                                     double* range, long long* counts, int* dropped, int nrows, int n_bins, int nplanes, int batch,
                                     int steps, long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_hist_window: need 0 <= nplanes <= 65535");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_hist_window: need 0 <= nplanes <= 65535");
     if (n_bins < 2 || n_bins > MAX_BINS || (n_bins & 1))
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_hist_window: need an even n_bins, 2 <= n_bins <= 1024");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_hist_window: need an even n_bins, 2 <= n_bins <= 1024");
     if (batch < 1 || steps < 1 || (long)batch * steps > MAX_PLANES_PER_CALL)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_hist_window: need batch >= 1, steps >= 1, batch * steps <= 2097152 (32-bit "
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_hist_window: need batch >= 1, steps >= 1, batch * steps <= 2097152 (32-bit "
                                                "counters per workgroup)");
     if (hw < 1 || nchunk_for(hw) > 2147483647L || nrows < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_hist_window: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_hist_window: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1");
     if (nplanes == 0) return ACE_OK;
     if (!gen || !gen_strides || !target || !target_strides || !rows || !scratch || !range || !counts || !dropped)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_hist_window: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_hist_window: null argument");
     if (reinterpret_cast<uintptr_t>(scratch) & 15u)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_hist_window: scratch must be 16-byte aligned");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_hist_window: scratch must be 16-byte aligned");
     HistArgs a;
     a.src[0] = gen; a.src[1] = target;
     a.strides[0] = gen_strides; a.strides[1] = target_strides;
@@ -262,10 +262,10 @@ extern "C" int ace_diag_hist_window(const float* const* gen, const long* gen_str
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)a.nchunk, nplanes, 2);
     hipLaunchKernelGGL(hist_range_kernel, grid, dim3(NT), 0, s, a);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(hist_update_kernel, dim3(nplanes, 2), dim3(64), 0, s, a);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(hist_bin_kernel, grid, dim3(NT), (size_t)WAVES * n_bins * sizeof(unsigned int), s, a);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

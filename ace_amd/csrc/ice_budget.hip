@@ -19,6 +19,7 @@
 #include <string>
 
 #include "../../include/ace_sfno.h"
+#include "errors.h"
 
 // every fp64 operation rounds on its own, as the reference's torch ops do (old + dt * (...) must not become an fma)
 #pragma clang fp contract(off)
@@ -175,10 +176,6 @@ std::atomic<long> g_flags{0}, g_apply{0}, g_clears{0};
 
 }  // namespace
 
-static thread_local std::string g_ierr;
-static int ifail(int code, const std::string& m) { g_ierr = m; return code; }
-extern "C" const char* ace_ice_budget_last_error(void) { return g_ierr.c_str(); }
-
 extern "C" long ace_ice_budget_scratch_bytes(int batch, long hw) {
     if (batch < 1 || hw < 1) return 0;
     return ACE_ICE_FLAG_BYTES + (((long)batch * hw + 15) & ~15L);
@@ -192,31 +189,31 @@ extern "C" int ace_ice_budget_launches(long* flags, long* apply, long* clears) {
 }
 
 extern "C" int ace_ice_budget_apply(const ace_ice_fields* f, double timestep, int batch, int H, int W, void* scratch, void* stream) {
-    if (!f) return ifail(ACE_ERR_INVALID, "null fields");
-    if (f->nvars < 0 || f->nvars > ACE_ICE_MAX_VARS) return ifail(ACE_ERR_INVALID, "nvars outside 0 .. " + std::to_string(ACE_ICE_MAX_VARS));
-    if (!(timestep > 0.0) || !std::isfinite(timestep)) return ifail(ACE_ERR_INVALID, "the timestep must be a positive finite number");
-    if (batch < 1 || batch > 65535) return ifail(ACE_ERR_INVALID, "batch outside 1 .. 65535");
-    if (H < 1 || W < 1) return ifail(ACE_ERR_INVALID, "H and W must be at least 1");
+    if (!f) return ace::fail(ACE_ERR_INVALID, "null fields");
+    if (f->nvars < 0 || f->nvars > ACE_ICE_MAX_VARS) return ace::fail(ACE_ERR_INVALID, "nvars outside 0 .. " + std::to_string(ACE_ICE_MAX_VARS));
+    if (!(timestep > 0.0) || !std::isfinite(timestep)) return ace::fail(ACE_ERR_INVALID, "the timestep must be a positive finite number");
+    if (batch < 1 || batch > 65535) return ace::fail(ACE_ERR_INVALID, "batch outside 1 .. 65535");
+    if (H < 1 || W < 1) return ace::fail(ACE_ERR_INVALID, "H and W must be at least 1");
     if (f->nvars == 0) return ACE_OK;
-    if (!scratch) return ifail(ACE_ERR_INVALID, "null scratch");
-    if (reinterpret_cast<uintptr_t>(scratch) % 16) return ifail(ACE_ERR_INVALID, "the scratch must be 16-byte aligned");
+    if (!scratch) return ace::fail(ACE_ERR_INVALID, "null scratch");
+    if (reinterpret_cast<uintptr_t>(scratch) % 16) return ace::fail(ACE_ERR_INVALID, "the scratch must be 16-byte aligned");
     const long HW = (long)H * W;
     bool vec = HW % 4 == 0;
     for (int v = 0; v < f->nvars; ++v) {
         const ace_ice_var& X = f->var[v];
         const ace_phys_plane* planes[5] = {&X.old_mass, &X.source, &X.sink, &X.transport, &X.mass};
         for (const ace_phys_plane* p : planes) {
-            if (!p->p) return ifail(ACE_ERR_INVALID, "variable " + std::to_string(v) + ": a plane is missing");
-            if (batch > 1 && p->stride < HW) return ifail(ACE_ERR_INVALID, "variable " + std::to_string(v) + ": a per-sample stride is below H * W");
-            if (reinterpret_cast<uintptr_t>(p->p) % 4) return ifail(ACE_ERR_INVALID, "variable " + std::to_string(v) + ": a plane is not 4-byte aligned");
+            if (!p->p) return ace::fail(ACE_ERR_INVALID, "variable " + std::to_string(v) + ": a plane is missing");
+            if (batch > 1 && p->stride < HW) return ace::fail(ACE_ERR_INVALID, "variable " + std::to_string(v) + ": a per-sample stride is below H * W");
+            if (reinterpret_cast<uintptr_t>(p->p) % 4) return ace::fail(ACE_ERR_INVALID, "variable " + std::to_string(v) + ": a plane is not 4-byte aligned");
             vec = vec && reinterpret_cast<uintptr_t>(p->p) % 16 == 0 && (batch == 1 || p->stride % 4 == 0);
         }
-        if (v == 0 && X.masked) return ifail(ACE_ERR_INVALID, "variable 0 provides the ice mask and cannot be masked");
+        if (v == 0 && X.masked) return ace::fail(ACE_ERR_INVALID, "variable 0 provides the ice mask and cannot be masked");
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned* flags = static_cast<unsigned*>(scratch);
     unsigned char* ice_zero = static_cast<unsigned char*>(scratch) + ACE_ICE_FLAG_BYTES;
-    if (hipMemsetAsync(flags, 0, ACE_ICE_FLAG_BYTES, s) != hipSuccess) return ifail(ACE_ERR_RUNTIME, "clearing the flags failed");
+    if (hipMemsetAsync(flags, 0, ACE_ICE_FLAG_BYTES, s) != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, "clearing the flags failed");
     ++g_clears;
     const int V = vec ? 4 : 1;
     const long work = (HW + V - 1) / V;
@@ -230,11 +227,11 @@ extern "C" int ace_ice_budget_apply(const ace_ice_fields* f, double timestep, in
         const int write_zero = v == 0 && need_zero;
         if (vec) hipLaunchKernelGGL(ice_flags<4>, grid, block, 0, s, X, timestep, HW, flags + v, ice_zero, nblk);
         else hipLaunchKernelGGL(ice_flags<1>, grid, block, 0, s, X, timestep, HW, flags + v, ice_zero, nblk);
-        if (hipGetLastError() != hipSuccess) return ifail(ACE_ERR_RUNTIME, "ice flags launch failed");
+        if (hipGetLastError() != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, "ice flags launch failed");
         ++g_flags;
         if (vec) hipLaunchKernelGGL(ice_apply<4>, grid, block, 0, s, X, timestep, HW, flags + v, ice_zero, write_zero, nblk);
         else hipLaunchKernelGGL(ice_apply<1>, grid, block, 0, s, X, timestep, HW, flags + v, ice_zero, write_zero, nblk);
-        if (hipGetLastError() != hipSuccess) return ifail(ACE_ERR_RUNTIME, "ice apply launch failed");
+        if (hipGetLastError() != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, "ice apply launch failed");
         ++g_apply;
     }
     return ACE_OK;

@@ -15,21 +15,13 @@
 #include <string>
 
 #include "../../include/ace_sfno.h"
+#include "errors.h"
 #include "kernels.h"
 #include "strip_common.h"
 
 using namespace ace;
 
 #define ACE_LL_SLACK 16   // zero entries behind a padded operand (the last taps of the last row read past the end)
-
-static thread_local std::string g_lerr;
-static int lfail(int code, const std::string& m) { g_lerr = m; return code; }
-extern "C" const char* ace_ll_last_error(void) { return g_lerr.c_str(); }
-#define LL_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess) return lfail(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
 
 namespace {
 
@@ -259,14 +251,14 @@ extern "C" int ace_ll_pad_planes(const float* x, long x_img_stride, long x_chan_
     if (!x || !hi || !lo || !xmax || !pmax || imgs < 1 || c < 1 || H < 1 || W < 1 || p < 0 || x_pitch < W || pitch_p < W + 2 * p ||
         (pitch_p & 3) || (circular && p > W) || !(bscale >= 0.f) || !(boff >= 0.f) || x_chan_stride < (long)H * x_pitch ||
         x_img_stride < (long)c * x_chan_stride)
-        return lfail(ACE_ERR_INVALID, "ace_ll_pad_planes: bad argument (pitch_p >= W + 2p, pitch_p % 4 == 0, a circular halo p <= W)");
+        return fail(ACE_ERR_INVALID, "ace_ll_pad_planes: bad argument (pitch_p >= W + 2p, pitch_p % 4 == 0, a circular halo p <= W)");
     if (!(act == ACT_NONE || act == ACT_GELU) || std::isnan(cap))
-        return lfail(ACE_ERR_INVALID, "ace_ll_pad_planes: activation must be none or (capped) gelu");
+        return fail(ACE_ERR_INVALID, "ace_ll_pad_planes: activation must be none or (capped) gelu");
     const long total = (long)imgs * ((c + 7) / 8) * (H + 2 * p) * pitch_p;
     hipLaunchKernelGGL(ll_pad_planes_kernel, dim3(ll_grid(total)), dim3(256), 0, static_cast<hipStream_t>(stream), x, x_img_stride,
                        x_chan_stride, x_pitch, c, H, W, p, circular, static_cast<_Float16*>(hi), static_cast<_Float16*>(lo), pitch_p, imgs,
                        ss, ss_img_stride, act, cap, xmax, bscale, boff, pmax, ACE_LL_SLACK);
-    LL_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -274,10 +266,10 @@ extern "C" int ace_ll_norm_stats(const float* x, long img_stride, long chan_stri
                                  const float* gamma, const float* beta, float* ss, float* mean_var, unsigned* amax, void* stream) {
     if (!x || !ss || !amax || imgs < 1 || c < 1 || H < 1 || W < 1 || pitch < W || chan_stride < (long)H * pitch ||
         img_stride < (long)c * chan_stride || !(eps >= 0.f) || (long)H * W > (1L << 30))
-        return lfail(ACE_ERR_INVALID, "ace_ll_norm_stats: bad argument");
+        return fail(ACE_ERR_INVALID, "ace_ll_norm_stats: bad argument");
     hipLaunchKernelGGL(ll_norm_stats_kernel, dim3((unsigned)((long)imgs * c)), dim3(256), 0, static_cast<hipStream_t>(stream), x, img_stride,
                        chan_stride, pitch, c, H, W, eps, gamma, beta, ss, mean_var, amax);
-    LL_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -285,11 +277,11 @@ extern "C" int ace_ll_pool2(const float* x, float* y, long planes, int H, int W,
                             long plane_stride_out, unsigned* amax, void* stream) {
     if (!x || !y || !amax || planes < 1 || H < 2 || W < 2 || pitch_in < W || pitch_out < W / 2 || plane_stride_in < (long)H * pitch_in ||
         plane_stride_out < (long)(H / 2) * pitch_out)
-        return lfail(ACE_ERR_INVALID, "ace_ll_pool2: bad argument (H, W >= 2)");
+        return fail(ACE_ERR_INVALID, "ace_ll_pool2: bad argument (H, W >= 2)");
     const long total = planes * (H / 2) * pitch_out;
     hipLaunchKernelGGL(ll_pool2_kernel, dim3(ll_grid(total)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, planes, H, W, pitch_in,
                        plane_stride_in, pitch_out, plane_stride_out, amax);
-    LL_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -299,12 +291,12 @@ extern "C" int ace_ll_upsample2_add(const float* x, long planes, int h, int w, i
     if (!x || !skip || !y || !amax || planes < 1 || h < 1 || w < 1 || H < 2 * h || W < 2 * w || pitch_x < w || pitch_skip < W ||
         pitch_y < W || plane_stride_x < (long)h * pitch_x || plane_stride_skip < (long)H * pitch_skip || plane_stride_y < (long)H * pitch_y ||
         (circular && W - 2 * w > 2 * w))
-        return lfail(ACE_ERR_INVALID, "ace_ll_upsample2_add: bad argument (skip at least 2h x 2w, a circular pad at most one wrap)");
+        return fail(ACE_ERR_INVALID, "ace_ll_upsample2_add: bad argument (skip at least 2h x 2w, a circular pad at most one wrap)");
     const int pad_top = (H - 2 * h) / 2, pad_left = (W - 2 * w) / 2;
     const long total = planes * H * pitch_y;
     hipLaunchKernelGGL(ll_upsample2_add_kernel, dim3(ll_grid(total)), dim3(256), 0, static_cast<hipStream_t>(stream), x, planes, h, w, pitch_x,
                        plane_stride_x, skip, pitch_skip, plane_stride_skip, y, H, W, pitch_y, plane_stride_y, pad_top, pad_left, circular,
                        periodic, amax);
-    LL_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

@@ -16,15 +16,7 @@
 #include <string>
 
 #include "../../include/ace_sfno.h"
-
-static thread_local std::string g_merr;
-static int mfail(int code, const std::string& m) { g_merr = m; return code; }
-extern "C" const char* ace_mask_last_error(void) { return g_merr.c_str(); }
-#define MASK_TRY(expr)                                                                                      \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess) return mfail(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
+#include "errors.h"
 
 namespace {
 
@@ -135,13 +127,13 @@ bool bad_shape(int nplanes, int batch, long hw) { return nplanes < 0 || nplanes 
 extern "C" int ace_mask_planes(const float* const* srcs, const long* src_strides, float* const* dsts, const long* dst_strides,
                                const int* mask_idx, const unsigned char* hits, int nmask, const float* fill, int nplanes, int batch,
                                long hw, void* stream) {
-    if (bad_shape(nplanes, batch, hw) || nmask < 0) return mfail(ACE_ERR_INVALID, "ace_mask_planes: bad shape");
+    if (bad_shape(nplanes, batch, hw) || nmask < 0) return ace::fail(ACE_ERR_INVALID, "ace_mask_planes: bad shape");
     if (nplanes == 0) return ACE_OK;
     if (!srcs || !src_strides || !dsts || !dst_strides || !mask_idx || !fill || (nmask > 0 && !hits))
-        return mfail(ACE_ERR_INVALID, "ace_mask_planes: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_mask_planes: null argument");
     hipLaunchKernelGGL(mask_planes_kernel, grid_for(hw, nplanes, batch), dim3(NT), 0, static_cast<hipStream_t>(stream), srcs,
                        src_strides, dsts, dst_strides, mask_idx, hits, nmask, fill, hw);
-    MASK_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -150,13 +142,13 @@ extern "C" int ace_mask_pack_normalize(const float* const* srcs, const long* src
                                        const long* stage_strides, const float* mean, const float* std_, float* dst, int npack,
                                        int nplanes, int batch, long hw, void* stream) {
     if (bad_shape(nplanes, batch, hw) || nmask < 0 || npack < 0 || npack > nplanes)
-        return mfail(ACE_ERR_INVALID, "ace_mask_pack_normalize: bad shape (0 <= npack <= nplanes)");
+        return ace::fail(ACE_ERR_INVALID, "ace_mask_pack_normalize: bad shape (0 <= npack <= nplanes)");
     if (nplanes == 0) return ACE_OK;
     if (!srcs || !src_strides || !mask_idx || !fill || (nmask > 0 && !hits) || (stage && !stage_strides) ||
         (npack > 0 && (!mean || !std_ || !dst)))
-        return mfail(ACE_ERR_INVALID, "ace_mask_pack_normalize: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_mask_pack_normalize: null argument");
     hipLaunchKernelGGL(mask_pack_normalize_kernel, grid_for(hw, nplanes, batch), dim3(NT), 0, static_cast<hipStream_t>(stream),
                        srcs, src_strides, mask_idx, hits, nmask, fill, stage, stage_strides, mean, std_, dst, npack, hw);
-    MASK_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

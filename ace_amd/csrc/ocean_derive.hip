@@ -23,6 +23,7 @@
 #include <string>
 
 #include "../../include/ace_sfno.h"
+#include "errors.h"
 
 // the reference's torch ops round after every multiply and add: no fused multiply-adds in the fp32 arithmetic
 #pragma clang fp contract(off)
@@ -259,52 +260,46 @@ __global__ __launch_bounds__(NT) void ocean_derive_kernel(ace_ocean_derive_desc 
     }
 }
 
-thread_local std::string g_err;
-int fail(const std::string& m) {
-    g_err = "ace_ocean_derive_window: " + m;
-    return ACE_ERR_INVALID;
-}
+int refuse(const std::string& m) { return ace::fail(ACE_ERR_INVALID, "ace_ocean_derive_window: " + m); }
 
 bool aligned4(const void* p, long s0 = 0, long s1 = 0) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && ((s0 | s1) & 3) == 0; }
 bool field_aligned(const ace_ocean_derive_field& f) { return !f.base || aligned4(f.base, f.bstride, f.tstride); }
 
 }  // namespace
 
-extern "C" const char* ace_ocean_derive_last_error(void) { return g_err.c_str(); }
-
 extern "C" int ace_ocean_derive_window(const ace_ocean_derive_desc* desc, void* stream) {
-    if (!desc) return fail("null argument");
+    if (!desc) return refuse("null argument");
     const ace_ocean_derive_desc& d = *desc;
     const unsigned want = d.want;
-    if (want >> ACE_OCEAN_DERIVE_NOUT) return fail("unknown bits in want");
-    if (d.batch < 1 || d.batch > 65535 || d.steps < 1 || d.hw < 1) return fail("need 1 <= batch <= 65535 (a grid dimension), steps >= 1, hw >= 1");
+    if (want >> ACE_OCEAN_DERIVE_NOUT) return refuse("unknown bits in want");
+    if (d.batch < 1 || d.batch > 65535 || d.steps < 1 || d.hw < 1) return refuse("need 1 <= batch <= 65535 (a grid dimension), steps >= 1, hw >= 1");
     const long nchunk = (d.hw + CHUNK - 1) / CHUNK;
-    if (nchunk > 2147483647L) return fail("need hw <= 1024 * (2^31 - 1)");
-    if (d.t_chunk < 0) return fail("need t_chunk >= 0");
-    if (d.nlev < 0 || d.nlev > ACE_OCEAN_MAX_LEVELS) return fail("nlev outside 0 .. " + std::to_string(ACE_OCEAN_MAX_LEVELS));
+    if (nchunk > 2147483647L) return refuse("need hw <= 1024 * (2^31 - 1)");
+    if (d.t_chunk < 0) return refuse("need t_chunk >= 0");
+    if (d.nlev < 0 || d.nlev > ACE_OCEAN_MAX_LEVELS) return refuse("nlev outside 0 .. " + std::to_string(ACE_OCEAN_MAX_LEVELS));
     if (want == 0) return ACE_OK;
     for (int i = 0; i < ACE_OCEAN_DERIVE_NOUT; ++i)
-        if (((want >> i) & 1u) && !d.out[i]) return fail("a wanted output has no destination");
+        if (((want >> i) & 1u) && !d.out[i]) return refuse("a wanted output has no destination");
     const bool need_S = (want & (W_OHC | W_TEND | W_ADV)) != 0, need_net = (want & (W_NET | W_ADV)) != 0;
     if (need_S) {
-        if (d.nlev < 1) return fail("the heat content needs 1 .. " + std::to_string(ACE_OCEAN_MAX_LEVELS) + " levels");
-        if (!d.dz || !d.mask0) return fail("the heat content needs dz and mask0");
+        if (d.nlev < 1) return refuse("the heat content needs 1 .. " + std::to_string(ACE_OCEAN_MAX_LEVELS) + " levels");
+        if (!d.dz || !d.mask0) return refuse("the heat content needs dz and mask0");
         for (int k = 0; k < d.nlev; ++k)
-            if (!d.thetao[k].f.base) return fail("the heat content needs every thetao level: level " + std::to_string(k) + " is absent");
-        if ((want & (W_TEND | W_ADV)) && !(d.dt_seconds > 0)) return fail("the tendency needs dt_seconds > 0");
+            if (!d.thetao[k].f.base) return refuse("the heat content needs every thetao level: level " + std::to_string(k) + " is absent");
+        if ((want & (W_TEND | W_ADV)) && !(d.dt_seconds > 0)) return refuse("the tendency needs dt_seconds > 0");
     }
     const bool has_ssf = d.sea_surface_fraction.base || d.land_fraction.base;
-    if ((want & W_HFDS) && d.hfds.base) return fail("hfds is wanted but its plane exists: there is nothing to derive");
-    if ((want & W_SIF) && d.sea_ice_fraction.base) return fail("sea_ice_fraction is wanted but its plane exists: there is nothing to derive");
-    if ((want & W_HFDS) && !(d.hfds_total_area.base && has_ssf)) return fail("hfds needs hfds_total_area and the sea-surface or land fraction");
+    if ((want & W_HFDS) && d.hfds.base) return refuse("hfds is wanted but its plane exists: there is nothing to derive");
+    if ((want & W_SIF) && d.sea_ice_fraction.base) return refuse("sea_ice_fraction is wanted but its plane exists: there is nothing to derive");
+    if ((want & W_HFDS) && !(d.hfds_total_area.base && has_ssf)) return refuse("hfds needs hfds_total_area and the sea-surface or land fraction");
     if (need_net && !((d.hfds.base || d.hfds_total_area.base) && has_ssf))
-        return fail("the net flux needs hfds or hfds_total_area, and the sea-surface or land fraction");
+        return refuse("the net flux needs hfds or hfds_total_area, and the sea-surface or land fraction");
     if ((want & W_SIF) && !(d.ocean_sea_ice_fraction.base && d.land_fraction.base))
-        return fail("sea_ice_fraction needs ocean_sea_ice_fraction and land_fraction");
+        return refuse("sea_ice_fraction needs ocean_sea_ice_fraction and land_fraction");
     if (want & W_HI) {
-        if (!d.sea_ice_volume.base || !d.area_m2 || !has_ssf) return fail("HI needs sea_ice_volume, area_m2 and the sea-surface or land fraction");
+        if (!d.sea_ice_volume.base || !d.area_m2 || !has_ssf) return refuse("HI needs sea_ice_volume, area_m2 and the sea-surface or land fraction");
         if (!d.ocean_sea_ice_fraction.base && !(d.sea_ice_fraction.base && d.land_fraction.base))
-            return fail("HI needs ocean_sea_ice_fraction, or sea_ice_fraction and land_fraction");
+            return refuse("HI needs ocean_sea_ice_fraction, or sea_ice_fraction and land_fraction");
     }
     int t_chunk = d.t_chunk;
     if (t_chunk == 0) {
@@ -316,7 +311,7 @@ extern "C" int ace_ocean_derive_window(const ace_ocean_derive_desc* desc, void* 
     }
     if (t_chunk > d.steps) t_chunk = d.steps;
     const long ntc = ((long)d.steps + t_chunk - 1) / t_chunk;
-    if (ntc > 65535) return fail("need ceil(steps / t_chunk) <= 65535 (a grid dimension)");
+    if (ntc > 65535) return refuse("need ceil(steps / t_chunk) <= 65535 (a grid dimension)");
 
     // one decision for the launch: every plane it may touch starts 16-byte aligned at every (sample, step)
     bool vec = (d.hw & 3) == 0 && field_aligned(d.hfds) && field_aligned(d.hfds_total_area) && field_aligned(d.hfgeou) &&
@@ -335,9 +330,6 @@ extern "C" int ace_ocean_derive_window(const ace_ocean_derive_desc* desc, void* 
     else
         hipLaunchKernelGGL(ocean_derive_kernel<false>, grid, dim3(NT), 0, s, d, t_chunk);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("ace_ocean_derive_window: launch failed: ") + hipGetErrorString(e);
-        return ACE_ERR_RUNTIME;
-    }
+    if (e != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, std::string("ace_ocean_derive_window: launch failed: ") + hipGetErrorString(e));
     return ACE_OK;
 }

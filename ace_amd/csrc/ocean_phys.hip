@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/ace_sfno.h"
+#include "errors.h"
 
 // the reference's torch ops round after every multiply and add: no fused multiply-adds in the per-column arithmetic
 #pragma clang fp contract(off)
@@ -191,19 +192,15 @@ struct ace_ocean_phys {
     long o1 = 0, o2 = 0;       // launches made (route query)
 };
 
-static thread_local std::string g_oerr;
-static int ofail(int code, const std::string& m) { g_oerr = m; return code; }
-extern "C" const char* ace_ocean_phys_last_error(void) { return g_oerr.c_str(); }
-
 extern "C" int ace_ocean_phys_create(const ace_ocean_config* c, const float* wlat_host, const float* dz_host, const float* mask_ohc_host,
                                      const float* mask0_host, ace_ocean_phys** out) {
-    if (!c || !out) return ofail(ACE_ERR_INVALID, "null argument");
-    if (c->nlat < 1 || c->nlon < 1 || c->max_batch < 1) return ofail(ACE_ERR_INVALID, "bad grid / batch");
-    if (c->hfds < 0 || c->hfds > 2 || c->ohc < 0 || c->ohc > 1) return ofail(ACE_ERR_INVALID, "unknown correction variant");
+    if (!c || !out) return ace::fail(ACE_ERR_INVALID, "null argument");
+    if (c->nlat < 1 || c->nlon < 1 || c->max_batch < 1) return ace::fail(ACE_ERR_INVALID, "bad grid / batch");
+    if (c->hfds < 0 || c->hfds > 2 || c->ohc < 0 || c->ohc > 1) return ace::fail(ACE_ERR_INVALID, "unknown correction variant");
     if (c->ohc) {
-        if (!wlat_host || !dz_host || !mask0_host) return ofail(ACE_ERR_INVALID, "the heat-content correction needs area weights, dz and the top-level mask");
-        if (c->nlev < 1 || c->nlev > MAXL) return ofail(ACE_ERR_INVALID, "the heat-content correction supports 1 .. " + std::to_string(MAXL) + " levels");
-        if (!(c->timestep_seconds > 0)) return ofail(ACE_ERR_INVALID, "timestep required");
+        if (!wlat_host || !dz_host || !mask0_host) return ace::fail(ACE_ERR_INVALID, "the heat-content correction needs area weights, dz and the top-level mask");
+        if (c->nlev < 1 || c->nlev > MAXL) return ace::fail(ACE_ERR_INVALID, "the heat-content correction supports 1 .. " + std::to_string(MAXL) + " levels");
+        if (!(c->timestep_seconds > 0)) return ace::fail(ACE_ERR_INVALID, "timestep required");
     }
     auto h = std::make_unique<ace_ocean_phys>();
     OceanParams& P = h->P;
@@ -216,7 +213,7 @@ extern "C" int ace_ocean_phys_create(const ace_ocean_config* c, const float* wla
     const size_t b_w = up((size_t)c->nlat * 4), b_m = c->ohc ? up(HW * 4) : 0, b_dz = up(HW * 4 * P.L);
     const size_t b_part = c->ohc ? (size_t)c->max_batch * NQ * NBLK_MAX * 8 : 0;
     const size_t total = b_w + 2 * b_m + b_dz + b_part + 256;
-    if (hipMalloc(&h->dev, total) != hipSuccess) return ofail(ACE_ERR_RUNTIME, "hipMalloc failed");
+    if (hipMalloc(&h->dev, total) != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, "hipMalloc failed");
     char* d = static_cast<char*>(h->dev);
     bool ok = hipMemset(d, 0, total) == hipSuccess;
     if (ok && c->ohc) {
@@ -227,7 +224,7 @@ extern "C" int ace_ocean_phys_create(const ace_ocean_config* c, const float* wla
     }
     if (!ok) {
         (void)hipFree(h->dev);
-        return ofail(ACE_ERR_RUNTIME, "device initialisation failed");
+        return ace::fail(ACE_ERR_RUNTIME, "device initialisation failed");
     }
     P.wlat = reinterpret_cast<const float*>(d);
     P.mask_ohc = (c->ohc && mask_ohc_host) ? reinterpret_cast<const float*>(d + b_w) : nullptr;
@@ -245,34 +242,34 @@ extern "C" void ace_ocean_phys_destroy(ace_ocean_phys* h) {
 }
 
 extern "C" int ace_ocean_phys_launches(const ace_ocean_phys* h, long* o1, long* o2) {
-    if (!h || !o1 || !o2) return ofail(ACE_ERR_INVALID, "null argument");
+    if (!h || !o1 || !o2) return ace::fail(ACE_ERR_INVALID, "null argument");
     *o1 = h->o1;
     *o2 = h->o2;
     return ACE_OK;
 }
 
 extern "C" int ace_ocean_phys_apply(ace_ocean_phys* h, const ace_ocean_fields* f, int batch, void* stream) {
-    if (!h || !f) return ofail(ACE_ERR_INVALID, "null argument");
+    if (!h || !f) return ace::fail(ACE_ERR_INVALID, "null argument");
     const OceanParams& P = h->P;
-    if (batch < 1 || batch > P.max_batch) return ofail(ACE_ERR_INVALID, "batch outside [1, max_batch]");
+    if (batch < 1 || batch > P.max_batch) return ace::fail(ACE_ERR_INVALID, "batch outside [1, max_batch]");
     if (f->npositive < 0 || f->npositive > ACE_OCEAN_MAX_POSITIVE || f->nzero < 0 || f->nzero > ACE_OCEAN_MAX_ZERO)
-        return ofail(ACE_ERR_INVALID, "too many force-positive / zero-where-ice-free fields");
+        return ace::fail(ACE_ERR_INVALID, "too many force-positive / zero-where-ice-free fields");
     auto has = [](const ace_phys_plane& p) { return p.p != nullptr; };
-    for (int i = 0; i < f->npositive; ++i) if (!has(f->positive[i])) return ofail(ACE_ERR_INVALID, "a force-positive field is missing");
+    for (int i = 0; i < f->npositive; ++i) if (!has(f->positive[i])) return ace::fail(ACE_ERR_INVALID, "a force-positive field is missing");
     if (P.sea_ice) {
-        if (!has(f->sif) || (P.remove_negative && !has(f->reb_land))) return ofail(ACE_ERR_INVALID, "sea-ice fraction correction: a required field is missing");
-        for (int i = 0; i < f->nzero; ++i) if (!has(f->zero[i])) return ofail(ACE_ERR_INVALID, "a zero-where-ice-free field is missing");
+        if (!has(f->sif) || (P.remove_negative && !has(f->reb_land))) return ace::fail(ACE_ERR_INVALID, "sea-ice fraction correction: a required field is missing");
+        for (int i = 0; i < f->nzero; ++i) if (!has(f->zero[i])) return ace::fail(ACE_ERR_INVALID, "a zero-where-ice-free field is missing");
     }
     if (P.hfds && !(has(f->hfds) && has(f->in_land) && has(f->in_sif) && has(f->in_sst) && has(f->dlw) && has(f->ulw) && has(f->dsw) &&
                     has(f->usw) && has(f->lhf) && has(f->shf) && has(f->precip) && (!f->hfds_total_area || has(f->f_ssf))))
-        return ofail(ACE_ERR_INVALID, "surface energy flux correction: a required field is missing");
+        return ace::fail(ACE_ERR_INVALID, "surface energy flux correction: a required field is missing");
     if (P.ohc) {
         for (int k = 0; k < P.L; ++k)
-            if (!has(f->thetao[k]) || !has(f->thetao_in[k])) return ofail(ACE_ERR_INVALID, "heat-content correction: a thetao level is missing");
-        if (!has(f->f_ssf) || f->flux_source < 0 || f->flux_source > 3) return ofail(ACE_ERR_INVALID, "heat-content correction: bad flux source");
-        if (f->flux_source <= 1 && !has(f->hfds)) return ofail(ACE_ERR_INVALID, "heat-content correction: the output heat flux is missing");
-        if (f->flux_source >= 2 && !has(f->in_flux)) return ofail(ACE_ERR_INVALID, "heat-content correction: the input heat flux is missing");
-        if (f->flux_source == 3 && !has(f->in_ssf)) return ofail(ACE_ERR_INVALID, "heat-content correction: the input sea-surface fraction is missing");
+            if (!has(f->thetao[k]) || !has(f->thetao_in[k])) return ace::fail(ACE_ERR_INVALID, "heat-content correction: a thetao level is missing");
+        if (!has(f->f_ssf) || f->flux_source < 0 || f->flux_source > 3) return ace::fail(ACE_ERR_INVALID, "heat-content correction: bad flux source");
+        if (f->flux_source <= 1 && !has(f->hfds)) return ace::fail(ACE_ERR_INVALID, "heat-content correction: the output heat flux is missing");
+        if (f->flux_source >= 2 && !has(f->in_flux)) return ace::fail(ACE_ERR_INVALID, "heat-content correction: the input heat flux is missing");
+        if (f->flux_source == 3 && !has(f->in_ssf)) return ace::fail(ACE_ERR_INVALID, "heat-content correction: the input sea-surface fraction is missing");
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long HW = (long)P.H * P.W;
@@ -282,12 +279,12 @@ extern "C" int ace_ocean_phys_apply(ace_ocean_phys* h, const ace_ocean_fields* f
     const bool o1 = f->npositive > 0 || P.sea_ice || P.hfds || P.ohc;
     if (o1) {
         hipLaunchKernelGGL(ocean_o1, grid, block, 0, s, P, *f, nblk);
-        if (hipGetLastError() != hipSuccess) return ofail(ACE_ERR_RUNTIME, "ocean O1 launch failed");
+        if (hipGetLastError() != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, "ocean O1 launch failed");
         ++h->o1;
     }
     if (P.ohc) {
         hipLaunchKernelGGL(ocean_o2, grid, block, 0, s, P, *f, nblk);
-        if (hipGetLastError() != hipSuccess) return ofail(ACE_ERR_RUNTIME, "ocean O2 launch failed");
+        if (hipGetLastError() != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, "ocean O2 launch failed");
         ++h->o2;
     }
     return ACE_OK;

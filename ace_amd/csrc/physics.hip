@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/ace_sfno.h"
+#include "errors.h"
 
 // the reference's torch ops round after every multiply and add: no fused multiply-adds in the per-column arithmetic
 #pragma clang fp contract(off)
@@ -314,22 +315,18 @@ struct ace_physics {
     std::string err;
 };
 
-static thread_local std::string g_perr;
-static int pfail(int code, const std::string& m) { g_perr = m; return code; }
-extern "C" const char* ace_physics_last_error(void) { return g_perr.c_str(); }
-
 extern "C" int ace_physics_create(const ace_phys_config* c, const float* area_weights_lat_host, const float* ak_host,
                                   const float* bk_host, ace_physics** out) {
-    if (!c || !out) return pfail(ACE_ERR_INVALID, "null argument");
-    if (c->nlat < 1 || c->nlon < 1 || c->max_batch < 1) return pfail(ACE_ERR_INVALID, "bad grid / batch");
+    if (!c || !out) return ace::fail(ACE_ERR_INVALID, "null argument");
+    if (c->nlat < 1 || c->nlon < 1 || c->max_batch < 1) return ace::fail(ACE_ERR_INVALID, "bad grid / batch");
     const bool geom = c->conserve_dry_air || c->zero_global_mean_moisture_advection || c->moisture_budget || c->energy_budget;
     const bool vert = c->conserve_dry_air || c->moisture_budget || c->energy_budget;
-    if (geom && !area_weights_lat_host) return pfail(ACE_ERR_INVALID, "area weights are required for the conservation corrections");
+    if (geom && !area_weights_lat_host) return ace::fail(ACE_ERR_INVALID, "area weights are required for the conservation corrections");
     if (vert && (!ak_host || !bk_host || c->nlev < 1 || c->nlev > MAXL))
-        return pfail(ACE_ERR_INVALID, "the conservation corrections need ak / bk with 1 <= nlev <= " + std::to_string(MAXL));
+        return ace::fail(ACE_ERR_INVALID, "the conservation corrections need ak / bk with 1 <= nlev <= " + std::to_string(MAXL));
     if (c->moisture_budget < 0 || c->moisture_budget > 4 || c->energy_budget < 0 || c->energy_budget > 1 || c->ocean < 0 || c->ocean > 2)
-        return pfail(ACE_ERR_INVALID, "unknown correction variant");
-    if ((c->moisture_budget || c->energy_budget) && !(c->timestep_seconds > 0)) return pfail(ACE_ERR_INVALID, "timestep required");
+        return ace::fail(ACE_ERR_INVALID, "unknown correction variant");
+    if ((c->moisture_budget || c->energy_budget) && !(c->timestep_seconds > 0)) return ace::fail(ACE_ERR_INVALID, "timestep required");
     auto h = std::make_unique<ace_physics>();
     PhysParams& P = h->P;
     std::memset(&P, 0, sizeof(P));
@@ -348,11 +345,11 @@ extern "C" int ace_physics_create(const ace_phys_config* c, const float* area_we
     const size_t b_w = ((size_t)c->nlat * 4 + 255) & ~(size_t)255;
     const size_t b_part = (size_t)3 * c->max_batch * NQ * NBLK_MAX * 8;
     const size_t b_ref = ((size_t)c->max_batch * 8 + 255) & ~(size_t)255;
-    if (hipMalloc(&h->dev, b_w + b_part + b_ref + 256) != hipSuccess) return pfail(ACE_ERR_RUNTIME, "hipMalloc failed");
+    if (hipMalloc(&h->dev, b_w + b_part + b_ref + 256) != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, "hipMalloc failed");
     char* d = static_cast<char*>(h->dev);
     if (hipMemset(d, 0, b_w + b_part + b_ref + 256) != hipSuccess || hipMemcpy(d, wl.data(), wl.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(h->dev);
-        return pfail(ACE_ERR_RUNTIME, "device initialisation failed");
+        return ace::fail(ACE_ERR_RUNTIME, "device initialisation failed");
     }
     P.wlat = reinterpret_cast<const float*>(d);
     P.part = reinterpret_cast<double*>(d + b_w);
@@ -368,50 +365,50 @@ extern "C" void ace_physics_destroy(ace_physics* h) {
 }
 // new initial condition: the next step re-seeds the dry-air reference (stream-ordered)
 extern "C" int ace_physics_reset(ace_physics* h, void* stream) {
-    if (!h) return pfail(ACE_ERR_INVALID, "null argument");
-    if (hipMemsetAsync(h->P.have_ref, 0, sizeof(int), static_cast<hipStream_t>(stream)) != hipSuccess) return pfail(ACE_ERR_RUNTIME, "memset failed");
+    if (!h) return ace::fail(ACE_ERR_INVALID, "null argument");
+    if (hipMemsetAsync(h->P.have_ref, 0, sizeof(int), static_cast<hipStream_t>(stream)) != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, "memset failed");
     return ACE_OK;
 }
 // carried CorrectorState (fme/core/corrector/state.py): ref_dev = (batch) fp64 on the device
 extern "C" int ace_physics_set_reference(ace_physics* h, const double* ref_dev, int batch, void* stream) {
-    if (!h || !ref_dev || batch < 1 || batch > h->P.max_batch) return pfail(ACE_ERR_INVALID, "bad argument");
+    if (!h || !ref_dev || batch < 1 || batch > h->P.max_batch) return ace::fail(ACE_ERR_INVALID, "bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int one = 1;
     if (hipMemcpyAsync(h->P.ref_mass, ref_dev, sizeof(double) * batch, hipMemcpyDeviceToDevice, s) != hipSuccess ||
         hipMemcpyAsync(h->P.have_ref, &one, sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return pfail(ACE_ERR_RUNTIME, "copy failed");
+        return ace::fail(ACE_ERR_RUNTIME, "copy failed");
     return ACE_OK;
 }
 extern "C" int ace_physics_get_reference(ace_physics* h, double* ref_dev, int* have_host, int batch, void* stream) {
-    if (!h || !ref_dev || batch < 1 || batch > h->P.max_batch) return pfail(ACE_ERR_INVALID, "bad argument");
+    if (!h || !ref_dev || batch < 1 || batch > h->P.max_batch) return ace::fail(ACE_ERR_INVALID, "bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     int have = 0;
     if (hipMemcpyAsync(ref_dev, h->P.ref_mass, sizeof(double) * batch, hipMemcpyDeviceToDevice, s) != hipSuccess ||
         hipMemcpyAsync(&have, h->P.have_ref, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return pfail(ACE_ERR_RUNTIME, "copy failed");
+        return ace::fail(ACE_ERR_RUNTIME, "copy failed");
     if (have_host) *have_host = have;
     return ACE_OK;
 }
 
 extern "C" int ace_physics_apply(ace_physics* h, const ace_phys_fields* f, int batch, void* stream) {
-    if (!h || !f) return pfail(ACE_ERR_INVALID, "null argument");
+    if (!h || !f) return ace::fail(ACE_ERR_INVALID, "null argument");
     const PhysParams& P = h->P;
-    if (batch < 1 || batch > P.max_batch) return pfail(ACE_ERR_INVALID, "batch outside [1, max_batch]");
+    if (batch < 1 || batch > P.max_batch) return ace::fail(ACE_ERR_INVALID, "batch outside [1, max_batch]");
     if (f->npositive < 0 || f->npositive > ACE_PHYS_MAX_POSITIVE || f->nprescribed < 0 || f->nprescribed > ACE_PHYS_MAX_PRESCRIBED)
-        return pfail(ACE_ERR_INVALID, "too many force-positive / prescribed fields");
+        return ace::fail(ACE_ERR_INVALID, "too many force-positive / prescribed fields");
     auto need = [&](const ace_phys_plane& p) { return p.p != nullptr; };
     auto levels = [&](const ace_phys_plane* a) { for (int k = 0; k < P.L; ++k) if (!a[k].p) return false; return true; };
     if (P.conserve_dry_air && !(need(f->ps) && need(f->ps_in) && levels(f->wat) && levels(f->wat_in)))
-        return pfail(ACE_ERR_INVALID, "conserve_dry_air needs surface pressure and specific_total_water of output and input");
-    if (P.zero_adv && !need(f->adv)) return pfail(ACE_ERR_INVALID, "tendency_of_total_water_path_due_to_advection is missing");
+        return ace::fail(ACE_ERR_INVALID, "conserve_dry_air needs surface pressure and specific_total_water of output and input");
+    if (P.zero_adv && !need(f->adv)) return ace::fail(ACE_ERR_INVALID, "tendency_of_total_water_path_due_to_advection is missing");
     if (P.moisture && !(need(f->ps) && need(f->ps_in) && levels(f->wat) && levels(f->wat_in) && need(f->lhf) && need(f->precip) &&
                         (P.moisture < 3 || need(f->adv))))
-        return pfail(ACE_ERR_INVALID, "moisture budget correction: a required field is missing");
+        return ace::fail(ACE_ERR_INVALID, "moisture budget correction: a required field is missing");
     if (P.energy && !(need(f->ps) && need(f->ps_in) && levels(f->wat) && levels(f->wat_in) && levels(f->T) && levels(f->T_in) &&
                       need(f->hgt_in) && need(f->hgt_next) && need(f->dswtoa_next) && need(f->lhf) && need(f->shf) && need(f->dswsfc) &&
                       need(f->uswsfc) && need(f->dlwsfc) && need(f->ulwsfc) && need(f->ulwtoa) && need(f->uswtoa)))
-        return pfail(ACE_ERR_INVALID, "total energy budget correction: a required field is missing");
-    if (P.ocean && !(need(f->sst) && need(f->sst_target) && need(f->ocean_fraction))) return pfail(ACE_ERR_INVALID, "ocean: a required field is missing");
+        return ace::fail(ACE_ERR_INVALID, "total energy budget correction: a required field is missing");
+    if (P.ocean && !(need(f->sst) && need(f->sst_target) && need(f->ocean_fraction))) return ace::fail(ACE_ERR_INVALID, "ocean: a required field is missing");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long HW = (long)P.H * P.W;
     int nblk = (int)((HW + NT - 1) / NT);
@@ -425,6 +422,6 @@ extern "C" int ace_physics_apply(ace_physics* h, const ace_phys_fields* f, int b
     if (p2) hipLaunchKernelGGL(phys_p2, grid, block, 0, s, P, *f, nblk);
     if (p3) hipLaunchKernelGGL(phys_p3, grid, block, 0, s, P, *f, nblk);
     if (p4) hipLaunchKernelGGL(phys_p4, grid, block, 0, s, P, *f, nblk);
-    if (hipGetLastError() != hipSuccess) return pfail(ACE_ERR_RUNTIME, "physics kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return ace::fail(ACE_ERR_RUNTIME, "physics kernel launch failed");
     return ACE_OK;
 }

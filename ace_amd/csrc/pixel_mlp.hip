@@ -29,18 +29,10 @@
 #include <vector>
 
 #include "../../include/ace_sfno.h"
+#include "errors.h"
 #include "pixel_act.h"
 
 #pragma clang fp contract(off)
-
-static thread_local std::string g_pmerr;
-static int pmfail(int code, const std::string& m) { g_pmerr = m; return code; }
-extern "C" const char* ace_pixel_mlp_last_error(void) { return g_pmerr.c_str(); }
-#define PM_TRY(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e__ = (expr);                                                                             \
-        if (e__ != hipSuccess) return pmfail(ACE_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
 
 namespace {
 
@@ -235,7 +227,7 @@ int launch(const PixelMlp* h, const float* x, const float* embed, float* y, int 
     else
         hipLaunchKernelGGL((pixel_mlp_kernel<MAXT, NPT, false, SOFT>), dim3((unsigned)nwg), dim3(NT), 0, st, h->a, h->blob, x, embed, y, hw,
                            upi, nunits);
-    PM_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -243,26 +235,26 @@ int launch(const PixelMlp* h, const float* x, const float* embed, float* y, int 
 
 extern "C" int ace_pixel_mlp_create2(int n_layers, const int* dims, const float* const* w_dev, const float* const* bias_dev,
                                      const int* act, int embed_layer, int embed_before_act, void* stream, void** handle) {
-    if (!handle) return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: null handle pointer");
+    if (!handle) return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_create: null handle pointer");
     *handle = nullptr;
     if (n_layers < 1 || n_layers > ACE_PIXEL_MLP_MAX_LAYERS)
-        return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: need 1 <= n_layers <= ACE_PIXEL_MLP_MAX_LAYERS (" +
+        return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_create: need 1 <= n_layers <= ACE_PIXEL_MLP_MAX_LAYERS (" +
                                            std::to_string(ACE_PIXEL_MLP_MAX_LAYERS) + ")");
-    if (!dims || !w_dev || !act) return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: null argument");
+    if (!dims || !w_dev || !act) return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_create: null argument");
     for (int l = 0; l <= n_layers; ++l)
         if (dims[l] < 1 || dims[l] > ACE_PIXEL_MLP_MAX_WIDTH)
-            return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: need 1 <= dims[l] <= ACE_PIXEL_MLP_MAX_WIDTH (" +
+            return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_create: need 1 <= dims[l] <= ACE_PIXEL_MLP_MAX_WIDTH (" +
                                                std::to_string(ACE_PIXEL_MLP_MAX_WIDTH) + ")");
     for (int l = 0; l < n_layers; ++l) {
-        if (!w_dev[l]) return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: null weight");
+        if (!w_dev[l]) return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_create: null weight");
         if (act[l] != ACE_PIXEL_MLP_ACT_NONE && act[l] != ACE_PIXEL_MLP_ACT_RELU && act[l] != ACE_PIXEL_MLP_ACT_GELU &&
             act[l] != ACE_PIXEL_MLP_ACT_SILU)
-            return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create2: act must be one of ACE_PIXEL_MLP_ACT_*");
+            return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_create2: act must be one of ACE_PIXEL_MLP_ACT_*");
     }
     if (embed_layer < -1 || embed_layer >= n_layers)
-        return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: need -1 <= embed_layer < n_layers");
+        return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_create: need -1 <= embed_layer < n_layers");
     if (embed_before_act != 0 && embed_before_act != 1)
-        return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create2: embed_before_act must be 0 or 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_create2: embed_before_act must be 0 or 1");
     hipStream_t st = static_cast<hipStream_t>(stream);
     PixelMlp* h = new PixelMlp();
     PMArgs& a = h->a;
@@ -300,7 +292,7 @@ extern "C" int ace_pixel_mlp_create2(int n_layers, const int* dims, const float*
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) {
             delete h;
-            return pmfail(ACE_ERR_RUNTIME, std::string("ace_pixel_mlp_create: reading the weights: ") + hipGetErrorString(e));
+            return ace::fail(ACE_ERR_RUNTIME, std::string("ace_pixel_mlp_create: reading the weights: ") + hipGetErrorString(e));
         }
         float* bl = blob.data() + a.boff[l];
         for (int o = 0; o < O; ++o) bl[o] = bias[o];
@@ -322,7 +314,7 @@ extern "C" int ace_pixel_mlp_create2(int n_layers, const int* dims, const float*
     if (e != hipSuccess) {
         if (h->blob) (void)hipFree(h->blob);
         delete h;
-        return pmfail(ACE_ERR_RUNTIME, std::string("ace_pixel_mlp_create: uploading the weights: ") + hipGetErrorString(e));
+        return ace::fail(ACE_ERR_RUNTIME, std::string("ace_pixel_mlp_create: uploading the weights: ") + hipGetErrorString(e));
     }
     *handle = h;
     return ACE_OK;
@@ -335,7 +327,7 @@ extern "C" int ace_pixel_mlp_create(int n_layers, const int* dims, const float* 
         for (int l = 0; l < n_layers; ++l)
             if (act[l] != ACE_PIXEL_MLP_ACT_NONE && act[l] != ACE_PIXEL_MLP_ACT_RELU) {
                 *handle = nullptr;
-                return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_create: act must be ACE_PIXEL_MLP_ACT_NONE or ACE_PIXEL_MLP_ACT_RELU");
+                return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_create: act must be ACE_PIXEL_MLP_ACT_NONE or ACE_PIXEL_MLP_ACT_RELU");
             }
     return ace_pixel_mlp_create2(n_layers, dims, w_dev, bias_dev, act, embed_layer, 0, stream, handle);
 }
@@ -349,11 +341,11 @@ extern "C" void ace_pixel_mlp_destroy(void* handle) {
 
 extern "C" int ace_pixel_mlp_forward(void* handle, const float* x, const float* embed, float* y, int batch, long hw, void* stream) {
     const PixelMlp* h = static_cast<const PixelMlp*>(handle);
-    if (!h) return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_forward: null handle");
-    if (!x || !y) return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_forward: null argument");
-    if (batch < 1 || hw < 1) return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_forward: need batch >= 1 and hw >= 1");
+    if (!h) return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_forward: null handle");
+    if (!x || !y) return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_forward: null argument");
+    if (batch < 1 || hw < 1) return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_forward: need batch >= 1 and hw >= 1");
     if (h->a.embed_layer >= 0 && !embed)
-        return pmfail(ACE_ERR_INVALID, "ace_pixel_mlp_forward: the handle was created with an embedding layer: embed must not be NULL");
+        return ace::fail(ACE_ERR_INVALID, "ace_pixel_mlp_forward: the handle was created with an embedding layer: embed must not be NULL");
     if (h->a.embed_layer < 0) embed = nullptr;
     hipStream_t st = static_cast<hipStream_t>(stream);
     constexpr int NARROW = ACE_PIXEL_MLP_NARROW_WIDTH / ACE_PIXEL_MLP_TILE, WIDE = ACE_PIXEL_MLP_MAX_WIDTH / ACE_PIXEL_MLP_TILE;

@@ -142,29 +142,29 @@ __global__ __launch_bounds__(NT) void region_segments_kernel(RegionArgs a) {
 extern "C" int ace_diag_region_segments(const float* const* srcs, const long* strides, const int* rows, const int* bounds,
                                         double* sums, float* means, int nrows, int nseg, int nplanes, int batch, int steps,
                                         int nlat, int nlon, int lat0, int nlat_r, int lon0, int nlon_r, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_region_segments: need 0 <= nplanes <= 65535");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_region_segments: need 0 <= nplanes <= 65535");
     if (batch < 1 || batch > 65535 || steps < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_region_segments: need 1 <= batch <= 65535 (a grid dimension), steps >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_region_segments: need 1 <= batch <= 65535 (a grid dimension), steps >= 1");
     if (nlat < 1 || nlon < 1 || nrows < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_region_segments: need nlat >= 1, nlon >= 1, nrows >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_region_segments: need nlat >= 1, nlon >= 1, nrows >= 1");
     if (lat0 < 0 || nlat_r < 1 || (long)lat0 + nlat_r > nlat)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_region_segments: need 0 <= lat0, 1 <= nlat_r, lat0 + nlat_r <= nlat");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_region_segments: need 0 <= lat0, 1 <= nlat_r, lat0 + nlat_r <= nlat");
     if (lon0 < 0 || nlon_r < 1 || (long)lon0 + nlon_r > nlon)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_region_segments: need 0 <= lon0, 1 <= nlon_r, lon0 + nlon_r <= nlon");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_region_segments: need 0 <= lon0, 1 <= nlon_r, lon0 + nlon_r <= nlon");
     const long R = (long)nlat_r * nlon_r;
     if (nchunk_for(R) > 2147483647L)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_region_segments: need nlat_r * nlon_r <= 1024 * (2^31 - 1)");
-    if (nseg < 0 || nseg > 2147483646) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_region_segments: need 0 <= nseg < 2^31 - 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_region_segments: need nlat_r * nlon_r <= 1024 * (2^31 - 1)");
+    if (nseg < 0 || nseg > 2147483646) return ace::fail(ACE_ERR_INVALID, "ace_diag_region_segments: need 0 <= nseg < 2^31 - 1");
     if (nplanes == 0 || nseg == 0) return ACE_OK;
-    if (!srcs || !strides || !rows || !bounds) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_region_segments: null argument");
+    if (!srcs || !strides || !rows || !bounds) return ace::fail(ACE_ERR_INVALID, "ace_diag_region_segments: null argument");
     if (!sums && !means)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_region_segments: null argument (at least one of sums and means is needed)");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_region_segments: null argument (at least one of sums and means is needed)");
     RegionArgs a;
     a.srcs = srcs; a.strides = strides; a.rows = rows; a.bounds = bounds; a.sums = sums; a.means = means;
     a.nrows = nrows; a.nseg = nseg; a.B = batch; a.T = steps;
     a.nlon = nlon; a.lat0 = lat0; a.lon0 = lon0; a.nlon_r = nlon_r; a.R = R;
     const dim3 grid((unsigned)nchunk_for(R), nplanes, batch);
     hipLaunchKernelGGL(region_segments_kernel, grid, dim3(NT), 0, static_cast<hipStream_t>(stream), a);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

@@ -184,26 +184,26 @@ extern "C" int ace_diag_regress_window(const float* const* gen, const long* gen_
                                        double* maps, const float* eps, const int* wrows, const float* weights, int nw,
                                        double* partial, long long* below_count, double* below_frac, int nrows, int nterms,
                                        int nmaps, int t_begin, int nplanes, int batch, int steps, long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_regress_window: need 0 <= nplanes <= 65535");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_regress_window: need 0 <= nplanes <= 65535");
     if (nmaps < 0 || nmaps > MAX_MAPS)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_regress_window: need 0 <= nmaps <= " + std::to_string(MAX_MAPS) +
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_regress_window: need 0 <= nmaps <= " + std::to_string(MAX_MAPS) +
                                                " (the accumulators of a pixel stay in registers); split the maps over several calls");
     if (nterms < 0 || nterms > MAX_TERMS || (nterms > 0 && nmaps == 0))
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_regress_window: need 0 <= nterms <= 64, and nmaps >= 1 when nterms > 0");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_regress_window: need 0 <= nterms <= 64, and nmaps >= 1 when nterms > 0");
     if (batch < 1 || steps < 1 || (long)batch * steps > 2147483647L)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_regress_window: need batch >= 1, steps >= 1, batch * steps < 2^31 (32-bit "
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_regress_window: need batch >= 1, steps >= 1, batch * steps < 2^31 (32-bit "
                                                "counters per thread)");
     if (hw < 1 || nchunk_for(hw) > 2147483647L || nrows < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_regress_window: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1");
-    if (t_begin < 0) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_regress_window: need t_begin >= 0");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_regress_window: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1");
+    if (t_begin < 0) return ace::fail(ACE_ERR_INVALID, "ace_diag_regress_window: need t_begin >= 0");
     if (nplanes == 0) return ACE_OK;
     if (!gen || !gen_strides || !target || !target_strides || !rows)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_regress_window: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_regress_window: null argument");
     if (nterms > 0 && (!coef || !slot || !maps))
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_regress_window: null argument (coef, slot and maps are needed when nterms > 0)");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_regress_window: null argument (coef, slot and maps are needed when nterms > 0)");
     const bool ind = eps != nullptr;
     if (ind && (!wrows || !weights || !partial || !below_count || !below_frac || nw < 1))
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_regress_window: null argument (wrows, weights, partial, below_count and "
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_regress_window: null argument (wrows, weights, partial, below_count and "
                                                "below_frac are needed when eps is given)");
     if ((nterms == 0 && !ind) || t_begin >= steps) return ACE_OK;
     RegArgs a;
@@ -219,10 +219,10 @@ extern "C" int ace_diag_regress_window(const float* const* gen, const long* gen_
     if (a.nmaps == 0) launch<0>(a, ind, grid, s);
     else if (a.nmaps <= 4) launch<4>(a, ind, grid, s);
     else launch<MAX_MAPS>(a, ind, grid, s);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     if (ind) {
         hipLaunchKernelGGL(regress_frac_kernel, dim3(nplanes, 2), dim3(64), 0, s, a);
-        DIAG_TRY(hipGetLastError());
+        ACE_HIP_TRY(hipGetLastError());
     }
     return ACE_OK;
 }

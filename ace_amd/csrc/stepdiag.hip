@@ -173,28 +173,28 @@ __global__ __launch_bounds__(64) void correction_combine_kernel(const double* __
 
 extern "C" int ace_stepdiag_snapshot(const float* const* srcs, const long* src_strides, float* const* dsts, const long* dst_strides,
                                      int nplanes, int batch, long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_stepdiag_snapshot: need 0 <= nplanes <= 65535 (a grid dimension)");
-    if (batch < 1 || batch > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_stepdiag_snapshot: need 1 <= batch <= 65535 (a grid dimension)");
-    if (hw < 1 || nchunk_for(hw) > 2147483647L) return ace_diag_fail_(ACE_ERR_INVALID, "ace_stepdiag_snapshot: need 1 <= hw <= 1024 * (2^31 - 1)");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_stepdiag_snapshot: need 0 <= nplanes <= 65535 (a grid dimension)");
+    if (batch < 1 || batch > 65535) return ace::fail(ACE_ERR_INVALID, "ace_stepdiag_snapshot: need 1 <= batch <= 65535 (a grid dimension)");
+    if (hw < 1 || nchunk_for(hw) > 2147483647L) return ace::fail(ACE_ERR_INVALID, "ace_stepdiag_snapshot: need 1 <= hw <= 1024 * (2^31 - 1)");
     if (nplanes == 0) return ACE_OK;
-    if (!srcs || !src_strides || !dsts || !dst_strides) return ace_diag_fail_(ACE_ERR_INVALID, "ace_stepdiag_snapshot: null argument");
+    if (!srcs || !src_strides || !dsts || !dst_strides) return ace::fail(ACE_ERR_INVALID, "ace_stepdiag_snapshot: null argument");
     hipLaunchKernelGGL(stepdiag_snapshot_kernel, dim3((unsigned)nchunk_for(hw), nplanes, batch), dim3(NT), 0,
                        static_cast<hipStream_t>(stream), srcs, src_strides, dsts, dst_strides, hw);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
 extern "C" int ace_stepdiag_delta_window(const float* const* outs, const long* out_strides, float* const* snaps,
                                          const long* snap_strides, int nplanes, int batch, int steps, long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_stepdiag_delta_window: need 0 <= nplanes <= 65535 (a grid dimension)");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_stepdiag_delta_window: need 0 <= nplanes <= 65535 (a grid dimension)");
     if (batch < 1 || steps < 1 || (long)batch * steps > 65535)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_stepdiag_delta_window: need batch >= 1, steps >= 1, batch * steps <= 65535 (a grid dimension)");
-    if (hw < 1 || nchunk_for(hw) > 2147483647L) return ace_diag_fail_(ACE_ERR_INVALID, "ace_stepdiag_delta_window: need 1 <= hw <= 1024 * (2^31 - 1)");
+        return ace::fail(ACE_ERR_INVALID, "ace_stepdiag_delta_window: need batch >= 1, steps >= 1, batch * steps <= 65535 (a grid dimension)");
+    if (hw < 1 || nchunk_for(hw) > 2147483647L) return ace::fail(ACE_ERR_INVALID, "ace_stepdiag_delta_window: need 1 <= hw <= 1024 * (2^31 - 1)");
     if (nplanes == 0) return ACE_OK;
-    if (!outs || !out_strides || !snaps || !snap_strides) return ace_diag_fail_(ACE_ERR_INVALID, "ace_stepdiag_delta_window: null argument");
+    if (!outs || !out_strides || !snaps || !snap_strides) return ace::fail(ACE_ERR_INVALID, "ace_stepdiag_delta_window: null argument");
     hipLaunchKernelGGL(stepdiag_delta_kernel, dim3((unsigned)nchunk_for(hw), nplanes, batch * steps), dim3(NT), 0,
                        static_cast<hipStream_t>(stream), outs, out_strides, snaps, snap_strides, steps, hw);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }
 
@@ -207,23 +207,23 @@ extern "C" int ace_diag_correction_window(const float* const* deltas, const long
                                           const int* wrows, const float* weights, int nw, double* partial, double* signed_sum,
                                           double* magnitude_sum, double* series, int nrows, int n_time, int t0, int nplanes, int batch,
                                           int steps, long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_correction_window: need 0 <= nplanes <= 65535");
-    if (steps < 1 || steps > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_correction_window: need 1 <= steps <= 65535");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_correction_window: need 0 <= nplanes <= 65535");
+    if (steps < 1 || steps > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_correction_window: need 1 <= steps <= 65535");
     if (batch < 1 || hw < 1 || nw < 1 || nrows < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_correction_window: need batch >= 1, hw >= 1, nw >= 1, nrows >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_correction_window: need batch >= 1, hw >= 1, nw >= 1, nrows >= 1");
     if (t0 < 0 || t0 + (long)steps > n_time)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_correction_window: need 0 <= t0, t0 + steps <= n_time");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_correction_window: need 0 <= t0, t0 + steps <= n_time");
     if (nplanes == 0) return ACE_OK;
     if (!deltas || !strides || !stds || !rows || !wrows || !weights || !partial || !signed_sum || !magnitude_sum || !series)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_correction_window: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_correction_window: null argument");
     const long nchunk = nchunk_for(hw);
-    if (nchunk > 2147483647L) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_correction_window: plane too large");
+    if (nchunk > 2147483647L) return ace::fail(ACE_ERR_INVALID, "ace_diag_correction_window: plane too large");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(correction_window_kernel, dim3((unsigned)nchunk, nplanes), dim3(NT), 0, s, deltas, strides, stds, rows, wrows,
                        weights, nw, partial, signed_sum, magnitude_sum, nrows, batch, steps, hw, (int)nchunk);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(correction_combine_kernel, dim3(steps, nplanes), dim3(64), 0, s, partial, rows, wrows, nw, series, nrows, n_time,
                        batch, steps, t0, nchunk * WAVES);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

@@ -117,21 +117,21 @@ __global__ __launch_bounds__(NT) void time_segments_kernel(SegArgs a) {
 extern "C" int ace_diag_time_segments(const float* const* srcs, const long* strides, const int* rows, const int* edges,
                                       double* sums, float* means, int nrows, int nseg, int nplanes, int batch, int steps,
                                       long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_time_segments: need 0 <= nplanes <= 65535");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_time_segments: need 0 <= nplanes <= 65535");
     if (batch < 1 || batch > 65535 || steps < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_time_segments: need 1 <= batch <= 65535 (a grid dimension), steps >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_time_segments: need 1 <= batch <= 65535 (a grid dimension), steps >= 1");
     if (hw < 1 || nchunk_for(hw) > 2147483647L || nrows < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_time_segments: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1");
-    if (nseg < 0 || nseg > 2147483646) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_time_segments: need 0 <= nseg < 2^31 - 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_time_segments: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1");
+    if (nseg < 0 || nseg > 2147483646) return ace::fail(ACE_ERR_INVALID, "ace_diag_time_segments: need 0 <= nseg < 2^31 - 1");
     if (nplanes == 0 || nseg == 0) return ACE_OK;
-    if (!srcs || !strides || !rows || !edges) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_time_segments: null argument");
+    if (!srcs || !strides || !rows || !edges) return ace::fail(ACE_ERR_INVALID, "ace_diag_time_segments: null argument");
     if (!sums && !means)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_time_segments: null argument (at least one of sums and means is needed)");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_time_segments: null argument (at least one of sums and means is needed)");
     SegArgs a;
     a.srcs = srcs; a.strides = strides; a.rows = rows; a.edges = edges; a.sums = sums; a.means = means;
     a.nrows = nrows; a.nseg = nseg; a.B = batch; a.T = steps; a.HW = hw;
     const dim3 grid((unsigned)nchunk_for(hw), nplanes, batch);
     hipLaunchKernelGGL(time_segments_kernel, grid, dim3(NT), 0, static_cast<hipStream_t>(stream), a);
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

@@ -187,19 +187,19 @@ __global__ __launch_bounds__(NT) void video_window_kernel(VideoArgs a) {
 extern "C" int ace_diag_video_window(const float* const* gen, const long* gen_strides, const float* const* target,
                                      const long* target_strides, const int* rows, double* mean, double* sq, float* err, int nrows,
                                      int n_time, int t0, int assign, int nplanes, int batch, int steps, long hw, void* stream) {
-    if (nplanes < 0 || nplanes > 65535) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_video_window: need 0 <= nplanes <= 65535 (a grid dimension)");
+    if (nplanes < 0 || nplanes > 65535) return ace::fail(ACE_ERR_INVALID, "ace_diag_video_window: need 0 <= nplanes <= 65535 (a grid dimension)");
     if (batch < 1 || steps < 1 || steps > 65535)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_video_window: need batch >= 1 and 1 <= steps <= 65535 (a grid dimension)");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_video_window: need batch >= 1 and 1 <= steps <= 65535 (a grid dimension)");
     if (hw < 1 || nchunk_for(hw) > 2147483647L || nrows < 1 || n_time < 1)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_video_window: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1, n_time >= 1");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_video_window: need 1 <= hw <= 1024 * (2^31 - 1), nrows >= 1, n_time >= 1");
     if (t0 < 0 || (long)t0 + steps > n_time)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_video_window: need t0 >= 0 and t0 + steps <= n_time");
-    if (!mean) return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_video_window: null argument (mean)");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_video_window: need t0 >= 0 and t0 + steps <= n_time");
+    if (!mean) return ace::fail(ACE_ERR_INVALID, "ace_diag_video_window: null argument (mean)");
     if ((sq == nullptr) != (err == nullptr))
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_video_window: sq and err are given together (the extended videos) or not at all");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_video_window: sq and err are given together (the extended videos) or not at all");
     if (nplanes == 0) return ACE_OK;
     if (!gen || !gen_strides || !target || !target_strides || !rows)
-        return ace_diag_fail_(ACE_ERR_INVALID, "ace_diag_video_window: null argument");
+        return ace::fail(ACE_ERR_INVALID, "ace_diag_video_window: null argument");
     VideoArgs a;
     a.gen = gen; a.gen_strides = gen_strides; a.target = target; a.target_strides = target_strides; a.rows = rows;
     a.mean = mean; a.sq = sq; a.err = err; a.nrows = nrows; a.n_time = n_time; a.t0 = t0; a.B = batch; a.HW = hw;
@@ -212,6 +212,6 @@ extern "C" int ace_diag_video_window(const float* const* gen, const long* gen_st
         if (assign) hipLaunchKernelGGL((video_window_kernel<false, true>), grid, dim3(NT), 0, s, a);
         else hipLaunchKernelGGL((video_window_kernel<false, false>), grid, dim3(NT), 0, s, a);
     }
-    DIAG_TRY(hipGetLastError());
+    ACE_HIP_TRY(hipGetLastError());
     return ACE_OK;
 }

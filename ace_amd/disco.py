@@ -135,13 +135,7 @@ def check_limits(in_chans: int, out_chans: int, kernel_size: int, who: str = "di
                                   f"ACE_DISCO_MAX_PRODUCTS = {MAX_PRODUCTS}")
 
 
-def _check(rc: int) -> None:
-    if rc == _lib.ACE_OK:
-        return
-    msg = _lib.lib().ace_disco_last_error().decode()
-    if rc == _lib.ACE_ERR_INVALID:
-        raise ValueError(msg)
-    raise RuntimeError(msg)
+_check = functools.partial(_lib.check, family="disco")
 
 
 class DiscoHandle:

@@ -21,6 +21,7 @@ the SFNO path; every tensor carries a 64-word "bound slot" (max |x|, produced by
 consuming convolution derives its power-of-two scale.  There is no CPU path: tensors must live on an MI355X."""
 import ctypes
 import dataclasses
+import functools
 import os
 from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
@@ -35,10 +36,7 @@ ACT_NONE, ACT_GELU = 0, 1
 _INF = float("inf")
 
 
-def _check(rc: int) -> None:
-    if rc != 0:
-        msg = _lib.lib().ace_hpx_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
+_check = functools.partial(_lib.check, family="hpx")
 
 
 @dataclasses.dataclass

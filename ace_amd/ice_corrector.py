@@ -13,10 +13,13 @@ where the reference's ``if torch.any(mask)`` reads the device up to three times 
 tensors in place; the input is only read.  The torch path, like the reference, returns new tensors for the fields it changes."""
 import ctypes
 import dataclasses
+import functools
 from ctypes import c_long
 from typing import Any, Dict, List, Mapping, Optional, Tuple
 
 import torch
+
+from ._lib import check
 
 TensorMapping = Mapping[str, torch.Tensor]
 TensorDict = Dict[str, torch.Tensor]
@@ -216,11 +219,7 @@ class IceCorrector:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _check(rc: int) -> None:
-    from . import _lib
-    if rc != 0:
-        msg = _lib.lib().ace_ice_budget_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
+_check = functools.partial(check, family="ice_budget")
 
 
 class FusedIceCorrector:
@@ -249,27 +248,17 @@ class FusedIceCorrector:
     def _make_scratch(self, nbytes: int) -> torch.Tensor:
         return torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
 
-    def _plane(self, dst, t: torch.Tensor, name: str) -> None:
-        B, (H, W) = self.batch, self.shape
-        if t.dtype != torch.float32 or t.device != self.device:
-            raise TypeError(f"fused ice corrector: '{name}' must be float32 on {self.device}, got {t.dtype} on {t.device}")
-        if t.dim() == 4 and t.shape[1] == 1:
-            t = t[:, 0]
-        if t.dim() != 3 or tuple(t.shape) != (B, H, W) or t.stride(-1) != 1 or t.stride(-2) != W:
-            raise ValueError(f"fused ice corrector: '{name}' must be ({B}, {H}, {W}) with contiguous rows, got shape "
-                             f"{tuple(t.shape)} strides {t.stride()}")
-        dst.p, dst.stride = t.data_ptr(), (t.stride(0) if B > 1 else H * W)
-
     def fields(self, inp, gen, forcing=None):
         """The planes of one step: a missing field raises KeyError, as the reference does."""
-        from ._lib import IceFields
-        f = IceFields()
+        from . import _lib
+        f = _lib.IceFields()
+        plane = lambda dst, t, name: _lib.bind_plane(dst, t, self.batch, self.shape, self.device, "fused ice corrector", name)
         for i, (name, terms, area_mode, masked) in enumerate(self._plan):
             v = f.var[i]
-            self._plane(v.old_mass, inp[name], name)
+            plane(v.old_mass, inp[name], name)
             for attr, term in zip(("source", "sink", "transport"), terms):
-                self._plane(getattr(v, attr), gen[term], term)
-            self._plane(v.mass, gen[name], name)
+                plane(getattr(v, attr), gen[term], term)
+            plane(v.mass, gen[name], name)
             v.area_mode, v.masked = int(area_mode), int(masked)
         f.nvars = len(self._plan)
         return f

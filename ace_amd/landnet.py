@@ -8,6 +8,7 @@ keys: "pos_embed.pos_embed", "model.0.layers.0.weight", "model.0.layers.0.bias",
 ``forward`` is native.  No CPU path."""
 import ctypes
 import dataclasses
+import functools
 from typing import List, Optional, Tuple
 
 import torch
@@ -21,13 +22,7 @@ MAX_LAYERS, MAX_WIDTH = 8, 256
 ACT_NONE, ACT_RELU = 0, 1
 
 
-def _check(rc: int) -> None:
-    if rc == _lib.ACE_OK:
-        return
-    msg = _lib.lib().ace_pixel_mlp_last_error().decode()
-    if rc == _lib.ACE_ERR_INVALID:
-        raise ValueError(msg)
-    raise RuntimeError(msg)
+_check = functools.partial(_lib.check, family="pixel_mlp")
 
 
 class _PositionalEmbedding(nn.Module):

@@ -10,10 +10,13 @@ Two paths compute the same thing.  The torch path is the reference's elementwise
 per distinct mask is computed on the device with the reference's own torch expression and cached, so the kernel only selects
 and its output is bitwise the torch path's."""
 import dataclasses
+import functools
 import re
 from typing import Any, Dict, List, Mapping, Optional, Tuple, Union
 
 import torch
+
+from ._lib import check
 
 TensorMapping = Mapping[str, torch.Tensor]
 _LEVEL = re.compile(r"_(\d+)$")
@@ -249,11 +252,7 @@ class StaticSpatialMasking:
         return out
 
 
-def _check(rc: int) -> None:
-    if rc != 0:
-        from . import _lib
-        msg = _lib.lib().ace_mask_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
+_check = functools.partial(check, family="mask")
 
 
 class NullSpatialMasking:

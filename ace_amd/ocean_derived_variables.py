@@ -376,9 +376,7 @@ class OceanDeriveFn:
         d.batch, d.steps, d.hw, d.t_chunk = B, steps, H * W, int(self.t_chunk)
         with torch.cuda.device(device):
             rc = _lib.lib().ace_ocean_derive_window(ctypes.byref(d), torch.cuda.current_stream(device).cuda_stream)
-        if rc != 0:
-            msg = _lib.lib().ace_ocean_derive_last_error().decode()
-            raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
+        _lib.check(rc, "ocean_derive")
         self.launches += 1
         del keep                                          # the launch is enqueued on the tensors' own stream: a copy made above may go
         return out

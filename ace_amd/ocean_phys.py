@@ -19,12 +19,6 @@ from .ocean_corrector import _name, level_names, ohc_flux_source
 _HFDS = {"residual_prediction": 1, "prescribed": 2}
 
 
-def _check(rc: int) -> None:
-    if rc != 0:
-        msg = _lib.lib().ace_ocean_phys_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
-
-
 def _atm(data, standard: str):
     for prefix in ATMOSPHERE_FIELD_NAME_PREFIXES[standard]:
         if prefix in data:
@@ -70,58 +64,48 @@ class FusedOceanCorrector:
         self.handle = c_void_p()
         p = lambda t: t.data_ptr() if t is not None else None
         with torch.cuda.device(self.device):
-            _check(_lib.lib().ace_ocean_phys_create(ctypes.byref(c), p(wl), p(dz), p(mask_ohc), p(mask0), ctypes.byref(self.handle)))
-
-    def _plane(self, dst, t: torch.Tensor, name: str, writable: bool = False) -> None:
-        B, (H, W) = self.batch, self.shape
-        if t.dtype != torch.float32 or t.device != self.device:
-            raise TypeError(f"fused ocean corrector: '{name}' must be float32 on {self.device}, got {t.dtype} on {t.device}")
-        if t.dim() == 4 and t.shape[1] == 1:
-            t = t[:, 0]
-        if t.dim() != 3 or tuple(t.shape) != (B, H, W) or t.stride(-1) != 1 or t.stride(-2) != W:
-            raise ValueError(f"fused ocean corrector: '{name}' must be ({B}, {H}, {W}) with contiguous rows, got shape "
-                             f"{tuple(t.shape)} strides {t.stride()}")
-        dst.p, dst.stride = t.data_ptr(), (t.stride(0) if B > 1 else H * W)
+            _lib.check(_lib.lib().ace_ocean_phys_create(ctypes.byref(c), p(wl), p(dz), p(mask_ohc), p(mask0), ctypes.byref(self.handle)), "ocean_phys")
 
     def fields(self, inp, gen, forcing) -> OceanFields:
         cfg, c = self._corrector.config, self.config
         f = OceanFields()
+        plane = lambda dst, t, name: _lib.bind_plane(dst, t, self.batch, self.shape, self.device, "fused ocean corrector", name)
         active = set(self._corrector.corrections)
         positive = self._corrector.force_positive_names if "force_positive" in active else []
         if len(positive) > OCEAN_MAX_POSITIVE:
             raise NotImplementedError(f"the fused ocean corrector clamps up to {OCEAN_MAX_POSITIVE} fields, got {len(positive)}")
         for k, n in enumerate(positive):
-            self._plane(f.positive[k], gen[n], n, True)
+            plane(f.positive[k], gen[n], n)
         f.npositive = len(positive)
         if c.sea_ice:
             sic = cfg.sea_ice_fraction_correction
-            self._plane(f.sif, gen[sic.sea_ice_fraction_name], sic.sea_ice_fraction_name, True)
+            plane(f.sif, gen[sic.sea_ice_fraction_name], sic.sea_ice_fraction_name)
             if len(sic.zero_where_ice_free_names) > OCEAN_MAX_ZERO:
                 raise NotImplementedError(f"the fused ocean corrector zeroes up to {OCEAN_MAX_ZERO} fields where ice free")
             for k, n in enumerate(sic.zero_where_ice_free_names):
-                self._plane(f.zero[k], gen[n], n, True)
+                plane(f.zero[k], gen[n], n)
             f.nzero = len(sic.zero_where_ice_free_names)
             if c.remove_negative_ocean_fraction:
-                self._plane(f.reb_land, inp[sic.land_fraction_name], sic.land_fraction_name)
+                plane(f.reb_land, inp[sic.land_fraction_name], sic.land_fraction_name)
         ssf_forcing = False
         if c.hfds:
             hname = "hfds" if "hfds" in gen else "hfds_total_area"
-            self._plane(f.hfds, gen[hname], hname, True)
+            plane(f.hfds, gen[hname], hname)
             f.hfds_total_area = int(hname == "hfds_total_area")
-            self._plane(f.in_land, inp["land_fraction"], "land_fraction")
+            plane(f.in_land, inp["land_fraction"], "land_fraction")
             sname = _name(inp, "sea_ice_fraction") or "ocean_sea_ice_fraction"
-            self._plane(f.in_sif, inp[sname], sname)
+            plane(f.in_sif, inp[sname], sname)
             f.in_sif_is_ocean_sif = int(sname == "ocean_sea_ice_fraction")
-            self._plane(f.in_sst, inp["sst"], "sst")
+            plane(f.in_sst, inp["sst"], "sst")
             for attr, std in (("dlw", "sfc_down_lw_radiative_flux"), ("ulw", "sfc_up_lw_radiative_flux"),
                               ("dsw", "sfc_down_sw_radiative_flux"), ("usw", "sfc_up_sw_radiative_flux"),
                               ("lhf", "latent_heat_flux"), ("shf", "sensible_heat_flux"), ("precip", "precipitation_rate")):
-                self._plane(getattr(f, attr), _atm(forcing, std), std)
+                plane(getattr(f, attr), _atm(forcing, std), std)
             if "total_frozen_precipitation_rate" in forcing:
-                self._plane(f.frozen, forcing["total_frozen_precipitation_rate"], "total_frozen_precipitation_rate")
+                plane(f.frozen, forcing["total_frozen_precipitation_rate"], "total_frozen_precipitation_rate")
             elif all(n in forcing for n in ("ICEsfc", "GRAUPELsfc", "SNOWsfc")):
                 for k, n in enumerate(("ICEsfc", "GRAUPELsfc", "SNOWsfc")):
-                    self._plane(f.frozen_parts[k], forcing[n], n)
+                    plane(f.frozen_parts[k], forcing[n], n)
             else:
                 _atm(forcing, "surface_pressure")      # AtmosphereData's zero fallback is zeros_like(surface_pressure)
             ssf_forcing = bool(f.hfds_total_area)
@@ -134,50 +118,50 @@ class FusedOceanCorrector:
                 raise ValueError(f"The last dimension of integrand must match the number of vertical layers in the depth vertical "
                                  f"coordinate: {len(thetao)} / {len(thetao_in)} thetao levels, {c.nlev} layers.")
             for k in range(c.nlev):
-                self._plane(f.thetao[k], gen[thetao[k]], thetao[k], True)
-                self._plane(f.thetao_in[k], inp[thetao_in[k]], thetao_in[k])
+                plane(f.thetao[k], gen[thetao[k]], thetao[k])
+                plane(f.thetao_in[k], inp[thetao_in[k]], thetao_in[k])
             if "sst" in gen:
-                self._plane(f.sst, gen["sst"], "sst", True)
+                plane(f.sst, gen["sst"], "sst")
             src = ohc_flux_source(gen, forcing)
             if src in ("gen_total_area", "gen"):
                 hname = "hfds_total_area" if src == "gen_total_area" else "hfds"
                 if c.hfds and f.hfds.p and f.hfds.p != gen[hname].data_ptr():
                     raise NotImplementedError("fused ocean corrector: output with both hfds and hfds_total_area and both flux "
                                               "corrections on; use the torch path (OceanCorrector.fused = False)")
-                self._plane(f.hfds, gen[hname], hname, True)
+                plane(f.hfds, gen[hname], hname)
                 f.flux_source = 0 if src == "gen_total_area" else 1
             elif "hfds" in inp:
-                self._plane(f.in_flux, inp["hfds"], "hfds")
+                plane(f.in_flux, inp["hfds"], "hfds")
                 f.flux_source = 2
             else:
-                self._plane(f.in_flux, inp["hfds_total_area"], "hfds_total_area")
+                plane(f.in_flux, inp["hfds_total_area"], "hfds_total_area")
                 iname = "sea_surface_fraction" if "sea_surface_fraction" in inp else "land_fraction"
-                self._plane(f.in_ssf, inp[iname], iname)
+                plane(f.in_ssf, inp[iname], iname)
                 f.in_ssf_is_land = int(iname == "land_fraction")
                 f.flux_source = 3
             if "hfgeou" in forcing:
-                self._plane(f.hfgeou, forcing["hfgeou"], "hfgeou")
+                plane(f.hfgeou, forcing["hfgeou"], "hfgeou")
             ssf_forcing = True
         if ssf_forcing:
             fname = "sea_surface_fraction" if "sea_surface_fraction" in forcing else "land_fraction"
-            self._plane(f.f_ssf, forcing[fname], fname)
+            plane(f.f_ssf, forcing[fname], fname)
             f.f_ssf_is_land = int(fname == "land_fraction")
         return f
 
     def __call__(self, inp, gen, forcing):
         f = self.fields(inp, gen, forcing)
         with torch.cuda.device(self.device):
-            _check(_lib.lib().ace_ocean_phys_apply(self.handle, ctypes.byref(f), self.batch,
-                                                   torch.cuda.current_stream(self.device).cuda_stream))
+            _lib.check(_lib.lib().ace_ocean_phys_apply(self.handle, ctypes.byref(f), self.batch,
+                                                       torch.cuda.current_stream(self.device).cuda_stream), "ocean_phys")
         return gen
 
     def apply(self, fields: OceanFields, stream: int) -> None:
         """One step on planes resolved once by ``fields`` (static buffers: ``OceanRolloutEngine`` keeps a struct per step)."""
-        _check(_lib.lib().ace_ocean_phys_apply(self.handle, ctypes.byref(fields), self.batch, stream))
+        _lib.check(_lib.lib().ace_ocean_phys_apply(self.handle, ctypes.byref(fields), self.batch, stream), "ocean_phys")
 
     def launches(self) -> Tuple[int, int]:
         o1, o2 = c_long(0), c_long(0)
-        _check(_lib.lib().ace_ocean_phys_launches(self.handle, ctypes.byref(o1), ctypes.byref(o2)))
+        _lib.check(_lib.lib().ace_ocean_phys_launches(self.handle, ctypes.byref(o1), ctypes.byref(o2)), "ocean_phys")
         return o1.value, o2.value
 
     def __del__(self):

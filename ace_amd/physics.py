@@ -7,6 +7,7 @@ RolloutEngine's static buffers, one ``ace_phys_fields`` struct per step of the w
 (ace_amd/corrector.py, ace_amd/ocean.py: what ``Stepper.predict`` runs) stays the readable restatement and the CPU-testable
 one; both are held to the reference's own golden rollouts."""
 import ctypes
+import functools
 from ctypes import c_int, c_void_p
 from typing import Callable, Dict, List, Mapping, Optional, Tuple
 
@@ -20,10 +21,7 @@ from ._lib import MAX_LEVELS, MAX_POSITIVE, MAX_PRESCRIBED, PhysConfig, PhysFiel
 _MOISTURE = {None: 0, "precipitation": 1, "evaporation": 2, "advection_and_precipitation": 3, "advection_and_evaporation": 4}
 
 
-def _check(rc: int) -> None:
-    if rc != 0:
-        msg = _lib.lib().ace_physics_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
+_check = functools.partial(_lib.check, family="physics")
 
 
 # ---- name resolution with AtmosphereData's rules (first prefix present; level-stacked prefixes end in _{k}) -----------------

@@ -19,6 +19,7 @@ with 2 x 2 average pooling (floor at odd sizes) on the way down and bilinear x 2
 the skip addition on the way up.  There is no CPU path: tensors must live on an MI355X."""
 import ctypes
 import dataclasses
+import functools
 from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch
@@ -26,6 +27,7 @@ from torch import nn
 
 from . import _lib
 from .healpix import CappedGELU
+from .healpix import _check as _check_hpx
 from .registry import ModuleConfig, ModuleSelector
 
 ACT_NONE, ACT_GELU = 0, 1
@@ -35,16 +37,7 @@ _MAX_REACH = 16      # (k - 1) dil the packed engine reads past a row
 _SLOTS = 512
 
 
-def _check(rc: int) -> None:
-    if rc != 0:
-        msg = _lib.lib().ace_ll_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
-
-
-def _check_hpx(rc: int) -> None:
-    if rc != 0:
-        msg = _lib.lib().ace_hpx_last_error().decode()
-        raise (ValueError if rc == _lib.ACE_ERR_INVALID else RuntimeError)(msg)
+_check = functools.partial(_lib.check, family="ll")
 
 
 def _round4(n: int) -> int:

@@ -28,6 +28,8 @@ from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
+from .aggregator import _check
+
 TensorMapping = Mapping[str, torch.Tensor]
 
 TIME_MEAN_LABEL = "time_mean_norm"
@@ -78,11 +80,6 @@ def diagnosed_names(corrector, ocean, out_names: Sequence[str], prescribed: Sequ
         raise ValueError("post-corrector adjustment names overlap the corrector's modified names: "
                          f"{[ocean.surface_temperature_name]}")
     return [n for n in names if n not in prescribed]
-
-
-def _check(rc: int) -> None:
-    from .aggregator import _check as check
-    check(rc)
 
 
 class CorrectionDeltaRecorder:

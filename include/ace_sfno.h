@@ -13,8 +13,12 @@
  *     unless the name ends in _host;
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  Calls enqueue
  *     work and return; nothing synchronises unless documented;
- *   - return value 0 = success; on failure a negative code is returned and
- *     ace_last_error() holds a message (thread-local).  The library never aborts;
+ *   - return value 0 = success; on failure a negative code is returned and the thread has a
+ *     message.  The library never aborts.  There is one message per thread for the whole
+ *     library: after a call of any family returns non-zero, ace_last_error() and every
+ *     ace_<family>_last_error() return that call's message on the same thread, until the
+ *     thread's next failing call.  What a getter returns on a thread with no failure before
+ *     it is not specified;
  *   - tensors are contiguous, row-major, in the reference's own shapes.
  */
 #ifndef ACE_SFNO_H
@@ -29,7 +33,7 @@ extern "C" {
 #define ACE_ERR_RUNTIME (-2)   /* HIP runtime failure (Python: RuntimeError) */
 #define ACE_ERR_STATE (-3)     /* call sequence error, e.g. forward before all weights are set */
 
-const char* ace_last_error(void);
+const char* ace_last_error(void);          /* this thread's message of its last failing call, of any family */
 int ace_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -416,7 +420,7 @@ int ace_gmr_unpack_denormalize(const float* src, const float* mean, const float*
  * float4 accesses on a (plane, sample) whose hw % 4 == 0 and whose addresses are 16-byte aligned, scalar otherwise.
  * Stream-ordered; no allocation or host synchronisation.
  * ------------------------------------------------------------------------------------------ */
-const char* ace_mask_last_error(void);
+const char* ace_mask_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 int ace_mask_planes(const float* const* srcs, const long* src_strides, float* const* dsts, const long* dst_strides,
                     const int* mask_idx, const unsigned char* hits, int nmask, const float* fill, int nplanes, int batch,
                     long hw, void* stream);
@@ -471,7 +475,7 @@ int ace_mask_pack_normalize(const float* const* srcs, const long* src_strides, c
 #define ACE_COUPLE_OFRAC_CARRIED 0
 #define ACE_COUPLE_OFRAC_FROM_SIF 1
 #define ACE_COUPLE_OFRAC_FROM_OCEAN_SIF 2
-const char* ace_couple_last_error(void);
+const char* ace_couple_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 int ace_couple_ocean_to_atmosphere(const float* const* srcs, const long* src_strides, float* const* dsts,
                                    const long* dst_strides, const float* const* masks, int npass, int mode, int interpolate,
                                    int n_inner, int batch, long hw, void* stream);
@@ -782,7 +786,7 @@ int ace_couple_atmosphere_to_ocean(const float* const* srcs, const long* src_str
  *                  extrema per pixel in registers: no scratch, no LDS, each slot owned by one thread, no atomics, bitwise
  *                  repeatable.  One launch however many planes; no allocation, no host synchronisation.
  * ------------------------------------------------------------------------------------------ */
-const char* ace_diag_last_error(void);
+const char* ace_diag_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 long ace_diag_partial_doubles(int nplanes, int batch, int steps, long hw);
 int ace_diag_window(const float* const* srcs, const long* strides, const int* rows, const int* wrows, const float* weights, int nw,
                     double* partial, double* tsum, double* series, int nrows, int n_time, int t0, int t_begin, int do_tsum,
@@ -938,7 +942,7 @@ typedef struct ace_phys_fields {
 } ace_phys_fields;
 
 typedef struct ace_physics ace_physics;
-const char* ace_physics_last_error(void);
+const char* ace_physics_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 /* area_weights_lat_host: nlat fp32 weights of one grid column (fme/core/metrics.py:14-32, longitudinally uniform);
  * ak_host / bk_host: nlev + 1 fp32 hybrid-sigma interface coefficients (fme/core/coordinates.py:150-280).  Either may be
  * NULL when no configured correction needs it. */
@@ -964,7 +968,7 @@ int ace_physics_apply(ace_physics* phys, const ace_phys_fields* fields, int batc
  * same fp32-class mode as the SFNO path).  No allocation or host synchronisation outside ace_hpx_weight_create.
  * ------------------------------------------------------------------------------------------ */
 #define ACE_HPX_SLACK_FLOATS 16   /* floats a caller keeps allocated behind a padded tensor (zeroed by ace_hpx_pad) */
-const char* ace_hpx_last_error(void);
+const char* ace_hpx_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 /* HEALPixPadding (healpix_paddings.py:239-611, Karlbauer et al.; "earth2grid" gives the same result): for every cell of
  * the padded mesh [12][nside + 2p][nside + 2p] the two source cells of the unpadded mesh, packed face << 24 | row << 12 |
  * column; padded = 0.5 a + 0.5 b (b == a: plain copy).  Host only. */
@@ -1034,7 +1038,7 @@ int ace_hpx_tconv2(const float* x, const ace_hpx_weight* w, const float* bias, f
  * (pitch >= W; gap columns [W, pitch) defined) with a bound slot as above; the convolutions are ace_hpx_conv_packed /
  * ace_hpx_conv1_packed on the P-format planes ace_ll_pad_planes writes.  Stream-ordered; no allocation or host synchronisation.
  * ------------------------------------------------------------------------------------------ */
-const char* ace_ll_last_error(void);
+const char* ace_ll_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 /* hi / lo [imgs][cpad / 8][(H + 2p) x pitch_p cells][8] (cpad = c rounded up to 8, the extra channels zero; + ACE_HPX_SLACK_FLOATS zero
  * entries behind each, kept allocated by the caller) <- the halo-padded act(scale x + shift): longitude circular (circular = 1, p <= W)
  * or zero, latitude zero, gap columns [W + 2p, pitch_p) zero.  ss (optional): (scale, shift) float pairs at ss[2 (img ss_img_stride + ch)]
@@ -1112,7 +1116,7 @@ typedef struct ace_ocean_fields {
 } ace_ocean_fields;
 
 typedef struct ace_ocean_phys ace_ocean_phys;
-const char* ace_ocean_phys_last_error(void);
+const char* ace_ocean_phys_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 /* area_weights_lat_host: nlat fp32 weights per row; dz_host: (nlev, nlat, nlon) fp32 layer thicknesses (DepthCoordinate.dz,
  * zero where masked); mask_ohc_host: (nlat, nlon) fp32 mask the provider gives for "ocean_heat_content" (NULL: none);
  * mask0_host: (nlat, nlon) fp32 top-level ocean mask (heat content is NaN where it is 0).  All but the first may be NULL
@@ -1207,7 +1211,7 @@ typedef struct ace_ocean_derive_desc {
     int t_chunk;
 } ace_ocean_derive_desc;
 
-const char* ace_ocean_derive_last_error(void);
+const char* ace_ocean_derive_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 /* `desc` is a HOST struct of device pointers (copied into the kernel arguments). */
 int ace_ocean_derive_window(const ace_ocean_derive_desc* desc, void* stream);
 
@@ -1265,7 +1269,7 @@ typedef struct ace_ice_fields {
     int nvars;
 } ace_ice_fields;
 
-const char* ace_ice_budget_last_error(void);
+const char* ace_ice_budget_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 long ace_ice_budget_scratch_bytes(int batch, long hw);
 /* `fields` is a HOST struct of device planes (copied into the kernel arguments). */
 int ace_ice_budget_apply(const ace_ice_fields* fields, double timestep, int batch, int H, int W, void* scratch, void* stream);
@@ -1327,7 +1331,7 @@ int ace_ice_budget_launches(long* flags, long* apply, long* clears);
 #define ACE_PIXEL_MLP_MAX_GRID 512             /* workgroups of a launch */
 #define ACE_PIXEL_MLP_LDS_BYTES 65536          /* a weight blob up to this size is copied into LDS, a larger one streamed from global memory */
 
-const char* ace_pixel_mlp_last_error(void);
+const char* ace_pixel_mlp_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 int ace_pixel_mlp_create(int n_layers, const int* dims, const float* const* w_dev, const float* const* bias_dev, const int* act,
                          int embed_layer, void* stream, void** handle);
 void ace_pixel_mlp_destroy(void* handle);
@@ -1405,7 +1409,7 @@ int ace_pixel_mlp_create2(int n_layers, const int* dims, const float* const* w_d
 #define ACE_DISCO_TARGET_UNITS 2048            /* a unit costs at most 1 / this of a sample's work, where the split allows ... */
 #define ACE_DISCO_MIN_UNIT_COST 4096           /* ... but a unit at or below this many (point, pixel, channel) products is not split */
 
-const char* ace_disco_last_error(void);
+const char* ace_disco_last_error(void);   /* as ace_last_error(): one message per thread for the whole library */
 int ace_disco_create(int H, int W, int K, const long* row_off, const int* hi, const int* wi, const float* vals, const float* w_dev,
                      int in_chans, int out_chans, int groups, int act, int has_embed, void* stream, void** handle);
 void ace_disco_destroy(void* handle);
